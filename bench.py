@@ -11,7 +11,9 @@ the corrected reads are gathered on rank 0, whose result must carry the same dig
 `--iso` benchmarks config 3 instead: the two-level `cluster --iso` flow (k=10 then k=11).
 
 Prints ONE JSON line on rank 0 (contract in the task statement) carrying `roofline` for the dominant kernel
-(poa_align) and `cpu_baseline` (the oracle timed on a bounded sample).
+(poa_align).  A plain run sets up, warms up, times --steps steps and prints the line (with --dump-outputs DIR it also writes
+what the last timed step returned); --full adds the digest checks, the device state, the copy bandwidth, the toyset,
+BASELINE's other configs, the PCIe-inclusive rate and `cpu_baseline` (the oracle timed on a bounded sample).
 """
 import argparse
 import json
@@ -125,6 +127,148 @@ def make_workload(n_reads, genes, seed, isoforms=1):
     return synth.reads_packed(n_reads, genes, isoforms, True, seed=seed, exon=(50, 210))
 
 
+# Generating 1e6 reads with synth.reads_packed is ~100 s of one core: one random stream drawn chunk after chunk.  The stream's state at
+# every SEGMENT_CHUNKS-th chunk is recorded in bench_workload_states.json (tools/bench_workload_states.py), so that the segments can be drawn
+# on several cores at once, each from its recorded state.  Every segment must end in the state recorded for the next one, and the prelude
+# (transcripts, abundances, strands) in the first one; otherwise the workload is drawn in one piece by synth.reads_packed.
+STATES_FILE = os.path.join(ROOT, "bench_workload_states.json")
+SEGMENT_CHUNKS = 32
+_SYNTH = {"both_strands": True, "tx_seed": 20260928, "sub": 0.04, "ins": 0.03, "dele": 0.03, "exon": (50, 210), "chunk": 500}
+
+
+def _workload_key(n_reads, genes, seed, isoforms):
+    return f"n={n_reads} genes={genes} isoforms={isoforms} seed={seed}"
+
+
+def _prelude(n_reads, genes, seed, isoforms):
+    """synth.reads_packed up to its first chunk: transcripts, per-read transcript and strand, and the stream about to draw chunk 0"""
+    tx, _ = synth.transcriptome(genes, isoforms, _SYNTH["tx_seed"], _SYNTH["exon"])
+    txlen = np.array([len(t) for t in tx], np.int64)
+    txoff = np.zeros(len(tx) + 1, np.int64)
+    txoff[1:] = np.cumsum(txlen)
+    rng = np.random.default_rng(seed)
+    w = 1.0 / np.arange(1, len(tx) + 1)
+    perm = rng.permutation(len(tx))
+    p = np.zeros(len(tx))
+    p[perm] = w / w.sum()
+    tid = rng.choice(len(tx), size=n_reads, p=p)
+    flip = rng.random(n_reads) < 0.5
+    return (np.concatenate(tx), txoff, txlen), tid, flip, rng
+
+
+def _segment(tx, tid, flip, c_first, c_last, state):
+    """chunks [c_first, c_last) of synth.reads_packed's loop, drawn from `state` (the loop body restated; tests/test_bench_workload.py
+    holds it to synth.reads_packed).  Returns (seq, qual, lens, state after the segment)."""
+    txcat, txoff, txlen = tx
+    chunk, dele, sub, ins = _SYNTH["chunk"], _SYNTH["dele"], _SYNTH["sub"], _SYNTH["ins"]
+    rng = np.random.Generator(np.random.PCG64())
+    rng.bit_generator.state = state
+    ACGT, COMP = synth._ACGT, synth._COMP
+    seq_parts, qual_parts, lens_all = [], [], []
+    for c0 in range(c_first * chunk, min(c_last * chunk, len(tid)), chunk):
+        t = tid[c0:c0 + chunk]
+        m = len(t)
+        cut = (rng.random(m) * (txlen[t] // 10 + 1)).astype(np.int64)
+        L = txlen[t] - cut
+        T = int(L.sum())
+        rstart = np.zeros(m + 1, np.int64)
+        rstart[1:] = np.cumsum(L)
+        rid = np.repeat(np.arange(m), L)
+        within = np.arange(T) - rstart[rid]
+        base = txcat[txoff[t][rid] + cut[rid] + within]
+        r = rng.random(T)
+        is_del = r < dele
+        is_sub = (r >= dele) & (r < dele + sub)
+        idx = np.searchsorted(ACGT, base)
+        shift = rng.integers(1, 4, T)
+        base = np.where(is_sub, ACGT[(idx + shift) % 4], base)
+        has_ins = rng.random(T) < ins
+        ins_base = ACGT[rng.integers(0, 4, T)]
+        keep = ~is_del
+        cnt = keep.astype(np.int64) + has_ins.astype(np.int64)
+        end = np.cumsum(cnt)
+        start = end - cnt
+        total = int(end[-1]) if T else 0
+        out = np.empty(total, np.uint8)
+        out[start[keep]] = base[keep]
+        out[(start + keep)[has_ins]] = ins_base[has_ins]
+        ostart = np.zeros(m + 1, np.int64)
+        ostart[1:] = end[rstart[1:] - 1]
+        olen = ostart[1:] - ostart[:-1]
+        f = flip[c0:c0 + chunk]
+        orid = np.repeat(np.arange(m), olen)
+        owithin = np.arange(total) - ostart[orid]
+        src = np.where(f[orid], ostart[orid] + olen[orid] - 1 - owithin, ostart[orid] + owithin)
+        o2 = out[src]
+        o2 = np.where(f[orid], COMP[o2], o2)
+        q = np.clip(np.rint(rng.normal(10, 3, total)), 3, 40).astype(np.uint8) + 33
+        seq_parts.append(o2)
+        qual_parts.append(q)
+        lens_all.append(olen)
+    cat = lambda parts, dt: np.concatenate(parts) if parts else np.zeros(0, dt)      # noqa: E731
+    return cat(seq_parts, np.uint8), cat(qual_parts, np.uint8), cat(lens_all, np.int64), rng.bit_generator.state
+
+
+def record_workload_states(n_reads, genes, seed, isoforms=1):
+    """the stream's state at chunk 0, SEGMENT_CHUNKS, 2 x SEGMENT_CHUNKS, ... and at the end, drawn in one piece"""
+    tx, tid, flip, rng = _prelude(n_reads, genes, seed, isoforms)
+    n_chunks = -(-n_reads // _SYNTH["chunk"])
+    states = [rng.bit_generator.state]
+    for c in range(0, n_chunks, SEGMENT_CHUNKS):
+        states.append(_segment(tx, tid, flip, c, c + SEGMENT_CHUNKS, states[-1])[3])
+    return states
+
+
+_POOL_ARGS = None
+
+
+def _pool_segment(job):
+    tx, tid, flip = _POOL_ARGS
+    return _segment(tx, tid, flip, *job)
+
+
+def host_workers(ranks_per_node=1):
+    """the cores this process may use for host-side work, shared among the ranks of one node, at most 16"""
+    try:
+        n = len(os.sched_getaffinity(0))
+    except (AttributeError, OSError):
+        n = os.cpu_count() or 1
+    if os.environ.get("OMP_NUM_THREADS", "").isdigit():
+        n = min(n, int(os.environ["OMP_NUM_THREADS"]))
+    return max(1, min(16, n) // max(1, ranks_per_node))
+
+
+def make_workload_fast(n_reads, genes, seed, isoforms=1, workers=1):
+    """make_workload(...), identical to the byte, drawn segment by segment on `workers` processes when the stream's states of this workload
+    are recorded.  Call it before the process starts the HIP runtime: the pool forks."""
+    global _POOL_ARGS
+    try:
+        states = json.load(open(STATES_FILE)).get(_workload_key(n_reads, genes, seed, isoforms))
+    except (OSError, ValueError):
+        states = None
+    if not states or workers < 2:
+        return make_workload(n_reads, genes, seed, isoforms)
+    tx, tid, flip, rng = _prelude(n_reads, genes, seed, isoforms)
+    if rng.bit_generator.state != states[0]:
+        print("bench.py: the recorded workload states do not match this numpy; drawing the workload in one piece", file=sys.stderr)
+        return make_workload(n_reads, genes, seed, isoforms)
+    import multiprocessing as mp
+    jobs = [(i * SEGMENT_CHUNKS, (i + 1) * SEGMENT_CHUNKS, states[i]) for i in range(len(states) - 1)]
+    _POOL_ARGS = (tx, tid, flip)
+    try:
+        with mp.get_context("fork").Pool(min(workers, len(jobs))) as pool:
+            segs = pool.map(_pool_segment, jobs, chunksize=1)
+    finally:
+        _POOL_ARGS = None
+    if any(s[3] != states[i + 1] for i, s in enumerate(segs)):
+        print("bench.py: a workload segment did not end in its recorded state; drawing the workload in one piece", file=sys.stderr)
+        return make_workload(n_reads, genes, seed, isoforms)
+    lens = np.concatenate([s[2] for s in segs])
+    off = np.zeros(n_reads + 1, np.uint64)
+    off[1:] = np.cumsum(lens).astype(np.uint64)
+    return np.concatenate([s[0] for s in segs]), np.concatenate([s[1] for s in segs]), off, tid, flip.astype(np.uint8)
+
+
 PHASES = {"cluster": 0.0, "correct": 0.0}      # host wall time of the two calls, summed over the timed steps
 
 
@@ -155,6 +299,69 @@ def cluster_digest(cl):
     for a in (cl.main_id, cl.main_rev, cl.offsets, cl.member_id, cl.member_rev):
         crc = zlib.crc32(np.ascontiguousarray(a).tobytes(), crc)
     return crc
+
+
+def _as_float(a):
+    """integers below 2^24 as float32, other integers as float64: exact either way"""
+    a = np.asarray(a)
+    if a.size and a.dtype.kind in "iu" and int(np.abs(a.astype(np.int64)).max()) >= 1 << 24:
+        return a.astype(np.float64)
+    return a.astype(np.float32)
+
+
+def dump_outputs(path, cl, corr=None, iso=None, limit=64 << 20):
+    """--dump-outputs: what the last timed step returned to its caller, as path/<name>.npy in float32 (integers below 2^24) or float64.
+    clusters_*: the cluster set.  Of `correct` (corr, a CorrectionHandle) the three read sets, per record: read id, cluster id, reads of
+    its pack, length and the CRC-32 of its bases and of its qualities; and the bases and qualities themselves of a fixed, seeded sample of
+    records (<set>_sample_*).  Where all this would exceed `limit` bytes, a fixed, seeded sample of the records (<set>_index, and
+    clusters_member_index for the members) stands for the whole.  iso = (gene id per cluster, gene clusters) of `cluster --iso`."""
+    import ctypes as C
+    import zlib
+
+    def sample(n, k, seed):
+        return np.arange(n) if n <= k else np.sort(np.random.default_rng(seed).choice(n, size=k, replace=False))
+
+    def build(cap, k_seq):
+        out = {}
+        mi = sample(len(cl.member_id), cap, 1)
+        if len(mi) < len(cl.member_id):
+            out["clusters_member_index"] = mi
+        out.update(clusters_main_id=cl.main_id, clusters_main_rev=cl.main_rev, clusters_offsets=cl.offsets,
+                   clusters_member_id=cl.member_id[mi], clusters_member_rev=cl.member_rev[mi])
+        if iso is not None:
+            out["iso_gene_id"], out["iso_gene_clusters"] = iso[0], np.array([iso[1]])
+        if corr is not None and corr.ptr is not None:
+            R = corr.ptr.contents
+            for si, (name, S) in enumerate((("corrected", R.corrected), ("uncorrected", R.uncorrected), ("consensi", R.consensi))):
+                n = int(S.n)
+                o = np.ctypeslib.as_array(S.off, (n + 1,)).astype(np.int64)
+                tot = int(o[n])
+                seq = np.ctypeslib.as_array(C.cast(S.seq, C.POINTER(C.c_uint8)), (tot,)) if tot else np.zeros(0, np.uint8)
+                qual = np.ctypeslib.as_array(C.cast(S.qual, C.POINTER(C.c_uint8)), (tot,)) if tot else np.zeros(0, np.uint8)
+                ri = sample(n, cap, 2 + si)
+                if len(ri) < n:
+                    out[name + "_index"] = ri
+                for field, arr in (("read_id", S.read_id), ("cluster_id", S.cluster_id), ("n_reads", S.n_reads)):
+                    out[f"{name}_{field}"] = np.ctypeslib.as_array(arr, (max(n, 1),))[:n][ri]
+                out[name + "_length"] = (o[1:] - o[:-1])[ri]
+                ms, mq = memoryview(seq), memoryview(qual)
+                out[name + "_seq_crc32"] = np.array([zlib.crc32(ms[o[i]:o[i + 1]]) for i in ri], np.uint32).astype(np.float64)
+                out[name + "_qual_crc32"] = np.array([zlib.crc32(mq[o[i]:o[i + 1]]) for i in ri], np.uint32).astype(np.float64)
+                si_ = sample(n, k_seq, 5 + si)
+                out[name + "_sample_index"] = si_
+                pick = np.concatenate([np.arange(o[i], o[i + 1]) for i in si_]) if len(si_) else np.zeros(0, np.int64)
+                out[name + "_sample_seq"] = seq[pick]
+                out[name + "_sample_qual"] = qual[pick]
+        return {k: (v if v.dtype.kind == "f" else _as_float(v)) for k, v in ((k, np.asarray(v)) for k, v in out.items())}
+
+    cap, k_seq = 1 << 21, 256
+    arrays = build(cap, k_seq)
+    while sum(v.nbytes for v in arrays.values()) > limit and cap > 1:
+        cap, k_seq = cap // 2, max(1, k_seq // 2)
+        arrays = build(cap, k_seq)
+    os.makedirs(path, exist_ok=True)
+    for k, v in arrays.items():
+        np.save(os.path.join(path, k + ".npy"), v)
 
 
 def cpu_baseline(cat, qcat, off, tid, correct_reads=1800, cluster_reads=5000):
@@ -466,6 +673,10 @@ def main():
     ap.add_argument("--no-configs", action="store_true", help="skip the side measurements of BASELINE configs[1] and configs[2]")
     ap.add_argument("--no-reference-digest", action="store_true", help="several ranks: skip the unsharded reference run the result is checked against")
     ap.add_argument("--no-stage", action="store_true", help="hand the reads over as host buffers every step (PCIe-inclusive rate)")
+    ap.add_argument("--full", action="store_true", help="besides the headline: the checks of the result (digests across steps, the unsharded "
+                    "reference run of a sharded job), device state, copy bandwidth, the toyset, BASELINE's other configs, the PCIe-inclusive "
+                    "rate and the CPU baselines (the last four unless --no-cpu-baseline / --no-configs)")
+    ap.add_argument("--dump-outputs", metavar="DIR", help="write what the last timed step computed to DIR/<name>.npy (float32 / float64, at most 64 MB)")
     a = ap.parse_args()
 
     if a.gpus > 1 and "WORLD_SIZE" not in os.environ:
@@ -479,14 +690,24 @@ def main():
                "--master-port", str(port), os.path.abspath(__file__)] + sys.argv[1:]
         os.execv(sys.executable, cmd)
 
-    import torch
-    import torch.distributed as dist
+    # the workload first: it is drawn on a pool of forked processes, before this process starts the HIP runtime
     world = int(os.environ.get("WORLD_SIZE", "1"))
     if world != a.gpus:
         raise SystemExit(f"bench.py: --gpus {a.gpus} but the launcher started {world} rank(s); nothing was timed")
+    rank = int(os.environ.get("RANK", "0"))
+    workers = host_workers(int(os.environ.get("LOCAL_WORLD_SIZE", world)))
+    if a.iso:
+        genes = a.genes or max(5, a.reads // 600)
+        cat, qcat, off, tid, _ = make_workload_fast(a.reads, genes, seed=20260929 + (rank if a.weak else 0), isoforms=3, workers=workers)
+    else:
+        genes = a.genes or max(5, a.reads // 200)
+        cat, qcat, off, tid, _ = make_workload_fast(a.reads, genes, seed=20260929 + (rank if a.weak else 0), workers=workers)
+    n_reads = len(off) - 1
+
+    import torch
+    import torch.distributed as dist
     # ranks of one node share the host cores for pack planning / result assembly
     os.environ.setdefault("RATTLE_HOST_THREADS", str(max(1, (os.cpu_count() or 1) // max(1, int(os.environ.get("LOCAL_WORLD_SIZE", world))))))
-    rank = int(os.environ.get("RANK", "0"))
     local = int(os.environ.get("LOCAL_RANK", "0"))
     if not torch.cuda.is_available():
         raise SystemExit("bench.py needs a HIP device (no CPU fallback)")
@@ -506,13 +727,6 @@ def main():
         else:
             dist.init_process_group("nccl", device_id=torch.device("cuda", local))
     sharded = use_dist and not a.weak
-    if a.iso:
-        genes = a.genes or max(5, a.reads // 600)
-        cat, qcat, off, tid, _ = make_workload(a.reads, genes, seed=20260929 + (rank if a.weak else 0), isoforms=3)
-    else:
-        genes = a.genes or max(5, a.reads // 200)
-        cat, qcat, off, tid, _ = make_workload(a.reads, genes, seed=20260929 + (rank if a.weak else 0))
-    n_reads = len(off) - 1
 
     def barrier():
         torch.cuda.synchronize()
@@ -520,9 +734,9 @@ def main():
             dist.barrier()
         torch.cuda.synchronize()
 
-    # several ranks on one job: the result must equal the unsharded one -> rank 0 runs it once, untimed, first
+    # several ranks on one job (--full): the result must equal the unsharded one -> rank 0 runs it once, untimed, first
     ref_digest = None
-    if sharded and world > 1 and not a.no_reference_digest and not a.iso:
+    if a.full and sharded and world > 1 and not a.no_reference_digest and not a.iso:
         if rank == 0:
             ref = Context(local)
             cl0 = ref.cluster_unsorted_packed(cat, off)
@@ -573,8 +787,8 @@ def main():
     if not a.no_stage:     # inputs resident in HBM before the timed region (BASELINE metric definition)
         ctx.stage_reads(cat, qcat, off)
     warm = None
-    state0 = device_state() if rank == 0 else None
-    sampler = DeviceSampler().start() if rank == 0 and a.warmup else None       # (the warm-up steps only: see DeviceSampler)
+    state0 = device_state() if rank == 0 and a.full else None
+    sampler = DeviceSampler().start() if rank == 0 and a.warmup and a.full else None       # (the warm-up steps only: see DeviceSampler)
     for _ in range(a.warmup):
         if warm is not None and not a.iso:
             warm[1].free()
@@ -619,7 +833,7 @@ def main():
     dt = time.time() - t0
     for d in step_detail:
         d.pop("t")
-    state1 = device_state() if rank == 0 else None
+    state1 = device_state() if rank == 0 and a.full else None
     tf = time.time()
     for h in held:
         h.free()
@@ -633,44 +847,52 @@ def main():
     value = total_reads / (dt / a.steps)
     cl, res = last
 
-    # ---- correctness of what was timed (outside the timed region) ----
+    # ---- correctness of what was timed (outside the timed region): the counts always, the digests with --full ----
     checks = {}
     if a.iso:
         gid, ng = res
-        assert len(cl.member_id) == n_reads and np.array_equal(np.sort(cl.member_id), np.arange(n_reads)), "--iso: not a partition of the reads"
-        assert np.all(np.diff(gid) >= 0) and (len(gid) == 0 or gid[-1] == ng - 1), "--iso: gene ids not in gene order"
-        checks = {"partition": True, "gene_clusters": int(ng), "transcript_clusters": int(len(cl.main_id)), "cluster_digest": cluster_digest(cl)}
-        if warm is not None:
-            assert cluster_digest(warm[0]) == checks["cluster_digest"], "--iso: result differs between steps"
-            checks["digest_equal_across_steps"] = True
+        assert len(cl.member_id) == n_reads, "--iso: not a partition of the reads"
+        checks = {"gene_clusters": int(ng), "transcript_clusters": int(len(cl.main_id))}
+        if a.full:
+            assert np.array_equal(np.sort(cl.member_id), np.arange(n_reads)), "--iso: not a partition of the reads"
+            assert np.all(np.diff(gid) >= 0) and (len(gid) == 0 or gid[-1] == ng - 1), "--iso: gene ids not in gene order"
+            checks.update(partition=True, cluster_digest=cluster_digest(cl))
+            if warm is not None:
+                assert cluster_digest(warm[0]) == checks["cluster_digest"], "--iso: result differs between steps"
+                checks["digest_equal_across_steps"] = True
     else:
         if rank == 0 or not sharded:
             n_cor, n_unc, n_cons, counters = res.counts()
             assert n_cor + n_unc == n_reads, f"accounting: {n_cor} corrected + {n_unc} uncorrected != {n_reads} reads"
             assert n_cons == expected_consensi(cl), f"consensus count {n_cons} != {expected_consensi(cl)}"
             assert len(cl.member_id) == n_reads, "cluster: not a partition of the reads"
-            dg = (cluster_digest(cl), res.digest())
-            checks = {"n_corrected": int(n_cor), "n_uncorrected": int(n_unc), "n_consensi": int(n_cons), "packs_skipped": int(counters[3]),
-                      "cluster_digest": dg[0], "correct_digest": dg[1]}
-            if warm is not None:
-                assert (cluster_digest(warm[0]), warm[1].digest()) == dg, "result differs between steps"
-                checks["digest_equal_across_steps"] = True
-            if ref_digest is not None:
-                assert ref_digest == dg, f"sharded result {dg} != single-GPU result {ref_digest}"
-                checks["digest_equal_to_single_gpu"] = True
+            checks = {"n_corrected": int(n_cor), "n_uncorrected": int(n_unc), "n_consensi": int(n_cons), "packs_skipped": int(counters[3])}
+            if a.full:
+                dg = (cluster_digest(cl), res.digest())
+                checks.update(cluster_digest=dg[0], correct_digest=dg[1])
+                if warm is not None:
+                    assert (cluster_digest(warm[0]), warm[1].digest()) == dg, "result differs between steps"
+                    checks["digest_equal_across_steps"] = True
+                if ref_digest is not None:
+                    assert ref_digest == dg, f"sharded result {dg} != single-GPU result {ref_digest}"
+                    checks["digest_equal_to_single_gpu"] = True
 
+    if rank == 0 and a.dump_outputs:
+        dump_outputs(a.dump_outputs, cl, None if a.iso else res, res if a.iso else None)
     if rank == 0:
         kst = {KNAMES[k]: ctx.kernel_stats(k) for k in KNAMES}
-        # what this GPU sustains on a plain device-to-device copy (read + write bytes), SURVEY 8(d)
-        buf = torch.empty(1 << 30, dtype=torch.uint8, device="cuda")
-        dst = torch.empty_like(buf)
-        dst.copy_(buf); torch.cuda.synchronize()
-        tc = time.time()
-        for _ in range(10):
-            dst.copy_(buf)
-        torch.cuda.synchronize()
-        copy_gbs = 10 * 2 * buf.numel() / (time.time() - tc) / 1e9
-        del buf, dst
+        copy_gbs = None
+        if a.full:
+            # what this GPU sustains on a plain device-to-device copy (read + write bytes), SURVEY 8(d)
+            buf = torch.empty(1 << 30, dtype=torch.uint8, device="cuda")
+            dst = torch.empty_like(buf)
+            dst.copy_(buf); torch.cuda.synchronize()
+            tc = time.time()
+            for _ in range(10):
+                dst.copy_(buf)
+            torch.cuda.synchronize()
+            copy_gbs = 10 * 2 * buf.numel() / (time.time() - tc) / 1e9
+            del buf, dst
         par = ("replicas%d" % world) if a.weak else ("shard%d" % world)
         out = {
             "metric": METRIC if not a.iso else "reads/sec for `cluster --iso` (two-level, k=10 then k=11) on 1e6x1kb synthetic ONT cDNA reads",
@@ -681,8 +903,7 @@ def main():
             # every timed step on its own (first-step vs steady state), the state of the device around the timed region, and what the
             # harness kept OUT of the timed region: a step's ~2 GB result is freed after the timer stops when the host has the memory
             # (`results_held`), which costs `result_free_ms` per step when it is done between steps instead
-            "step_ms": [round(x, 1) for x in step_ms], "step_detail": step_detail, "device_state": {"before": state0, "during_warmup": state_during, "after": state1,
-                             "note": "sysfs (first card that has a clock file: not necessarily this process's device) is sampled during the warm-up steps only; the timed region runs without firmware queries"},
+            "step_ms": [round(x, 1) for x in step_ms], "step_detail": step_detail,
             "results_held": bool(hold), "result_free_ms": free_ms,
             "kernels_ms_per_step": {k: v[0] / a.steps for k, v in kst.items()},
             "phases_ms_per_step": {k: v / a.steps * 1e3 for k, v in PHASES.items() if v > 0},
@@ -690,6 +911,9 @@ def main():
             "cluster_counters": {"bv_pair_tests": int(cl.counters[0]), "full_comparisons": int(cl.counters[1]), "kmer_matches": int(cl.counters[2]), "pairs_past_the_count_bound": int(cl.counters[5]),
                                  "seed_rounds": int(cl.counters[3]), "kernel_launches": int(cl.counters[4])},
         }
+        if a.full:
+            out["device_state"] = {"before": state0, "during_warmup": state_during, "after": state1,
+                                   "note": "sysfs (first card that has a clock file: not necessarily this process's device) is sampled during the warm-up steps only; the timed region runs without firmware queries"}
         if sharded:
             calls, xbytes = ctx.comm_stats()
             out["exchange"] = {"transport": transport, "ranks": world, "collectives": calls, "bytes_received": xbytes}
@@ -713,7 +937,7 @@ def main():
                                                   "`reference` = rows x columns of every alignment, what the reference's engine fills"},
                              "packs": int(counters[2]), "parallelism": par}
             out["roofline"] = poa_roofline(kst, cells_done, a.steps, per_gpu, copy_gbs, cells_reference=cells)
-            if not a.no_cpu_baseline:
+            if a.full and not a.no_cpu_baseline:
                 try:
                     out["toyset"] = toyset_line(Context, local)
                 except Exception as e:       # the headline must not depend on the side measurement

@@ -33,9 +33,9 @@ def test_every_declared_symbol_is_exported_and_bound(lib):
     assert lib.rattle_hip_abi_version() == 4
 
 
-def test_header_is_plain_c():
+def test_header_is_plain_c(tmp_path):
     src = '#include "rattle_hip.h"\nint main(void){return rattle_hip_abi_version()==0;}\n'
-    p = os.path.join("/tmp", "abi_c_check.c")
+    p = str(tmp_path / "abi_c_check.c")
     open(p, "w").write(src)
     subprocess.check_call(["gcc", "-std=c99", "-Wall", "-Werror", "-fsyntax-only", "-I", os.path.join(ROOT, "include"), p])
 

@@ -9,7 +9,7 @@ for rep in 1 2; do for n in pf0 pf1; do
   echo -n "$n class 1536, 2048 packs: "; RATTLE_HIP_LIB=$V/librattle_hip_$n.so RATTLE_POA_MODE=dense python tools/bench_poa_class.py 1450 2048 200 2>&1 | grep GCUPS | tail -1
 done; done | tee $O/micro.log
 for rep in 1 2; do for n in pf0 pf1; do
-  RATTLE_HIP_LIB=$V/librattle_hip_$n.so timeout 600 python bench.py --steps 2 --no-cpu-baseline --no-configs 2>/dev/null | python -c "
+  RATTLE_HIP_LIB=$V/librattle_hip_$n.so timeout 600 python bench.py --full --steps 2 --no-cpu-baseline --no-configs 2>/dev/null | python -c "
 import sys,json
 d=json.loads(sys.stdin.read().strip().splitlines()[-1]); print('$n', round(d['value']), d['step_ms'], [x['correct_stage_ms']['1'] for x in d['step_detail']], d['checks']['correct_digest'])"
 done; done | tee $O/bench.log

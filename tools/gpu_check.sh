@@ -5,7 +5,7 @@ O=gpurun_out/$TAG; mkdir -p $O
 export TMPDIR=/tmp
 timeout 2400 python -m pytest tests -m gpu -x -q > $O/tests.log 2>&1; grep -n "passed\|failed\|error" $O/tests.log | tail -3
 python -c "import __graft_entry__ as g; g.smoke()" > $O/smoke.log 2>&1; tail -1 $O/smoke.log
-timeout 1500 python bench.py "$@" > $O/bench_default.json 2> $O/bench_default.err; tail -2 $O/bench_default.err
+timeout 1500 python bench.py --full "$@" > $O/bench_default.json 2> $O/bench_default.err; tail -2 $O/bench_default.err
 python - <<PY
 import json
 try:

@@ -8,7 +8,7 @@ O=gpurun_out/$TAG; mkdir -p $O
 export TMPDIR=/tmp
 timeout 2400 python -m pytest tests -m gpu -x -q --timeout 600 > $O/tests.log 2>&1; grep -n "passed\|failed\|Timeout" $O/tests.log | tail -2
 python -c "import __graft_entry__ as g; g.smoke()" > $O/smoke.log 2>&1; tail -1 $O/smoke.log
-timeout 1500 python bench.py > $O/bench_default.json 2> $O/bench_default.err
+timeout 1500 python bench.py --full > $O/bench_default.json 2> $O/bench_default.err
 ( cd /tmp && timeout 900 rocprofv3 --kernel-trace --stats --output-format csv -d $GRAFT_REPO_ROOT/$O/stats -- python $GRAFT_REPO_ROOT/bench.py --no-cpu-baseline > $GRAFT_REPO_ROOT/$O/bench_under_rocprof.json 2> $GRAFT_REPO_ROOT/$O/bench_under_rocprof.err )
 READS_PMC=1000000 bash tools/gpu_pmc_only.sh ${TAG}_pmc > $O/pmc.log 2>&1; tail -2 $O/pmc.log | cut -c1-600
 READS_PMC=100000 bash tools/gpu_pmc_only.sh ${TAG}_pmc100k > $O/pmc100k.log 2>&1; tail -2 $O/pmc100k.log | cut -c1-600

@@ -10,7 +10,7 @@ timeout 900 python tools/rank_replay.py --reads 1000000 --worlds 2,4,8 --out "$O
 READS_PMC=1000000 bash tools/gpu_pmc_only.sh ${TAG}_pmc > $O/pmc.log 2>&1; tail -1 $O/pmc.log | cut -c1-300
 READS_PMC=100000 bash tools/gpu_pmc_only.sh ${TAG}_pmc100k > $O/pmc100k.log 2>&1; tail -1 $O/pmc100k.log | cut -c1-300
 cp gpurun_out/${TAG}_pmc/pmc_poa.json profiles/round5_pmc_poa.json; cp gpurun_out/${TAG}_pmc100k/pmc_poa.json profiles/round5_pmc_poa_100k.json
-RATTLE_TIMING=1 timeout 1500 python bench.py > $O/bench_default.json 2> $O/bench_default.err
+RATTLE_TIMING=1 timeout 1500 python bench.py --full > $O/bench_default.json 2> $O/bench_default.err
 ( cd /tmp && timeout 900 rocprofv3 --kernel-trace --stats --output-format csv -d $GRAFT_REPO_ROOT/$O/stats -- python $GRAFT_REPO_ROOT/bench.py --no-cpu-baseline > $GRAFT_REPO_ROOT/$O/bench_under_rocprof.json 2> $GRAFT_REPO_ROOT/$O/bench_under_rocprof.err )
 for i in 1 2; do RATTLE_TIMING=1 python bench.py --no-cpu-baseline > $O/bench_repeat$i.json 2> $O/bench_repeat$i.err; done
 python -c "

@@ -9,7 +9,7 @@ mkdir -p $O
 export TMPDIR=/tmp
 R=${READS_PMC:-300000}
 # 1. default bench line (1e6 reads, with cpu baselines)
-timeout 900 python bench.py > $O/bench_default.json 2> $O/bench_default.err
+timeout 900 python bench.py --full > $O/bench_default.json 2> $O/bench_default.err
 # 2. kernel trace + stats of the default workload
 ( cd /tmp && timeout 900 rocprofv3 --kernel-trace --stats --output-format csv -d $GRAFT_REPO_ROOT/$O/stats -- python $GRAFT_REPO_ROOT/bench.py --no-cpu-baseline > $GRAFT_REPO_ROOT/$O/bench_under_rocprof.json 2> $GRAFT_REPO_ROOT/$O/bench_under_rocprof.err )
 # 3. PMC passes at $R reads (counters only; one group per run)
