@@ -2732,8 +2732,9 @@ __global__ __launch_bounds__(64 * NW * pk_teams(RING, PK), poa_min_waves(CPL, NW
                         // certificate.  Only for a pack three quarters of whose alignments so far HAD a band (a pack of noisy reads belongs to the full-row kernels,
                         // which spread a row over four to sixteen wavefronts); A.debug bit 3: always (tests)
                         const bool strips_ok = (A.debug & 8u) || (n_band_ok >= 8u && 4u * n_band_ok >= 3u * (q - q0));
+                        // (s_bc[1], the edges the columns do not order, is this alignment's only where the flags fitted; otherwise it is stale)
                         const uint32_t n_strips = (Lu + 511u) >> 9;
-                        if (!band_on && strips_ok && !s_bc[1] && (uint64_t)n_strips * (nu + 1u) * 512u <= A.cell_cap) {
+                        if (!band_on && strips_ok && !(fits_flags && s_bc[1]) && (uint64_t)n_strips * (nu + 1u) * 512u <= A.cell_cap) {
                             const uint32_t Lpb = (Lu + 7u) & ~7u;
                             uint32_t brs = 16;
                             while (brs >= 2u && band_lds_bytes(brs, 8, Lpb) > rbu) brs >>= 1;
@@ -3547,6 +3548,7 @@ struct poa_env {
     int streams = 0;                     // RATTLE_POA_STREAMS: streams the classes of a pass are dealt onto
     bool timing = false;                 // RATTLE_TIMING: one line per class and pass
     int head_start_us = 30;              // RATTLE_POA_HEAD_START_US: see poa_head_start (0: none)
+    bool noring = false;                 // RATTLE_POA_NORING=1: classes 4 .. 7 take their forms without a ring, as if the bitmaps left no LDS for one (tests)
     poa_env() {
         timeline = getenv("RATTLE_POA_TIMELINE"); mode = getenv("RATTLE_POA_MODE"); profile_json = getenv("RATTLE_POA_PROFILE_JSON");
         if (const char *v = getenv("RATTLE_POA_NODE_CAP")) node_cap = (uint32_t)std::max(64, atoi(v));
@@ -3557,6 +3559,7 @@ struct poa_env {
         if (const char *v = getenv("RATTLE_POA_STREAMS")) streams = atoi(v);
         timing = getenv("RATTLE_TIMING") != nullptr;
         if (const char *v = getenv("RATTLE_POA_HEAD_START_US")) head_start_us = std::max(0, std::min(1000, atoi(v)));
+        if (const char *v = getenv("RATTLE_POA_NORING")) noring = atoi(v) != 0;
     }
 };
 
@@ -3795,8 +3798,8 @@ int poa_device_run(rattle_ctx *ctx, const uint8_t *d_seq_in, const uint64_t *d_o
         };
         // a retry pass with a huge graph: the node bitmaps leave no room for a ready-made ring -- fall back to the dense form (2 bytes per cell)
         if (gc < 4 && P.V->pk != 1 && P.V->pk != 8 && (lds_bytes(P.V) > 158u * 1024 || !mt_ring_ok)) { P.V = &k_dense[gc]; A.ring_slots = A.ring_reach = A.ring_slack = 0; A.o_planm = take(0); A.band = 0; }
-        if ((gc == 4 || gc == 5 || gc == 6) && lds_bytes(P.V) > 158u * 1024) P.V = &k_noring[gc - 4];
-        if (gc == POA_CLASSES - 1 && lds_bytes(P.V) > 158u * 1024) P.V = &k_long_noring;
+        if ((gc == 4 || gc == 5 || gc == 6) && (lds_bytes(P.V) > 158u * 1024 || ENV.noring)) P.V = &k_noring[gc - 4];
+        if (gc == POA_CLASSES - 1 && (lds_bytes(P.V) > 158u * 1024 || ENV.noring)) P.V = &k_long_noring;
         P.shm = lds_bytes(P.V);
         A.node_cap = ncap; A.edge_cap = ecap; A.cell_cap = ccap; A.aln_cap = acap; A.spill_cap = scap; A.seq_cap = lds_seq;
         return o;
@@ -3927,10 +3930,10 @@ int poa_device_run(rattle_ctx *ctx, const uint8_t *d_seq_in, const uint64_t *d_o
             aoff += P.per_slot * P.n_slots;
             qoff += (uint32_t)P.todo.size();
             if (ENV.timing)
-                fprintf(stderr, "[rattle]     poa class %s%u cols (%u waves x %u, %s %u%s) pass %d: %zu packs, %u slots x %.1f MB, %d blocks/CU\n",
+                fprintf(stderr, "[rattle]     poa class %s%u cols (%u waves x %u, %s %u%s) pass %d: %zu packs, %u slots x %.1f MB, %d blocks/CU, group %d pk %u%s\n",
                         poa_group_class(c) == POA_CLASSES - 1 ? "> 8192: segments of " : poa_group_band(c) ? (poa_group_chain(c) ? "(band, long chains) " : "(band) ") : c >= 12 ? "(long chains) " : c >= POA_CLASSES ? "(shallow packs) " : "", 64 * P.V->nw * P.V->cpl, P.V->nw, P.V->cpl,
                         P.V->pk == 7 ? "teams" : "ring", P.V->ring, P.V->pk == 7 ? (", ring " + std::to_string(A.ring_slots) + " reach " + std::to_string(A.ring_reach)).c_str() : "", pass, P.todo.size(), P.n_slots,
-                        P.per_slot / 1e6, P.bpc);
+                        P.per_slot / 1e6, P.bpc, c, P.V->pk, P.V->pk == 8 ? (" band " + std::to_string(A.band)).c_str() : "");      // (group, PK and the band's LDS bytes: which instance ran, for the tests)
         }
         if (e != hipSuccess) { set_error(std::string("poa setup: ") + hipGetErrorString(e)); rc = RATTLE_ERR_HIP; break; }
         {
@@ -4036,7 +4039,7 @@ int poa_device_run(rattle_ctx *ctx, const uint8_t *d_seq_in, const uint64_t *d_o
                     fprintf(stderr, "[rattle]     poa: %zu pack(s) of group %d have an alignment without a certified band (or outgrew the band's slot): again over the full rows (the last one: sequence %llu of its pack, %llu nt against %llu rows, best score in the band %llu)\n",
                             P.todo.size(), c, dbg[1] & 0xFFFFFFFFu, dbg[0] >> 32, dbg[0] & 0xFFFFFFFFu, dbg[1] >> 32);
                 }
-                P.no_band = true; P.rounds = 0; P.node_cap = ENV.node_cap ? ENV.node_cap : 10240u; P.cell_cap = 24ull << 20;
+                P.no_band = true; P.rounds = 0; P.clamped = false; P.node_cap = ENV.node_cap ? ENV.node_cap : 10240u; P.cell_cap = 24ull << 20;      // (a clamp was the band slot's)
                 continue;
             }
             if (!P.todo.empty()) {

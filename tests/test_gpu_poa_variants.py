@@ -1,0 +1,451 @@
+"""Every kernel C instance and every pack group of poa_device_run against the oracle, byte for byte.
+
+poa_device_run sorts the packs of a call into groups (column class, shallow or deep, long chain, band) and picks one instance of
+poa_kernel per group from its variant tables by load, LDS room, arena budget and what failed in the pass before.  Each case here
+reaches some of them on purpose and reads which ones ran from the RATTLE_TIMING line of every group and pass (`group G pk P`, and the
+band's LDS bytes for PK 8).  VARIANTS and GROUPS name the case that reaches each instance and group kind;
+tests/test_poa_variant_inventory.py keeps them equal to what poa.hip has (a variant added without a case fails there, on CPU)."""
+import re
+
+import numpy as np
+import pytest
+
+from test_gpu_poa import _band_failure_packs, _near_identical_pack
+
+pytestmark = pytest.mark.gpu
+
+# (CPL, RING, NW, PK) of every distinct POA_VARIANT in poa.hip, the ring macros resolved -> the case whose timing lines must show it
+VARIANTS = {
+    (4, 8, 4, 1): "test_class_edges_in_every_form[dense]",
+    (6, 4, 4, 1): "test_class_edges_in_every_form[dense]",
+    (8, 8, 4, 1): "test_class_edges_in_every_form[dense]",
+    (10, 8, 4, 1): "test_class_edges_in_every_form[dense]",
+    (4, 4, 4, 7): "test_class_edges_in_every_form[mt4]",
+    (6, 4, 4, 7): "test_class_edges_in_every_form[mt4]",
+    (8, 4, 4, 7): "test_class_edges_in_every_form[mt4]",
+    (10, 4, 4, 7): "test_class_edges_in_every_form[mt4]",
+    (4, 2, 4, 7): "test_class_edges_in_every_form[mt2]",
+    (6, 2, 4, 7): "test_class_edges_in_every_form[mt2]",
+    (8, 2, 4, 7): "test_class_edges_in_every_form[mt2]",
+    (10, 2, 4, 7): "test_class_edges_in_every_form[mt2]",
+    (4, 1, 4, 7): "test_class_edges_in_every_form[mt1]",
+    (6, 1, 4, 7): "test_class_edges_in_every_form[mt1]",
+    (8, 1, 4, 7): "test_class_edges_in_every_form[mt1]",
+    (10, 1, 4, 7): "test_class_edges_in_every_form[mt1]",
+    (8, 4, 8, 3): "test_wide_and_segmented_class_edges",
+    (8, 4, 12, 3): "test_wide_and_segmented_class_edges",
+    (8, 4, 16, 3): "test_wide_and_segmented_class_edges",
+    (8, 3, 16, 2): "test_wide_and_segmented_class_edges",
+    (16, 0, 4, 0): "test_no_ring_forms",
+    (24, 0, 4, 0): "test_no_ring_forms",
+    (32, 0, 4, 0): "test_no_ring_forms",
+    (8, 0, 16, 2): "test_no_ring_forms",
+    (4, 8, 1, 8): "test_one_wavefront_band[rows]",
+    (4, 8, 4, 8): "test_long_chains[default]",
+}
+
+# group kinds of poa_device_run (POA_GROUPS): 0-7 column classes, 8-11 shallow packs of classes 4-7, 12-15 long chains of classes 0-3,
+# 16-19 band packs of classes 0-3, 20-23 band long chains -> the case whose timing lines must show it
+GROUPS = {
+    0: "test_class_edges_in_every_form[dense]", 1: "test_class_edges_in_every_form[dense]",
+    2: "test_class_edges_in_every_form[dense]", 3: "test_class_edges_in_every_form[dense]",
+    4: "test_deep_long_read_groups", 5: "test_deep_long_read_groups", 6: "test_deep_long_read_groups", 7: "test_deep_long_read_groups",
+    8: "test_wide_and_segmented_class_edges", 9: "test_wide_and_segmented_class_edges",
+    10: "test_wide_and_segmented_class_edges", 11: "test_wide_and_segmented_class_edges",
+    12: "test_long_chains[mt2]", 13: "test_long_chains[mt2]", 14: "test_long_chains[mt2]", 15: "test_long_chains[mt2]",
+    16: "test_one_wavefront_band[rows]", 17: "test_one_wavefront_band[rows]",
+    18: "test_one_wavefront_band[rows]", 19: "test_one_wavefront_band[rows]",
+    20: "test_long_chains[default]", 21: "test_long_chains[default]", 22: "test_long_chains[default]", 23: "test_long_chains[default]",
+}
+
+POA_CHAIN_SEQS = 256
+POA_BAND_SPREAD = 400
+POA_SHALLOW_READS = 40
+CLASS_COLS = (1024, 1536, 2048, 2560, 4096, 6144, 8192)
+
+_LINE = re.compile(r"poa class (?P<prefix>.*?)(?P<cols>\d+) cols \((?P<nw>\d+) waves x (?P<cpl>\d+), (?:ring|teams) (?P<ring>\d+)"
+                   r"(?:, ring (?P<slots>\d+) reach \d+)?\) pass (?P<pass>\d+): (?P<packs>\d+) packs, \d+ slots x (?P<mb>[\d.]+) MB, "
+                   r"\d+ blocks/CU, group (?P<group>\d+) pk (?P<pk>\d+)(?: band (?P<band>\d+))?")
+
+
+def _lines(err):
+    out = []
+    for m in _LINE.finditer(err):
+        d = {k: int(v) for k, v in m.groupdict().items() if k not in ("prefix", "mb") and v is not None}
+        d["mb"] = float(m["mb"])
+        d["variant"] = (d["cpl"], d["ring"], d["nw"], d["pk"])
+        out.append(d)
+    return out
+
+
+def _group_of(pack, band=False):
+    """poa_device_run's group of one pack (lengths and depth only)"""
+    m = max(len(s) for s in pack)
+    lens = [len(s) for s in pack if s]
+    cls = 0
+    while cls < len(CLASS_COLS) and m > CLASS_COLS[cls]:
+        cls += 1
+    if cls >= 4 and len(pack) <= POA_SHALLOW_READS:
+        cls += 4
+    band_pack = band and cls < 4 and m - min(lens) <= POA_BAND_SPREAD
+    if cls < 4 and len(pack) > POA_CHAIN_SEQS:
+        cls += 12
+    if band_pack:
+        cls += 8 if cls >= 12 else 16
+    return cls
+
+
+_ORACLE = {}
+
+
+def _want(oracle, pack):
+    """the oracle's rows and cells of one pack (cached: several cases send the same packs under other forms).  The AVX2 rows are exact
+    where they run (5 L + 64 < 32 000; the oracle keeps the scalar loops elsewhere)."""
+    key = tuple(pack)
+    if key not in _ORACLE:
+        oracle.set_poa_simd(True)
+        try:
+            _ORACLE[key] = oracle.poa_msa(list(pack))
+        finally:
+            oracle.set_poa_simd(False)
+    return _ORACLE[key]
+
+
+def _run(gpu_ctx, oracle, capfd, monkeypatch, packs, env=None):
+    """one call of the MSA entry with RATTLE_TIMING on; every pack's rows == the oracle's, counters[0] == the oracle's cells"""
+    monkeypatch.setenv("RATTLE_TIMING", "1")
+    for k, v in (env or {}).items():
+        monkeypatch.setenv(k, v)
+    capfd.readouterr()
+    rows, width, counters = gpu_ctx.poa_msa(packs)
+    err = capfd.readouterr().err
+    cells = 0
+    for p, pack in enumerate(packs):
+        want, c = _want(oracle, pack)
+        cells += c
+        assert width[p] == len(want[0]), p
+        assert rows[p] == want, p
+    assert int(counters[0]) == cells
+    lines = _lines(err)
+    assert lines, err[-2000:]
+    return counters, lines
+
+
+def _assert_reached(request, lines):
+    """the instances and group kinds VARIANTS / GROUPS credit to this case ran in it"""
+    name = request.node.name
+    seen_v = {d["variant"] for d in lines}
+    seen_g = {d["group"] for d in lines}
+    want_v = {v for v, t in VARIANTS.items() if t == name}
+    want_g = {g for g, t in GROUPS.items() if t == name}
+    assert want_v <= seen_v, (sorted(want_v - seen_v), sorted(seen_v))
+    assert want_g <= seen_g, (sorted(want_g - seen_g), sorted(seen_g))
+
+
+# ---- packs ----
+_ACGT = np.frombuffer(b"ACGT", np.uint8)
+
+
+def _random_seq(rng, n):
+    return _ACGT[rng.integers(0, 4, n)]
+
+
+def _subs(rng, a, rate):
+    b = a.copy()
+    hit = rng.random(len(b)) < rate
+    b[hit] = _ACGT[rng.integers(0, 4, int(hit.sum()))]
+    return b
+
+
+def _noisy(rng, a, err):
+    """substitutions, deletions and insertions at err / 3 each"""
+    r = rng.random(len(a))
+    s = _subs(rng, a, err / 3)[r >= err / 3]
+    pos = np.sort(rng.integers(0, len(s) + 1, int(err / 3 * len(s))))
+    return np.insert(s, pos, _ACGT[rng.integers(0, 4, len(pos))])
+
+
+def _edge_pack(L, depth=3, seed=0):
+    """the longest read exactly L nt: copies of one random sequence with 1 % substitutions, the last 5'-truncated"""
+    rng = np.random.default_rng(L * 7 + seed)
+    base = _random_seq(rng, L)
+    pack = [base.tobytes()] + [_subs(rng, base, 0.01).tobytes() for _ in range(depth - 2)]
+    if depth > 2:
+        pack.append(_subs(rng, base[int(rng.integers(1, 1 + L // 10)):], 0.01).tobytes())
+    else:
+        pack.append(_subs(rng, base, 0.01).tobytes())      # (the read aligned: L columns)
+    return pack
+
+
+def _score_packs(L):
+    """identical reads (H reaches 5 L: 12 800 at 2560 columns, 40 960 at 8192 -- beyond int16), and the same with a mismatch in the last
+    column and one 15 columns before it: the best cell is not the last column, and rows tie"""
+    rng = np.random.default_rng(L + 99)
+    x = _random_seq(rng, L)
+    last = x.copy(); last[-1] = _ACGT[(int(np.nonzero(_ACGT == x[-1])[0][0]) + 1) % 4]
+    near = x.copy(); near[-15] = _ACGT[(int(np.nonzero(_ACGT == x[-15])[0][0]) + 2) % 4]
+    x, last, near = x.tobytes(), last.tobytes(), near.tobytes()
+    return [[x, x, x], [x, last, x, near]]
+
+
+def _chain_pack(rng, lmax, n, err=0.003):
+    """a POA #3 group: n near-identical sequences, 5'-truncated by up to POA_BAND_SPREAD - 20 nt, the longest exactly lmax"""
+    base = _random_seq(rng, lmax)
+    pack = [base.tobytes()]
+    for _ in range(n - 1):
+        pack.append(_subs(rng, base[int(rng.integers(0, POA_BAND_SPREAD - 20)):], err).tobytes())
+    return pack
+
+
+# ---- the one-wavefront band ----
+def _cheap_band_packs(n):
+    rng = np.random.default_rng(4242)
+    packs = []
+    while len(packs) < n:
+        p = _near_identical_pack(rng, int(rng.integers(300, 451)), int(rng.integers(3, 5)), 0.004, trunc=0.05)
+        if max(len(s) for s in p) <= 1024 and max(len(s) for s in p) - min(len(s) for s in p) <= POA_BAND_SPREAD:
+            packs.append(p)
+    return packs
+
+
+def _band_edge_packs(lengths):
+    """band packs whose longest read sits at a class or band-strip edge, lengths spread by less than POA_BAND_SPREAD"""
+    rng = np.random.default_rng(808)
+    packs = []
+    for L in lengths:
+        for k in range(2):
+            base = _random_seq(rng, L)
+            p = [base.tobytes()] + [_subs(rng, base[int(rng.integers(0, 300)):], 0.003).tobytes() for _ in range(2 + k)]
+            packs.append(p)
+    return packs
+
+
+def _band_slots(band_bytes, qcap):
+    """ring slots of a PK 8 launch from A.band (poa.hip band_lds_bytes): 8 slots of 4 columns per lane, or 4 (or the 2 x 8 last resort)"""
+    if band_bytes == 8 * 1280 + (qcap // 4 + 66) * 8 + 256:
+        return 8
+    if band_bytes == max(4 * 1280 + (qcap // 4 + 66) * 8 + 256, 2 * 2560 + (qcap // 8 + 66) * 16 + 256):
+        return 4
+    return None
+
+
+def _device_cus():
+    """compute units of device 0, from the HIP runtime the library runs on (hipDeviceAttributeMultiprocessorCount = 63)"""
+    import ctypes
+    from rattle_amd._lib import load
+    hip = load()                                   # (dlsym through the library finds the runtime it links)
+    n = ctypes.c_int(0)
+    assert hip.hipDeviceGetAttribute(ctypes.byref(n), 63, 0) == 0
+    assert 8 <= n.value <= 1024, n.value
+    return n.value
+
+
+@pytest.mark.parametrize("form", ["rows", "strips"])
+def test_one_wavefront_band(gpu_ctx, oracle, capfd, monkeypatch, request, form):
+    """More than four band packs per CU: every band group takes k_band1 (one wavefront per pack, ten or more per CU), whose ring has 8
+    slots or, where the bitmaps and the sequence leave too little LDS, 4.  All packs distinct (the queue is sorted by bases: copies would
+    sit side by side and hide stale slot state).  Two calls: with no band pack longer than 450 nt in class 0 its group keeps the 8-slot
+    ring; with the 512 / 513 / 1024 packs it takes 4.  strips: RATTLE_POA_DEBUG=8, an alignment without a band runs the full rows as strips."""
+    n_cu = _device_cus()
+    cheap = _cheap_band_packs(-(-33 * n_cu // 8))
+    env = {"RATTLE_POA_BAND": "1"}
+    if form == "strips":
+        env["RATTLE_POA_DEBUG"] = "8"
+    slots_seen = set()
+    all_lines = []
+    for edges in ((1025, 1536, 1537, 2048, 2049, 2560), (512, 513, 1024, 1025, 1536, 1537, 2048, 2049, 2560)):
+        edge_packs = _band_edge_packs(edges)
+        packs = cheap + edge_packs
+        assert len(set(map(tuple, packs))) == len(packs)
+        groups = {}
+        for p in packs:
+            groups.setdefault(_group_of(p, band=True), []).append(p)
+        assert set(groups) == {16, 17, 18, 19}
+        counters, lines = _run(gpu_ctx, oracle, capfd, monkeypatch, packs, env)
+        assert int(counters[5]) >= 1, counters                    # alignments with a certified band: a band really ran
+        first = [d for d in lines if d["pass"] == 0]
+        assert {d["group"] for d in first} == set(groups)
+        for d in first:
+            assert d["variant"] == (4, 8, 1, 8), d                 # "1 waves x 4": k_band1 for every band group
+            tl = max(len(s) for p in groups[d["group"]] for s in p)
+            qcap = ((tl + 3) // 4 * 4 + 15) & ~15
+            slots = _band_slots(d["band"], qcap)
+            assert slots is not None, d
+            slots_seen.add(slots)
+        all_lines += lines
+    assert slots_seen == {4, 8}, slots_seen
+    _assert_reached(request, all_lines)
+
+
+# ---- long chains: packs of more than POA_CHAIN_SEQS sequences ----
+def _long_chain_packs():
+    rng = np.random.default_rng(300)
+    return [_chain_pack(rng, 600, 300), _chain_pack(rng, 1030, 260), _chain_pack(rng, 1540, 260), _chain_pack(rng, 2050, 260)]
+
+
+@pytest.mark.parametrize("mode", ["default", "mt2", "dense"])
+def test_long_chains(gpu_ctx, oracle, capfd, monkeypatch, request, mode):
+    """POA #3 of a large cluster: one pack of 257-300 near-identical sequences per packed class.  Band on: the band long-chain groups
+    20-23 (k_band4: one chain per group is far below four per CU); forced mt2: no band, the long-chain groups 12-15 on two teams; forced
+    dense: the band, and the barrier form for what loses it."""
+    packs = _long_chain_packs()
+    env = {"RATTLE_POA_BAND": "1"}
+    if mode != "default":
+        env["RATTLE_POA_MODE"] = mode
+    band = mode != "mt2"
+    want_groups = {_group_of(p, band=band) for p in packs}
+    assert want_groups == ({20, 21, 22, 23} if band else {12, 13, 14, 15})
+    counters, lines = _run(gpu_ctx, oracle, capfd, monkeypatch, packs, env)
+    first = [d for d in lines if d["pass"] == 0]
+    assert {d["group"] for d in first} == want_groups
+    for d in first:
+        assert d["variant"] == ((4, 8, 4, 8) if band else ((4, 6, 8, 10)[d["group"] - 12], 2, 4, 7)), d
+    if band:
+        assert int(counters[5]) >= 1, counters
+    _assert_reached(request, lines)
+
+
+def test_noisy_long_chain_without_band(gpu_ctx, oracle, capfd, monkeypatch):
+    """A noisy POA #3 group of 270 reads in class 1 with the band off: group 13, the teams form chosen by the chains' own load (mt4)."""
+    rng = np.random.default_rng(270)
+    tx = _random_seq(rng, 1150)
+    pack = sorted((_noisy(rng, tx[int(rng.integers(0, 60)):], 0.03).tobytes() for _ in range(270)), key=lambda s: -len(s))
+    assert 1024 < len(pack[0]) <= 1536 and _group_of(pack) == 13
+    counters, lines = _run(gpu_ctx, oracle, capfd, monkeypatch, [pack], {"RATTLE_POA_BAND": "0"})
+    assert [d["group"] for d in lines if d["pass"] == 0] == [13]
+    assert lines[0]["variant"] == (6, 4, 4, 7), lines[0]
+
+
+# ---- the wide classes without a ring ----
+_NORING = {4: (16, 0, 4, 0), 5: (24, 0, 4, 0), 6: (32, 0, 4, 0), 7: (8, 0, 16, 2)}
+
+
+def test_no_ring_forms(gpu_ctx, oracle, capfd, monkeypatch, request):
+    """RATTLE_POA_NORING=1: classes 4-7 take k_noring / k_long_noring, as when the node bitmaps leave no LDS for the ring; lengths at the
+    class edges and inside the classes (the sequence's LDS copy is sized by the ring form's columns per thread)."""
+    packs = [_edge_pack(L, 2) for L in (3000, 4096, 5000, 6144, 7010, 8192, 8193)]
+    counters, lines = _run(gpu_ctx, oracle, capfd, monkeypatch, packs, {"RATTLE_POA_NORING": "1"})
+    for d in lines:
+        assert d["variant"] == _NORING[d["group"] - 4], d
+        assert d["ring"] == 0, d                                  # "ring 0"
+    assert {d["group"] for d in lines} == {8, 9, 10, 11}
+    _assert_reached(request, lines)
+
+
+def _bit_words(ncap):
+    return (ncap + 63) // 64 * 2
+
+
+def _wide_lds_bytes(ncap, tl, cpl=8, ring=4, nw=16):
+    """poa.hip plan_class: LDS of a PK 3 launch = the sequence (qcap) + poa_region_bytes + 64"""
+    qcap = ((tl + cpl - 1) // cpl * cpl + 15) & ~15
+    ring_words = cpl if 64 * nw * cpl > 2048 else cpl // 2
+    ring_bytes = ring * 64 * nw * ring_words * 4 + ring * 4 * max(nw, 4)
+    return qcap + (2 * _bit_words(ncap) + 512) * 4 + ring_bytes + 64
+
+
+def test_no_ring_when_the_bitmaps_fill_lds(gpu_ctx, oracle, capfd, monkeypatch):
+    """The natural trigger, no switch: a class-6 pack of ~87 k bases whose node capacity (RATTLE_POA_NODE_CAP=120000, so the bases
+    decide it) gives bitmaps that leave the 4-row ring of <8, 4, 16, 3> no room under 158 KB: k_noring[2] runs."""
+    rng = np.random.default_rng(6)
+    base = _random_seq(rng, 7300)
+    pack = [base.tobytes()] + [_subs(rng, base[int(rng.integers(1000, 1300)):], 0.003).tobytes() for _ in range(13)]
+    tb = sum(map(len, pack))
+    ncap = (min(120000, tb + 1) + 31) & ~31
+    assert _group_of(pack) == 10 and tb > 85000
+    assert _wide_lds_bytes(ncap, 7300) > 158 * 1024
+    limit = max(n for n in range(0, 120000, 64) if _wide_lds_bytes(n, 8192) <= 158 * 1024)
+    assert 80000 < limit < 82000 and ncap > limit                 # the limit: ~81 k nodes in class 6
+    counters, lines = _run(gpu_ctx, oracle, capfd, monkeypatch, [pack], {"RATTLE_POA_NODE_CAP": "120000"})
+    assert [(d["group"], d["variant"]) for d in lines if d["pass"] == 0] == [(10, (32, 0, 4, 0))]
+
+
+# ---- deep long-read packs ----
+def test_deep_long_read_groups(gpu_ctx, oracle, capfd, monkeypatch, request):
+    """More than POA_SHALLOW_READS reads in a pack whose longest read is over 2560 nt: groups 4-7 (slots sized by depth).  Noisy packs of
+    45-48 reads at ~3000 and ~5000 nt; for classes 6 and 7, one long read and 44 short pieces of it."""
+    rng = np.random.default_rng(45)
+    packs = []
+    for L, n in ((3000, 45), (5000, 48)):
+        tx = _random_seq(rng, L)
+        packs.append(sorted((_noisy(rng, tx[int(rng.integers(0, 100)):], 0.02).tobytes() for _ in range(n)), key=lambda s: -len(s)))
+    for L in (7000, 9000):
+        tx = _random_seq(rng, L)
+        pieces = []
+        for _ in range(44):
+            a = int(rng.integers(0, L - 400))
+            pieces.append(_subs(rng, tx[a:a + 400], 0.01).tobytes())
+        packs.append([tx.tobytes()] + pieces)
+    assert [_group_of(p) for p in packs] == [4, 5, 6, 7]
+    counters, lines = _run(gpu_ctx, oracle, capfd, monkeypatch, packs)
+    assert {d["group"] for d in lines if d["pass"] == 0} == {4, 5, 6, 7}
+    _assert_reached(request, lines)
+
+
+# ---- class edges and the score range ----
+_PACKED_EDGES = (1024, 1025, 1536, 1537, 2048, 2049, 2560, 2561)
+_FORM_PK = {"dense": 1, "mt4": 7, "mt2": 7, "mt1": 7}
+_FORM_RING = {"mt4": 4, "mt2": 2, "mt1": 1}
+
+
+@pytest.mark.parametrize("mode", ["dense", "mt4", "mt2", "mt1"])
+def test_class_edges_in_every_form(gpu_ctx, oracle, capfd, monkeypatch, request, mode):
+    """The longest read at each packed class's maximum and one more (1024/1025 ... 2560/2561: the last thread's last column, qcap
+    rounding, the class boundary), and the highest score a packed cell holds: identical reads at 2560 nt (H = 12 800 in the 14-bit record),
+    with mismatches at the end so that the best cell is not the last column and rows tie."""
+    packs = [_edge_pack(L) for L in _PACKED_EDGES] + _score_packs(2560)
+    counters, lines = _run(gpu_ctx, oracle, capfd, monkeypatch, packs, {"RATTLE_POA_MODE": mode})
+    assert {d["group"] for d in lines} == {0, 1, 2, 3, 8}
+    for d in lines:
+        if d["group"] < 4:
+            assert d["pk"] == _FORM_PK[mode] and d["cpl"] == (4, 6, 8, 10)[d["group"]], d
+            if mode in _FORM_RING:
+                assert d["ring"] == _FORM_RING[mode], d
+    _assert_reached(request, lines)
+
+
+def test_wide_and_segmented_class_edges(gpu_ctx, oracle, capfd, monkeypatch, request):
+    """4096/4097, 6144/6145, 8192/8193 and 16384/16385 (the segment edge of the int32 rows), shallow and cheap; and the score range of
+    the 32-bit and 16-bit unsigned records: identical reads at 6144, 8192 (H = 40 960 > 32 767) and 8193 nt, with and without mismatches
+    at the end."""
+    packs = [_edge_pack(L, 2) for L in (4096, 4097, 6144, 6145, 8192, 8193, 16384, 16385)]
+    for L in (6144, 8192, 8193):
+        packs += _score_packs(L)
+    counters, lines = _run(gpu_ctx, oracle, capfd, monkeypatch, packs)
+    assert {d["group"] for d in lines} == {8, 9, 10, 11}
+    _assert_reached(request, lines)
+
+
+# ---- the arena budget ----
+def test_clamped_arena_that_still_fits(gpu_ctx, oracle, capfd, monkeypatch):
+    """RATTLE_POA_BUDGET_MB below one slot's first-pass record but above what the graph needs: cell_cap is cut to the budget (the record
+    almost fills its slot) and the pack still gives the oracle's rows; nothing is skipped."""
+    pack = _edge_pack(2000, 3, seed=1)
+    _, free_lines = _run(gpu_ctx, oracle, capfd, monkeypatch, [pack])
+    per = free_lines[0]["mb"] * 1e6
+    # the graph needs ~2040 rows x 2000 columns x 2 bytes (8 MB) beside ~1.3 MB of node tables and the 1 MB margin; the first pass sizes the
+    # record for 6000 rows (24 MB)
+    budget_mb = int(per * 0.55) >> 20
+    assert budget_mb >= 11
+    counters, lines = _run(gpu_ctx, oracle, capfd, monkeypatch, [pack], {"RATTLE_POA_BUDGET_MB": str(budget_mb)})
+    assert len(lines) == 1 and lines[0]["pass"] == 0 and lines[0]["mb"] * 1e6 <= budget_mb << 20 < per, (lines, per)
+
+
+def test_clamped_band_then_full_rows(gpu_ctx, oracle, capfd, monkeypatch):
+    """RATTLE_POA_BAND=1 and a budget that clamps the band slot, with a pack whose certificate fails (a 300-nt deletion): the pack goes back
+    to the full rows, whose first-pass slot is larger than the budget too.  The full rows are clamped afresh and hold the graph (the clamp
+    of the band's slot says nothing about theirs; it used to end the pack with "exceed the device arena")."""
+    pack = _band_failure_packs()["long_deletion"]
+    env = {"RATTLE_POA_BAND": "1"}
+    _, free_lines = _run(gpu_ctx, oracle, capfd, monkeypatch, [pack], env)
+    band_per = [d for d in free_lines if d["pk"] == 8][0]["mb"] * 1e6
+    full_per = [d for d in free_lines if d["pk"] != 8][0]["mb"] * 1e6
+    # the full rows need ~1200 rows x 1200 columns x 2 bytes (2.9 MB) beside ~1.2 MB of node tables and the 1 MB margin
+    budget_mb = (int(band_per) >> 20) - 1
+    assert budget_mb >= 6 and (budget_mb << 20) < band_per and (budget_mb << 20) < full_per
+    env["RATTLE_POA_BUDGET_MB"] = str(budget_mb)
+    counters, lines = _run(gpu_ctx, oracle, capfd, monkeypatch, [pack], env)
+    band = [d for d in lines if d["pk"] == 8]
+    full = [d for d in lines if d["pk"] != 8]
+    assert band and band[0]["mb"] * 1e6 <= budget_mb << 20, lines          # the band's slot was clamped ...
+    assert full and all(d["mb"] * 1e6 <= budget_mb << 20 for d in full), lines      # ... and so were the full rows'
