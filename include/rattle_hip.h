@@ -324,6 +324,41 @@ int rattle_hip_lpt_assign(const uint64_t *cost, uint32_t n, int nranks, uint32_t
  * of explicit exceptions the table carries. */
 int rattle_hip_debug_phred_symbol(double p, int *table_value, int *libm_value);
 
+/* Test hook: ONE evaluation of the greedy clustering (cluster_together over a list of rectangles, as a greedy step hands them to
+ * the device: kernel A's survivor list, the count pass for |common|, the exact rejection on it, the full pass and the verdicts)
+ * on the loaded reads, with what it computed on the way.  Rectangle r: seeds x candidates, or, triangular, the seeds against
+ * each other (pairs s < c); thr is its bit-vector threshold.  count_pass: 0 = as the driver picks it, 1 = seed-major,
+ * 2 = per-pair search.  Only t_s, t_v, use_hc and is_rna of params are read. */
+typedef struct {
+    const uint32_t *seed_ids;
+    uint32_t n_seeds;
+    const uint32_t *cand_ids;   /* ignored when triangular */
+    uint32_t n_cands;
+    int triangular;
+    double thr;
+} rattle_debug_rect;
+
+typedef struct {
+    uint32_t n;
+    uint32_t *rect, *seed, *cand;   /* rectangle; seed and candidate index within it */
+    uint8_t *strand;
+    int32_t *count;                 /* survivors: the count pass's result (|common| or its upper bound); else 0 */
+} rattle_debug_pairs;
+
+typedef struct {
+    rattle_debug_pairs survivors;   /* kernel A's survivors */
+    rattle_debug_pairs kept;        /* the survivors past the exact rejection double(k * count) / min_len >= t_s */
+    rattle_debug_pairs hits;        /* accepted pairs */
+    uint64_t *counters;             /* [n_rects * 8]: the rectangle's work counters as in rattle_cluster_set */
+    int count_pass;                 /* bit 0: the seed-major count pass ran, bit 1: the per-pair search ran */
+    uint64_t filter_launches;       /* kernel A launches (one more per survivor-capacity retry) */
+    uint64_t oversize_pairs;        /* pairs that went through the oversize full pass */
+} rattle_debug_eval;
+
+int rattle_hip_debug_evaluate(rattle_ctx *ctx, const rattle_cluster_params *params, int count_pass, const rattle_debug_rect *rects,
+                              uint32_t n_rects, rattle_debug_eval **out);
+void rattle_hip_debug_evaluate_free(rattle_debug_eval *e);
+
 /* ------------------------------------------------------------------------------------
  * Per-kernel timing measured with HIP events on the stream the kernels run on.
  * kernel: 0 kmer_extract, 1 bv_filter, 2 pair_score, 3 poa_align, 4 post_msa.  Accumulated since

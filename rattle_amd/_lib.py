@@ -59,6 +59,21 @@ class PackPlan(C.Structure):
                 ("unqueued_cluster", C.POINTER(C.c_int32))]
 
 
+class DebugRect(C.Structure):
+    _fields_ = [("seed_ids", C.POINTER(C.c_uint32)), ("n_seeds", C.c_uint32), ("cand_ids", C.POINTER(C.c_uint32)),
+                ("n_cands", C.c_uint32), ("triangular", C.c_int), ("thr", C.c_double)]
+
+
+class DebugPairs(C.Structure):
+    _fields_ = [("n", C.c_uint32), ("rect", C.POINTER(C.c_uint32)), ("seed", C.POINTER(C.c_uint32)),
+                ("cand", C.POINTER(C.c_uint32)), ("strand", C.POINTER(C.c_uint8)), ("count", C.POINTER(C.c_int32))]
+
+
+class DebugEval(C.Structure):
+    _fields_ = [("survivors", DebugPairs), ("kept", DebugPairs), ("hits", DebugPairs), ("counters", C.POINTER(C.c_uint64)),
+                ("count_pass", C.c_int), ("filter_launches", C.c_uint64), ("oversize_pairs", C.c_uint64)]
+
+
 # int fn(void *user, const void *send, uint64 send_bytes, void *recv, const uint64 *recv_bytes)
 ALLGATHERV_FN = C.CFUNCTYPE(C.c_int, C.c_void_p, C.c_void_p, C.c_uint64, C.c_void_p, C.POINTER(C.c_uint64))
 
@@ -87,6 +102,8 @@ SIGNATURES = {
     "rattle_hip_cluster_subset": (C.c_int, [C.c_void_p, _P(ClusterParams), _u32p, C.c_uint32, _P(_P(ClusterSet))]),
     "rattle_hip_cluster_subsets": (C.c_int, [C.c_void_p, _P(ClusterParams), _u32p, _u64p, C.c_uint32, _P(_P(ClusterSet)), C.c_int]),
     "rattle_hip_debug_phred_symbol": (C.c_int, [C.c_double, _P(C.c_int), _P(C.c_int)]),
+    "rattle_hip_debug_evaluate": (C.c_int, [C.c_void_p, _P(ClusterParams), C.c_int, _P(DebugRect), C.c_uint32, _P(_P(DebugEval))]),
+    "rattle_hip_debug_evaluate_free": (None, [_P(DebugEval)]),
     "rattle_hip_stage_reads": (C.c_int, [C.c_void_p, _u8p, _u8p, _u64p, C.c_uint32]),
     "rattle_hip_unstage_reads": (C.c_int, [C.c_void_p]),
     "rattle_hip_cluster_unsorted": (C.c_int, [C.c_void_p, _u8p, _u64p, C.c_uint32, C.c_int, _P(ClusterParams),

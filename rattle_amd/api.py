@@ -445,6 +445,44 @@ class Context:
         check(self.lib.rattle_hip_comm_stats(self.h, C.byref(a), C.byref(b)))
         return a.value, b.value
 
+    def debug_evaluate(self, rects, t_s=0.2, t_v=1000000.0, use_hc=False, is_rna=False, count_pass="auto"):
+        """One evaluation of the greedy clustering on the loaded reads (rattle_hip_debug_evaluate, a test hook).
+        rects: list of (seed_ids, cand_ids, thr); cand_ids None = triangular (the seeds against each other, pairs s < c).
+        count_pass: "auto" (the driver's rule), "seed" or "search".  Returns a dict: "survivors" (with "count"), "kept" and
+        "hits", each a dict of arrays rect / seed / cand / strand (indices within the rectangle); "counters" [n_rects, 8];
+        "count_pass" (the set of passes that ran); "filter_launches"; "oversize_pairs"."""
+        mode = {"auto": 0, "seed": 1, "search": 2}[count_pass]
+        P = ClusterParams(t_s, t_v, 0.0, 0.0, 0.0, 0, int(use_hc), 0.0, int(is_rna))
+        keep = []
+        R = (_lib.DebugRect * max(len(rects), 1))()
+        for r, (seeds, cands, thr) in enumerate(rects):
+            s = np.ascontiguousarray(seeds if len(seeds) else [0], np.uint32)
+            keep.append(s)
+            R[r].seed_ids = _ptr(s, C.c_uint32); R[r].n_seeds = len(seeds); R[r].thr = float(thr)
+            if cands is None:
+                R[r].triangular = 1
+            else:
+                c = np.ascontiguousarray(cands if len(cands) else [0], np.uint32)
+                keep.append(c)
+                R[r].cand_ids = _ptr(c, C.c_uint32); R[r].n_cands = len(cands)
+        out = C.POINTER(_lib.DebugEval)()
+        check(self.lib.rattle_hip_debug_evaluate(self.h, C.byref(P), mode, R, len(rects), C.byref(out)))
+        D = out.contents
+
+        def pairs(Q, with_count):
+            n = Q.n
+            d = {f: np.ctypeslib.as_array(getattr(Q, f), (max(n, 1),))[:n].copy() for f in ("rect", "seed", "cand", "strand")}
+            if with_count:
+                d["count"] = np.ctypeslib.as_array(Q.count, (max(n, 1),))[:n].copy()
+            return d
+
+        res = {"survivors": pairs(D.survivors, True), "kept": pairs(D.kept, False), "hits": pairs(D.hits, False),
+               "counters": np.ctypeslib.as_array(D.counters, (len(rects) * 8 + 1,))[:len(rects) * 8].reshape(len(rects), 8).copy(),
+               "count_pass": {p for b, p in ((1, "seed"), (2, "search")) if D.count_pass & b},
+               "filter_launches": int(D.filter_launches), "oversize_pairs": int(D.oversize_pairs)}
+        self.lib.rattle_hip_debug_evaluate_free(out)
+        return res
+
     def kernel_stats(self, kernel: int):
         ms = C.c_double(); n = C.c_uint64(); b = C.c_uint64()
         check(self.lib.rattle_hip_kernel_stats(self.h, kernel, C.byref(ms), C.byref(n), C.byref(b)))

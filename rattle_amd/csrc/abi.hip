@@ -539,6 +539,33 @@ int rattle_hip_debug_phred_symbol(double p, int *table_value, int *libm_value) {
     return (int)T.exc_bits.size();
 }
 
+int rattle_hip_debug_evaluate(rattle_ctx *c, const rattle_cluster_params *P, int count_pass, const rattle_debug_rect *R,
+                              uint32_t n_rects, rattle_debug_eval **out) {
+    if (!c || !P || !out || (n_rects && !R)) { set_error("null argument"); return RATTLE_ERR_ARG; }
+    *out = nullptr;
+    if (count_pass < 0 || count_pass > 2) { set_error("count_pass must be 0 (auto), 1 (seed-major) or 2 (search)"); return RATTLE_ERR_ARG; }
+    RT_TRY(use_device(c));
+    if (c->idx.k == 0) { set_error("no reads loaded"); return RATTLE_ERR_STATE; }
+    if (!P->is_rna && !c->idx.both) { set_error("cDNA mode needs the reads loaded with both_strands=1"); return RATTLE_ERR_STATE; }
+    if (P->is_rna && c->idx.both) { set_error("--rna mode needs the reads loaded with both_strands=0"); return RATTLE_ERR_STATE; }
+    for (uint32_t r = 0; r < n_rects; ++r) {
+        if ((R[r].n_seeds && !R[r].seed_ids) || (!R[r].triangular && R[r].n_cands && !R[r].cand_ids)) { set_error("null argument"); return RATTLE_ERR_ARG; }
+        for (uint32_t i = 0; i < R[r].n_seeds; ++i) if (R[r].seed_ids[i] >= c->idx.n) { set_error("seed id out of range"); return RATTLE_ERR_ARG; }
+        if (!R[r].triangular)
+            for (uint32_t i = 0; i < R[r].n_cands; ++i) if (R[r].cand_ids[i] >= c->idx.n) { set_error("cand id out of range"); return RATTLE_ERR_ARG; }
+    }
+    return debug_evaluate(c, P, count_pass, R, n_rects, out);
+}
+
+static void free_pairs(rattle_debug_pairs &d) { free(d.rect); free(d.seed); free(d.cand); free(d.strand); free(d.count); }
+
+void rattle_hip_debug_evaluate_free(rattle_debug_eval *e) {
+    if (!e) return;
+    free_pairs(e->survivors); free_pairs(e->kept); free_pairs(e->hits);
+    free(e->counters);
+    free(e);
+}
+
 int rattle_hip_kernel_stats(rattle_ctx *c, int kernel, double *ms, uint64_t *launches, uint64_t *bytes) {
     if (!c || kernel < 0 || kernel >= K_COUNT) { set_error("bad kernel id"); return RATTLE_ERR_ARG; }
     if (ms) *ms = c->stats[kernel].ms;

@@ -152,6 +152,7 @@ struct request {
     bool triangular = false;
     double thr = 0.0;                         // bit-vector threshold of the pass (cluster.cpp:19,43)
     uint64_t *counters = nullptr;             // the job's work counters
+    uint32_t tag = 0;                         // the test hook's rectangle number (eval_sink)
     std::vector<hit_t> hits;                  // out: accepted (seed index, candidate index, strand); sorted if triangular
     uint32_t n_cands() const { return (uint32_t)(triangular ? seeds.size() : cands.size()); }
     uint64_t n_pairs() const {
@@ -160,11 +161,22 @@ struct request {
     }
 };
 
+// What one evaluation computed on its way, for the test hook (rattle_hip_debug_evaluate): pairs as (request tag, seed index,
+// candidate index, strand), the count pass's result of every survivor.  The greedy driver runs without one.
+struct eval_sink {
+    struct pair { uint32_t rect, seed, cand; uint8_t strand; int32_t count; };
+    std::vector<pair> surv, kept;
+    int count_pass = 0;                       // bit 0: the seed-major pass ran, bit 1: the per-pair search
+    uint64_t filter_launches = 0, oversize = 0;
+};
+
 // ---- device evaluation of a set of rectangles -------------------------------------------------------------
 struct evaluator {
     rattle_ctx *ctx;
     const rattle_cluster_params *P;
     uint64_t launches = 0;
+    int count_mode = 0;                       // 0: RATTLE_PAIR_COUNT, else the nsurv >= 64 ns rule; 1: seed-major; 2: search
+    eval_sink *sink = nullptr;                // test hook only
     // RATTLE_TIMING: where the host's wall time of a clustering goes
     double t_split[6] = {0, 0, 0, 0, 0, 0};
     std::chrono::steady_clock::time_point t_mark;
@@ -340,6 +352,7 @@ struct evaluator {
             RT_HIP(hipMemsetAsync(ctx->d_counter.p, 0, 16, st));
             RT_TRY(launch_bv_filter_rects(ctx, nrect, tiles, npairs, false, true, (uint32_t)std::min<size_t>(cap, 0xFFFFFFF0u)));
             ++launches;
+            if (sink) ++sink->filter_launches;
             RT_HIP(hipMemcpyAsync(ctx->h_counter.p, ctx->d_counter.p, 4, hipMemcpyDeviceToHost, st));
             RT_HIP(hipStreamSynchronize(st));
             nsurv = ctx->h_counter.p[0];
@@ -366,7 +379,8 @@ struct evaluator {
         // "search": one wavefront per pair, binary searches in the candidate's list (pair_score.hip) -- better for the short
         // runs of the --iso level.  RATTLE_PAIR_COUNT=seed|search forces one of them.
         static const char *force = getenv("RATTLE_PAIR_COUNT");
-        const bool seed_major = force ? !strcmp(force, "seed") : (uint64_t)nsurv >= 64ull * ns;
+        const bool seed_major = count_mode ? count_mode == 1 : force ? !strcmp(force, "seed") : (uint64_t)nsurv >= 64ull * ns;
+        if (sink) sink->count_pass |= seed_major ? 1 : 2;
         if (seed_major) RT_TRY(sort_survivors_by_seed(ctx, nsurv, ns));
         hipLaunchKernelGGL(expand_pairs_kernel, dim3((nsurv + 255) / 256), dim3(256), 0, st, ctx->d_surv.p, nsurv,
                            ctx->d_seed.p, ctx->d_cand.p, ctx->d_pi.p, ctx->d_pj.p, ctx->d_ps.p);
@@ -385,6 +399,7 @@ struct evaluator {
         RT_HIP(hipStreamSynchronize(st));
         lap(2);
         const uint32_t n2 = (uint32_t)ctx->h_bound_stats.p[0];
+        if (sink) RT_TRY(take_pairs(reqs, rect_req, nsurv, n2));      // before pass 2 overwrites d_res
         ctx->stats[K_SCORE].bytes += ctx->h_bound_stats.p[1];
         for (uint32_t j = 0; j < nrect; ++j) {
             uint64_t *cn = reqs[rect_req[j]]->counters;
@@ -425,6 +440,7 @@ struct evaluator {
             RT_HIP(hipStreamSynchronize(st));
             RT_TRY(launch_pair_score_oversize(ctx, big, big_m));
             ++launches;
+            if (sink) sink->oversize += nbig;
             RT_HIP(hipMemsetAsync(vout + 1, 0, 16, st));
             hipLaunchKernelGGL(verdict_kernel, dim3((nbig + 255) / 256), dim3(256), 0, st, ctx->d_res.p, ctx->d_var.p, nbig, (const uint32_t *)d_big,
                                ctx->d_pi.p, ctx->d_pj.p, ctx->d_slot2.p, X.len.p, use_hc, t_s, t_v, vout, d_hits, d_big);
@@ -448,6 +464,25 @@ struct evaluator {
         }
         for (uint32_t j = 0; j < nrect; ++j) if (reqs[rect_req[j]]->triangular) sort_hits(reqs[rect_req[j]]->hits);      // level 2 takes them in any order
         lap(4);
+        return 0;
+    }
+
+    // test hook: the survivors with their counts (d_surv / d_res after count_bound_kernel) and the kept pairs (d_slot2)
+    int take_pairs(request **reqs, const std::vector<uint32_t> &rect_req, uint32_t nsurv, uint32_t n2) {
+        std::vector<uint32_t> surv((size_t)nsurv * 2), slot2((size_t)n2 * 2);
+        std::vector<int32_t> cnt(nsurv);
+        RT_HIP(hipMemcpyAsync(surv.data(), ctx->d_surv.p, surv.size() * 4, hipMemcpyDeviceToHost, ctx->stream));
+        RT_HIP(hipMemcpyAsync(cnt.data(), ctx->d_res.p, cnt.size() * 4, hipMemcpyDeviceToHost, ctx->stream));
+        if (n2) RT_HIP(hipMemcpyAsync(slot2.data(), ctx->d_slot2.p, slot2.size() * 4, hipMemcpyDeviceToHost, ctx->stream));
+        RT_HIP(hipStreamSynchronize(ctx->stream));
+        const bool many = rects.size() > 1;
+        auto pair_of = [&](uint32_t a, uint32_t c, int32_t count) {
+            const uint32_t rj = many ? seed_req[a >> 1] : 0;
+            const bvf_rect &J = rects[rj];
+            return eval_sink::pair{reqs[rect_req[rj]]->tag, (a >> 1) - J.s_base, c - J.c_base, (uint8_t)(a & 1u), count};
+        };
+        for (uint32_t p = 0; p < nsurv; ++p) sink->surv.push_back(pair_of(surv[2 * (size_t)p], surv[2 * (size_t)p + 1], cnt[p]));
+        for (uint32_t p = 0; p < n2; ++p) sink->kept.push_back(pair_of(slot2[2 * (size_t)p], slot2[2 * (size_t)p + 1], 0));
         return 0;
     }
 };
@@ -775,6 +810,54 @@ int cluster_driver_many(rattle_ctx *ctx, const rattle_cluster_params *P, const u
     }
     RT_TRY(run_jobs(ctx, P, jobs, false));
     for (uint32_t i = 0; i < n_which; ++i) outs[which[i]] = jobs[i].flatten();
+    return 0;
+}
+
+// Test hook: ONE evaluation of the given rectangles as a greedy step makes it (evaluator::run, unsharded), with the count pass
+// chosen by the caller, and what it computed on the way.
+int debug_evaluate(rattle_ctx *ctx, const rattle_cluster_params *P, int count_mode, const rattle_debug_rect *R, uint32_t n_rects,
+                   rattle_debug_eval **out) {
+    std::vector<request> q(n_rects);
+    std::vector<uint64_t> counters((size_t)n_rects * 8 + 1, 0);
+    std::vector<request *> reqs(n_rects);
+    for (uint32_t r = 0; r < n_rects; ++r) {
+        q[r].seeds.assign(R[r].seed_ids, R[r].seed_ids + R[r].n_seeds);
+        if (!R[r].triangular) q[r].cands.assign(R[r].cand_ids, R[r].cand_ids + R[r].n_cands);
+        q[r].triangular = R[r].triangular != 0;
+        q[r].thr = R[r].thr;
+        q[r].counters = counters.data() + 8 * (size_t)r;
+        q[r].tag = r;
+        reqs[r] = &q[r];
+    }
+    evaluator E{ctx, P};
+    eval_sink sink;
+    E.count_mode = count_mode;
+    E.sink = &sink;
+    RT_TRY(E.run(reqs, false));
+    size_t nh = 0;
+    for (auto &x : q) nh += x.hits.size();
+    rattle_debug_eval *D = (rattle_debug_eval *)calloc(1, sizeof(rattle_debug_eval));
+    auto fill = [](rattle_debug_pairs &d, size_t n) {
+        d.n = (uint32_t)n;
+        d.rect = (uint32_t *)malloc(4 * std::max<size_t>(n, 1)); d.seed = (uint32_t *)malloc(4 * std::max<size_t>(n, 1));
+        d.cand = (uint32_t *)malloc(4 * std::max<size_t>(n, 1)); d.strand = (uint8_t *)malloc(std::max<size_t>(n, 1));
+        d.count = (int32_t *)malloc(4 * std::max<size_t>(n, 1));
+    };
+    fill(D->survivors, sink.surv.size()); fill(D->kept, sink.kept.size()); fill(D->hits, nh);
+    auto put = [](rattle_debug_pairs &d, size_t i, const eval_sink::pair &p) {
+        d.rect[i] = p.rect; d.seed[i] = p.seed; d.cand[i] = p.cand; d.strand[i] = p.strand; d.count[i] = p.count;
+    };
+    for (size_t i = 0; i < sink.surv.size(); ++i) put(D->survivors, i, sink.surv[i]);
+    for (size_t i = 0; i < sink.kept.size(); ++i) put(D->kept, i, sink.kept[i]);
+    size_t h = 0;
+    for (uint32_t r = 0; r < n_rects; ++r)
+        for (const hit_t &x : q[r].hits) put(D->hits, h++, eval_sink::pair{r, x.seed, x.cand, x.rev, 0});
+    D->counters = (uint64_t *)malloc(counters.size() * 8);
+    memcpy(D->counters, counters.data(), counters.size() * 8);
+    D->count_pass = sink.count_pass;
+    D->filter_launches = sink.filter_launches;
+    D->oversize_pairs = sink.oversize;
+    *out = D;
     return 0;
 }
 

@@ -384,5 +384,7 @@ int cluster_driver_many(rattle_ctx *ctx, const rattle_cluster_params *P, const u
                         const uint32_t *which, uint32_t n_which, rattle_cluster_set **outs);
 int cluster_driver(rattle_ctx *ctx, const rattle_cluster_params *P, const uint32_t *subset, uint32_t n_subset,
                    rattle_cluster_set **out);
+int debug_evaluate(rattle_ctx *ctx, const rattle_cluster_params *P, int count_mode, const rattle_debug_rect *R, uint32_t n_rects,
+                   rattle_debug_eval **out);
 
 }  // namespace rattle
