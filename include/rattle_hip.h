@@ -108,7 +108,10 @@ typedef struct {
     /* work counters.  Exact and identical on every rank of a sharded job: [0] bit-vector pair tests, [1] full
        comparisons (pairs past the filter: their common k-mers are counted).  [2] k-mer matches summed over the count pass:
        exact when the pass counts per pair, an UPPER BOUND when the seed-major count kernel folds the hash (k > 10) or a
-       seed's repeat list overflows -- it depends on which form the driver picked and is for reporting only.  Local to the
+       seed's repeat list overflows -- it depends on which form the driver picked and is for reporting only.  The "index"
+       form (RATTLE_PAIR_COUNT=index): k <= 10: exactly |common|; k > 10: the sum over the candidate's k-mers b of the
+       multiplicity of fold(hash(b)), fold(h) = (h ^ h >> 20) & 0xFFFFF, among the seed's folded hashes -- an upper bound
+       of |common| with no overflow rule (it keeps no repeat list).  Local to the
        calling rank: [3] seed rounds, [4] kernel launches, [5] pairs whose match count could still reach t_s and went
        through the patience search (the others are rejected exactly on the count). */
     uint64_t counters[8];
@@ -328,7 +331,7 @@ int rattle_hip_debug_phred_symbol(double p, int *table_value, int *libm_value);
  * the device: kernel A's survivor list, the count pass for |common|, the exact rejection on it, the full pass and the verdicts)
  * on the loaded reads, with what it computed on the way.  Rectangle r: seeds x candidates, or, triangular, the seeds against
  * each other (pairs s < c); thr is its bit-vector threshold.  count_pass: 0 = as the driver picks it, 1 = seed-major,
- * 2 = per-pair search.  Only t_s, t_v, use_hc and is_rna of params are read. */
+ * 2 = per-pair search, 3 = seed-batch k-mer index.  Only t_s, t_v, use_hc and is_rna of params are read. */
 typedef struct {
     const uint32_t *seed_ids;
     uint32_t n_seeds;
@@ -350,7 +353,7 @@ typedef struct {
     rattle_debug_pairs kept;        /* the survivors past the exact rejection double(k * count) / min_len >= t_s */
     rattle_debug_pairs hits;        /* accepted pairs */
     uint64_t *counters;             /* [n_rects * 8]: the rectangle's work counters as in rattle_cluster_set */
-    int count_pass;                 /* bit 0: the seed-major count pass ran, bit 1: the per-pair search ran */
+    int count_pass;                 /* bit 0: the seed-major count pass ran, bit 1: the per-pair search ran, bit 2: the index pass ran */
     uint64_t filter_launches;       /* kernel A launches (one more per survivor-capacity retry) */
     uint64_t oversize_pairs;        /* pairs that went through the oversize full pass */
 } rattle_debug_eval;

@@ -448,10 +448,10 @@ class Context:
     def debug_evaluate(self, rects, t_s=0.2, t_v=1000000.0, use_hc=False, is_rna=False, count_pass="auto"):
         """One evaluation of the greedy clustering on the loaded reads (rattle_hip_debug_evaluate, a test hook).
         rects: list of (seed_ids, cand_ids, thr); cand_ids None = triangular (the seeds against each other, pairs s < c).
-        count_pass: "auto" (the driver's rule), "seed" or "search".  Returns a dict: "survivors" (with "count"), "kept" and
+        count_pass: "auto" (the driver's rule), "seed", "search" or "index".  Returns a dict: "survivors" (with "count"), "kept" and
         "hits", each a dict of arrays rect / seed / cand / strand (indices within the rectangle); "counters" [n_rects, 8];
         "count_pass" (the set of passes that ran); "filter_launches"; "oversize_pairs"."""
-        mode = {"auto": 0, "seed": 1, "search": 2}[count_pass]
+        mode = {"auto": 0, "seed": 1, "search": 2, "index": 3}[count_pass]
         P = ClusterParams(t_s, t_v, 0.0, 0.0, 0.0, 0, int(use_hc), 0.0, int(is_rna))
         keep = []
         R = (_lib.DebugRect * max(len(rects), 1))()
@@ -478,7 +478,7 @@ class Context:
 
         res = {"survivors": pairs(D.survivors, True), "kept": pairs(D.kept, False), "hits": pairs(D.hits, False),
                "counters": np.ctypeslib.as_array(D.counters, (len(rects) * 8 + 1,))[:len(rects) * 8].reshape(len(rects), 8).copy(),
-               "count_pass": {p for b, p in ((1, "seed"), (2, "search")) if D.count_pass & b},
+               "count_pass": {p for b, p in ((1, "seed"), (2, "search"), (4, "index")) if D.count_pass & b},
                "filter_launches": int(D.filter_launches), "oversize_pairs": int(D.oversize_pairs)}
         self.lib.rattle_hip_debug_evaluate_free(out)
         return res

@@ -543,7 +543,7 @@ int rattle_hip_debug_evaluate(rattle_ctx *c, const rattle_cluster_params *P, int
                               uint32_t n_rects, rattle_debug_eval **out) {
     if (!c || !P || !out || (n_rects && !R)) { set_error("null argument"); return RATTLE_ERR_ARG; }
     *out = nullptr;
-    if (count_pass < 0 || count_pass > 2) { set_error("count_pass must be 0 (auto), 1 (seed-major) or 2 (search)"); return RATTLE_ERR_ARG; }
+    if (count_pass < 0 || count_pass > 3) { set_error("count_pass must be 0 (auto), 1 (seed-major), 2 (search) or 3 (index)"); return RATTLE_ERR_ARG; }
     RT_TRY(use_device(c));
     if (c->idx.k == 0) { set_error("no reads loaded"); return RATTLE_ERR_STATE; }
     if (!P->is_rna && !c->idx.both) { set_error("cDNA mode needs the reads loaded with both_strands=1"); return RATTLE_ERR_STATE; }

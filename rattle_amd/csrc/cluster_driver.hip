@@ -166,7 +166,7 @@ struct request {
 struct eval_sink {
     struct pair { uint32_t rect, seed, cand; uint8_t strand; int32_t count; };
     std::vector<pair> surv, kept;
-    int count_pass = 0;                       // bit 0: the seed-major pass ran, bit 1: the per-pair search
+    int count_pass = 0;                       // bit 0: the seed-major pass ran, bit 1: the per-pair search, bit 2: the seed-batch index
     uint64_t filter_launches = 0, oversize = 0;
 };
 
@@ -175,7 +175,8 @@ struct evaluator {
     rattle_ctx *ctx;
     const rattle_cluster_params *P;
     uint64_t launches = 0;
-    int count_mode = 0;                       // 0: RATTLE_PAIR_COUNT, else the nsurv >= 64 ns rule; 1: seed-major; 2: search
+    int count_mode = 0;                       // 0: RATTLE_PAIR_COUNT, else the nsurv >= 64 ns rule; 1: seed-major; 2: search; 3: index
+    uint64_t n_form[3] = {0, 0, 0};           // evaluations whose count pass was seed-major / search / index (RATTLE_TIMING)
     eval_sink *sink = nullptr;                // test hook only
     // RATTLE_TIMING: where the host's wall time of a clustering goes
     double t_split[6] = {0, 0, 0, 0, 0, 0};
@@ -374,21 +375,30 @@ struct evaluator {
             RT_HIP(hipMemcpyAsync(ctx->d_seed_rect.p, seed_req.data(), ns * 4, hipMemcpyHostToDevice, st));
         }
         RT_HIP(hipMemsetAsync(ctx->d_bound_stats.p, 0, (2 + 3 * (size_t)nrect + 4) * 8, st));
-        // Two count passes.  "seed": survivors sorted by seed, the seed's k-mer set as a bit set in LDS, its candidates' lists
+        // Three count passes.  "seed": survivors sorted by seed, the seed's k-mer set as a bit set in LDS, its candidates' lists
         // streamed past it (pair_count.hip) -- pays where a seed has many surviving candidates (gene level: hundreds).
         // "search": one wavefront per pair, binary searches in the candidate's list (pair_score.hip) -- better for the short
-        // runs of the --iso level.  RATTLE_PAIR_COUNT=seed|search forces one of them.
+        // runs of the --iso level.  "index": an inverted k-mer index over the seeds, every candidate's list streamed once
+        // (pair_index.hip) -- for long reads, where the bit-vector filter lets every pair through.  RATTLE_PAIR_COUNT=
+        // seed|search|index forces one of them (any other value: search); the automatic rule picks between the first two.
         static const char *force = getenv("RATTLE_PAIR_COUNT");
-        const bool seed_major = count_mode ? count_mode == 1 : force ? !strcmp(force, "seed") : (uint64_t)nsurv >= 64ull * ns;
-        if (sink) sink->count_pass |= seed_major ? 1 : 2;
+        const int form = count_mode ? count_mode
+                         : force ? (!strcmp(force, "seed") ? 1 : !strcmp(force, "index") ? 3 : 2)
+                                 : (uint64_t)nsurv >= 64ull * ns ? 1 : 2;
+        const bool seed_major = form == 1, indexed = form == 3;
+        if (sink) sink->count_pass |= 1 << (form - 1);
+        ++n_form[form - 1];
         if (seed_major) RT_TRY(sort_survivors_by_seed(ctx, nsurv, ns));
+        if (indexed) RT_TRY(group_survivors_by_cand(ctx, nsurv, nc));
         hipLaunchKernelGGL(expand_pairs_kernel, dim3((nsurv + 255) / 256), dim3(256), 0, st, ctx->d_surv.p, nsurv,
                            ctx->d_seed.p, ctx->d_cand.p, ctx->d_pi.p, ctx->d_pj.p, ctx->d_ps.p);
         // ---- pass 1: |common| of every surviving pair.  bases <= k * |LIS| <= k * |common| (similarity.cpp:52-85), so a pair
         // with double(k * |common|) / min_len < t_s cannot pass cluster.cpp:23-27 whatever its chain looks like: exact
         // rejection without the patience search.  In the low-threshold merge passes that is nearly every pair.  The test
         // (same double expression) and the compaction of the pairs that pass run on the device.
-        if (seed_major) RT_TRY(launch_pair_count_seed(ctx, nsurv)); else RT_TRY(launch_pair_count(ctx, nsurv));
+        if (seed_major) RT_TRY(launch_pair_count_seed(ctx, nsurv));
+        else if (indexed) RT_TRY(launch_pair_count_index(ctx, nsurv, h_seed.data(), (uint32_t)ns, (uint32_t)nc, many));
+        else RT_TRY(launch_pair_count(ctx, nsurv));
         const double t_s = P->t_s, t_v = P->t_v;
         const uint32_t kk = (uint32_t)X.k;
         hipLaunchKernelGGL(count_bound_kernel, dim3((nsurv + 255) / 256), dim3(256), 0, st, ctx->d_surv.p, ctx->d_res.p, nsurv,
@@ -782,6 +792,9 @@ int run_jobs(rattle_ctx *ctx, const rattle_cluster_params *P, std::vector<job> &
     if (timing)
         fprintf(stderr, "[rattle]   %zu job(s): host steps %.1f ms | build+upload %.1f, filter %.1f, count pass %.1f, host bound test %.1f, full pass + verdicts %.1f ms\n",
                 jobs.size(), t_steps, E.t_split[0], E.t_split[1], E.t_split[2], E.t_split[3], E.t_split[4]);
+    if (timing)
+        fprintf(stderr, "[rattle]   count pass of the evaluations with survivors: seed %llu, search %llu, index %llu\n",
+                (unsigned long long)E.n_form[0], (unsigned long long)E.n_form[1], (unsigned long long)E.n_form[2]);
     return 0;
 }
 

@@ -285,6 +285,8 @@ struct rattle_ctx {
     rattle::dbuf<uint32_t> d_surv;          // survivor list (2 words per entry)
     rattle::dbuf<uint32_t> d_surv2;         // ... sorted by seed (double buffer of the device sort)
     rattle::dbuf<uint8_t> d_sort_tmp;
+    // the "index" count pass (pair_index.hip): survivor range per candidate slot, bucket offsets, bucket entries, scan totals
+    rattle::dbuf<uint32_t> d_ix_coff, d_ix_boff, d_ix_ent, d_ix_bsum;
     rattle::dbuf<uint32_t> d_counter;
     rattle::dbuf<uint32_t> d_pi, d_pj;
     rattle::dbuf<uint8_t> d_ps;
@@ -371,6 +373,9 @@ int sort_survivors_by_seed(rattle_ctx *ctx, uint32_t n, uint64_t n_seeds);
 int launch_pair_count_seed(rattle_ctx *ctx, uint32_t n_pairs);
 // the same pairs, |common| only (d_res[pair]); see pair_score.hip
 int launch_pair_count(rattle_ctx *ctx, uint32_t n_pairs);
+// pair_index.hip : the count pass over an inverted k-mer index of the evaluation's seeds (survivors grouped by candidate)
+int group_survivors_by_cand(rattle_ctx *ctx, uint32_t n, uint64_t n_cands);
+int launch_pair_count_index(rattle_ctx *ctx, uint32_t n_pairs, const uint32_t *h_seed, uint32_t ns, uint32_t nc, bool many);
 // poa.hip : device-resident POA over packs (sequences, offsets, column output in HBM)
 int poa_device_run(rattle_ctx *ctx, const uint8_t *d_seq, const uint64_t *d_off, const uint64_t *h_off, uint32_t n_seqs,
                    const uint32_t *h_pack_first, uint32_t n_packs, uint32_t *d_col, uint32_t *d_width, uint32_t *h_width,

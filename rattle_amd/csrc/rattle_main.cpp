@@ -604,11 +604,24 @@ int mode_cluster(int argc, char **argv) {
         {"min_reads_cluster", {"-r", "--min-reads-cluster"}, true}, {"repr_percentile", {"-p", "--repr-percentile"}, true},
         {"rna", {"--rna"}, false}, {"verbose", {"--verbose"}, false}, {"raw", {"--raw"}, false},
         {"lower_len", {"--lower-length"}, true}, {"upper_len", {"--upper-length"}, true}, {"device", {"--device"}, true},
-        {"devices", {"--devices"}, true}, {"host-exchange", {"--host-exchange"}, false}, {"write-unzipped", {"--write-unzipped"}, false}};
+        {"devices", {"--devices"}, true}, {"host-exchange", {"--host-exchange"}, false}, {"write-unzipped", {"--write-unzipped"}, false},
+        {"count-pass", {"--count-pass"}, true}};
     args_t a = parse(argc, argv, defs);
+    const char *usage = "rattle cluster -i reads.fq [-o dir] [--rna] [--iso] ... (flags of RATTLE's cluster mode)\n"
+                        "  --devices 0,1,..   one job over several GPUs (RCCL; --host-exchange: in-process exchange on host buffers)\n"
+                        "  --count-pass auto|seed|search|index   form of the count pass (what RATTLE_PAIR_COUNT sets; default auto)\n";
+    if (a.has("count-pass")) {
+        // the library reads the variable once, at its first evaluation: set it before any device thread starts
+        const std::string form = a.str("count-pass", "auto");
+        if (form == "auto") unsetenv("RATTLE_PAIR_COUNT");
+        else if (form == "seed" || form == "search" || form == "index") setenv("RATTLE_PAIR_COUNT", form.c_str(), 1);
+        else {
+            std::cerr << "ERROR: --count-pass takes auto, seed, search or index (got '" << form << "')\nusage: " << usage;
+            return EXIT_FAILURE;
+        }
+    }
     if (a.has("help")) {
-        std::cerr << "rattle cluster -i reads.fq [-o dir] [--rna] [--iso] ... (flags of RATTLE's cluster mode)\n"
-                     "  --devices 0,1,..   one job over several GPUs (RCCL; --host-exchange: in-process exchange on host buffers)\n"
+        std::cerr << usage <<
                      "  --write-unzipped   also write the inflated copy of a .gz input next to it, as the reference does\n";
         return EXIT_SUCCESS;
     }
