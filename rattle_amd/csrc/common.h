@@ -216,6 +216,8 @@ struct pack_plan {
 };
 int plan_packs(const uint64_t *off, uint32_t n_reads, uint32_t n_clusters, const uint32_t *coff, const int32_t *mid, const uint8_t *mrev,
                const rattle_correct_params *P, int nranks, pack_plan &out);
+// a read set of the result for n records and tot bases (NUL behind them); the arrays are never null pointers (exchange.hip)
+void alloc_read_set(rattle_read_set &S, uint32_t n, uint64_t tot);
 // longest-processing-time-first assignment of weighted items to nranks bins (ties: lower index / lower rank)
 void lpt_assign(const std::vector<uint64_t> &cost, int nranks, std::vector<uint32_t> &owner);
 // all-gather of one byte string per rank (sizes first, then the payload)
@@ -294,8 +296,6 @@ struct rattle_ctx {
     rattle::dbuf<double> d_var;
     rattle::dbuf<uint32_t> d_scratch;       // global scratch for oversize pairs
     rattle::hbuf<uint32_t> h_surv;
-    rattle::hbuf<int32_t> h_res;
-    rattle::hbuf<double> h_var;
     rattle::hbuf<uint32_t> h_counter;
     // POA arena: kept across stages and calls (allocating ~100 GB costs seconds)
     uint8_t *poa_arena = nullptr;

@@ -1,4 +1,4 @@
-// Host orchestration of `rattle correct`, /root/reference/correct.cpp:311-563, over kernels C and D.
+// Host orchestration of `rattle correct`, the reference's correct.cpp:311-563, over kernels C and D.
 //
 // The reference runs a queue of packs through worker threads, two POAs per pack
 // (correct.cpp:398-405, 428-436) plus one per multi-pack cluster (:520-532).  Packs are
@@ -16,6 +16,20 @@
 // packs' reads and all consensi; correction_gather reassembles the single-GPU result on the root.
 //
 // Packs that do not fit the device are skipped and reported, never fatal (rattle_skip_list).
+//
+// One call is a `correct_job`: the state the steps share, and one member function per step.  correct_driver() at the end
+// of the file is the list of stages:
+//   plan      packs from ids and lengths (correct.cpp:328-370), this rank's share of them
+//   stage 1   POA #1 of every pack (:398-405) + fix ends + correction (:407-409); the corrected reads are compacted on
+//             the device and downloaded by a helper thread behind the later stages
+//   stage 2   POA #2 over the corrected reads of a pack, stably sorted by length desc (:427-445), + consensus vote
+//   stage 3   per-cluster consensus (:489-556): POA #3 over the pack consensi of a cluster with more than one pack
+// A POA #3 group is sequential in its number of packs, so the clusters with many packs would leave the device to one
+// workgroup each at the end.  When there are enough of them ("big" clusters), their packs go through POA #2 first (stage 2a)
+// and their POA #3 (3a) shares a device pass with the POA #2 of all other packs (2b); the remaining small POA #3 groups
+// follow (3b).  With several ranks each pass covers this rank's packs / groups and ends with an all-gather of its consensi.
+// (Round 4 also ran the big clusters' chain as a second flow on a helper context; round 5 removed it -- byte-identical but
+// slower, two stage-1 passes have two tails -- for the row loop of a lone workgroup, poa.hip: dp_rows_mt.)
 #include <algorithm>
 #include <cmath>
 #include <cstdlib>
@@ -125,15 +139,17 @@ hread oriented_read(const uint8_t *seq, const uint8_t *qual, const uint64_t *off
     return h;
 }
 
+// an array of the result for n entries (never a null pointer: at least one entry)
+template <typename T>
+T *result_array(size_t n) { return (T *)malloc(std::max<size_t>(1, n) * sizeof(T)); }
+
 void fill_set(rattle_read_set &S, const std::vector<hread> &v, const std::vector<int32_t> &cid, const std::vector<int32_t> &nr) {
-    S.n = (uint32_t)v.size();
-    size_t n = std::max<size_t>(1, v.size());
-    S.read_id = (int32_t *)malloc(n * 4); S.cluster_id = (int32_t *)malloc(n * 4); S.n_reads = (int32_t *)malloc(n * 4);
-    S.off = (uint64_t *)malloc((v.size() + 1) * 8);
     uint64_t tot = 0;
+    for (const hread &h : v) tot += h.seq.size();
+    alloc_read_set(S, (uint32_t)v.size(), tot);
+    tot = 0;
     for (size_t i = 0; i < v.size(); ++i) { S.off[i] = tot; tot += v[i].seq.size(); }
     S.off[v.size()] = tot;
-    S.seq = (char *)malloc(tot + 1); S.qual = (char *)malloc(tot + 1);
     for (size_t i = 0; i < v.size(); ++i) {
         S.read_id[i] = v[i].rid; S.cluster_id[i] = cid[i]; S.n_reads[i] = nr.empty() ? 0 : nr[i];
         const uint64_t p = S.off[i];
@@ -142,7 +158,6 @@ void fill_set(rattle_read_set &S, const std::vector<hread> &v, const std::vector
         memcpy(S.qual + p, v[i].qual.data(), ql);
         if (ql < v[i].seq.size()) memset(S.qual + p + ql, '!', v[i].seq.size() - ql);
     }
-    S.seq[tot] = 0; S.qual[tot] = 0;
 }
 
 // constants of kernel D: phred_symbol thresholds (host libm) and phred_err per quality byte (utils.cpp:10-13)
@@ -302,129 +317,124 @@ void put_rec(std::vector<uint8_t> &b, uint32_t id, uint32_t flag, const char *s,
     if (len) memcpy(b.data() + at + 12, s, len);
 }
 
-}  // namespace
+struct skip_t { int32_t cid; uint32_t pack, stage; std::vector<int32_t> rids; };
 
-int correct_driver(rattle_ctx *ctx, const uint8_t *seq, const uint8_t *qual, const uint64_t *off, uint32_t n_reads,
-                   uint32_t n_clusters, const uint32_t *coff, const int32_t *mid, const uint8_t *mrev,
-                   const rattle_correct_params *P, rattle_correction **out) {
-    char order[8] = {0};
-    memcpy(order, P->vote_order[0] ? P->vote_order : "U-GTCA", 6);
-    for (int i = 0; i < 6; ++i)
-        if (!order[i] || !strchr("ACGTU-", order[i])) { set_error("vote_order must be a permutation of ACGTU-"); return RATTLE_ERR_ARG; }
-    rattle_correction *R = (rattle_correction *)calloc(1, sizeof(rattle_correction));
-    *out = R;
-    hipStream_t st = ctx->stream;
-    phase_timer T_all("correct: total");
-    const int rank = ctx->xchg.rank, nranks = ctx->xchg.nranks;
-
-    // ---- correct.cpp:328-370 pack building: ids and strands only, the bases stay where they are
-    pack_plan PL;
-    RT_TRY(plan_packs(off, n_reads, n_clusters, coff, mid, mrev, P, nranks, PL));
-    const uint32_t n_packs = (uint32_t)PL.pk_cid.size();
+// One `correct` call: what its steps share, and the steps in the order correct_driver() runs them.
+struct correct_job {
+    rattle_ctx *const ctx;
+    const uint8_t *const seq, *const qual;           // the reads (host)
+    const uint64_t *const off;
+    const uint32_t n_reads, n_clusters;
+    const rattle_correct_params *const P;
+    const char *const order;                         // vote slot order
+    rattle_correction *const R;
+    const int rank, nranks;
+    const hipStream_t st;
     uint64_t counters[8] = {0, 0, 0, 0, 0, 0, 0, 0};
-    counters[2] = n_packs;
 
-    // the order a cluster's pack consensi enter POA #3 in (default: pack order)
-    std::vector<std::vector<uint32_t>> cl_perm(P->n_pack_orders ? n_clusters : 0);
-    for (uint32_t i = 0; i < P->n_pack_orders; ++i) {
-        if (!P->pack_order_cluster || !P->pack_order_offsets || !P->pack_order_perm) { set_error("pack order arrays missing"); return RATTLE_ERR_ARG; }
-        const uint32_t c = P->pack_order_cluster[i];
-        if (c >= n_clusters) { set_error("pack order: cluster out of range"); return RATTLE_ERR_ARG; }
-        const uint32_t a = P->pack_order_offsets[i], b = P->pack_order_offsets[i + 1];
-        std::vector<uint32_t> perm(P->pack_order_perm + a, P->pack_order_perm + b), chk(perm);
-        std::sort(chk.begin(), chk.end());
-        bool ok = b - a == PL.cl_np[c];
-        for (uint32_t t = 0; ok && t < chk.size(); ++t) ok = chk[t] == t;
-        if (!ok) { set_error("pack order of cluster " + std::to_string(c) + " is not a permutation of its " + std::to_string(PL.cl_np[c]) + " packs"); return RATTLE_ERR_ARG; }
-        cl_perm[c] = perm;
-    }
-
-    // my packs, in pack order (all of them on one rank)
-    std::vector<uint32_t> mine;
-    for (uint32_t p = 0; p < n_packs; ++p) if ((int)PL.pk_owner[p] == rank) mine.push_back(p);
-    const uint32_t nm = (uint32_t)mine.size();
-
-    // ---- POA #2 over the corrected reads of a pack, stably sorted by length desc (:427-445), + consensus vote;
-    // per-cluster consensus (:489-556) with POA #3 for clusters of more than one pack.
-    // A POA #3 group is sequential in its number of packs, so the clusters with many packs would leave the
-    // device to one workgroup each at the end.  When there are enough of them, their packs go through
-    // POA #2 first (stage 2a) and their POA #3 (stage 3a) runs beside other work; the remaining small POA #3 groups
-    // follow (stage 3b).  With several ranks each stage covers this rank's packs / groups and ends with an all-gather of
-    // its consensi.
-    // (RATTLE_BIG_CLUSTER_PACKS / RATTLE_BIG_MIN_PACKS override the two thresholds: tests force the split on small inputs)
-    const uint32_t BIG = std::max(2, getenv("RATTLE_BIG_CLUSTER_PACKS") ? atoi(getenv("RATTLE_BIG_CLUSTER_PACKS")) : 48);
-    const uint64_t big_min = getenv("RATTLE_BIG_MIN_PACKS") ? (uint64_t)atoll(getenv("RATTLE_BIG_MIN_PACKS")) : 1024;
-    std::vector<uint8_t> big(n_clusters, 0);
+    pack_plan PL;
+    uint32_t n_packs = 0, nm = 0;
+    std::vector<std::vector<uint32_t>> cl_perm;      // the order a cluster's pack consensi enter POA #3 in (default: pack order)
+    std::vector<uint32_t> mine;                      // my packs, in pack order (all of them on one rank); k below is an index in here
+    std::vector<uint8_t> big;                        // per cluster: its packs go through stage 2a, its POA #3 through 3a
     bool any_big = false;
-    {
-        uint64_t big_packs = 0;
-        for (uint32_t c = 0; c < n_clusters; ++c) if (PL.cl_np[c] >= BIG) big_packs += PL.cl_np[c];
-        if (big_packs >= big_min) for (uint32_t c = 0; c < n_clusters; ++c) { big[c] = PL.cl_np[c] >= BIG; any_big |= big[c] != 0; }
-    }
-    // (Round 4 also ran the big clusters' chain as a second flow on a helper context beside the POA #1 of everything else: byte-
-    // identical, but slower -- two stage-1 passes have two tails -- and removed in round 5.  What shortens the chain instead is the
-    // row loop of a lone workgroup: poa.hip, dp_rows_mt.)
-    struct s1group {
-        stage S;
-        std::vector<sref> r;                         // the group's pack members, pack after pack
-        std::vector<uint32_t> ks;                    // index in `mine` of each of its packs
-        std::vector<uint32_t> olen, tfront, tback;   // per member
-    } G[1];
-    std::vector<uint8_t> g_of(nm, 0);
-    std::vector<uint32_t> k_in(nm, 0);
-    G[0].S.first.assign(1, 0);
-    for (uint32_t k = 0; k < nm; ++k) {
-        const uint32_t p = mine[k];
-        const int g = 0;
-        g_of[k] = (uint8_t)g; k_in[k] = (uint32_t)G[g].ks.size();
-        G[g].ks.push_back(k);
-        for (uint32_t q = PL.first[p]; q < PL.first[p + 1]; ++q) G[g].r.push_back(PL.members[q]);
-        G[g].S.first.push_back((uint32_t)G[g].r.size());
-    }
 
-    // Several ranks: everything up to here depends on the arguments alone (the same on every rank).  From here on a rank
-    // works on its own packs, and a failure of its own (a bad base in one of ITS reads, a HIP error, an allocation) must not
-    // leave the other ranks blocked in the next all-gather: the rank remembers the error, keeps joining the exchanges with a
-    // failure record, and every rank returns an error after the exchange that carried it.
-    int local_rc = 0;
-    std::string local_msg;
-    auto local_step = [&](int r) -> bool {           // true: carry on with this rank's own work
-        if (r != 0 && local_rc == 0) { local_rc = r; local_msg = rattle_hip_last_error(); }
-        return local_rc == 0;
-    };
-#define LOCAL_TRY(call) do { if (local_rc == 0) { const int r_ = (call); if (r_ != 0) { if (nranks == 1) return r_; local_step(r_); } } } while (0)
+    // stage 1: first[k] .. first[k + 1] of S1 are the members of pack mine[k]
+    stage S1;
+    std::vector<sref> r;                             // my packs' members, pack after pack
+    std::vector<uint32_t> olen, tfront, tback;       // per member
+    dbuf<uint8_t> d_rseq, d_rqual;                   // the reads in HBM, unless they are staged there already
+    const uint8_t *dev_seq = nullptr, *dev_qual = nullptr;
+    dbuf<uint8_t> d_os, d_oq;                        // corrected reads, compacted on the device
+    std::thread d2h;                                 // ... and their download
+    hipError_t d2h_err = hipSuccess;
+    std::vector<uint32_t> cor_pack;
 
-    LOCAL_TRY(ensure_post_constants(ctx));
-    // only A, C, G, T, U are defined for the vote (an unordered_map key set in the reference)
-    {
-        bool ok[256] = {false};
-        ok['A'] = ok['C'] = ok['G'] = ok['T'] = ok['U'] = true;
-        std::atomic<int> bad(0);
-        const size_t chunk = 4096;
-        for (int g = 0; g < 1; ++g) {
-            const std::vector<sref> &R1 = G[g].r;
-            const size_t n1g = R1.size();
-            parallel_for((n1g + chunk - 1) / chunk, P->n_threads, [&](size_t c) {
-                for (size_t q = c * chunk; q < std::min<size_t>(n1g, (c + 1) * chunk); ++q)
-                    for (uint64_t b = off[R1[q].rid]; b < off[R1[q].rid + 1]; ++b)
-                        if (!ok[seq[b]]) { bad = 1; return; }
-            });
-        }
-        if (bad) {
-            set_error("correct: read contains a base other than A, C, G, T, U");
-            if (nranks == 1) return RATTLE_ERR_ARG;
-            local_step(RATTLE_ERR_ARG);
-        }
-    }
-
-    // skip list (this rank's share; unqueued entries on rank 0)
-    struct skip_t { int32_t cid; uint32_t pack, stage; std::vector<int32_t> rids; };
-    std::vector<skip_t> skips;
-
+    std::vector<uint8_t> pk_dead;                    // stage at which a pack was given up (this rank's packs: exact; others: from the exchange)
+    std::vector<std::string> pk_cons, cl_cons;       // pack consensus (POA #2) / cluster consensus, filled by the exchanges
+    std::vector<uint8_t> pk_has, cl_has;
+    std::vector<skip_t> skips;                       // skip list (this rank's share; unqueued entries on rank 0)
     std::vector<hread> uncorrected;
     std::vector<int32_t> unc_cid;
     std::vector<uint32_t> unc_pack;
-    if (rank == 0) {
+
+    // Several ranks: the plan depends on the arguments alone (the same on every rank).  After it a rank works on its own packs,
+    // and a failure of its own (a bad base in one of ITS reads, a HIP error, an allocation) must not leave the other ranks
+    // blocked in the next all-gather: the rank remembers the error, keeps joining the exchanges with a failure record, and
+    // every rank returns an error after the exchange that carried it.
+    int local_rc = 0;
+    std::string local_msg;
+
+    ~correct_job() { if (d2h.joinable()) d2h.join(); }      // on every way out, before d_os / d_oq go
+
+    // the result of a step of this rank's own work: a single rank returns its error at once, one of several remembers its first
+    int own_error(int rc) {
+        if (rc == 0 || nranks == 1) return rc;
+        if (local_rc == 0) { local_rc = rc; local_msg = rattle_hip_last_error(); }
+        return 0;
+    }
+
+    int set_pack_orders() {
+        cl_perm.resize(P->n_pack_orders ? n_clusters : 0);
+        for (uint32_t i = 0; i < P->n_pack_orders; ++i) {
+            if (!P->pack_order_cluster || !P->pack_order_offsets || !P->pack_order_perm) { set_error("pack order arrays missing"); return RATTLE_ERR_ARG; }
+            const uint32_t c = P->pack_order_cluster[i];
+            if (c >= n_clusters) { set_error("pack order: cluster out of range"); return RATTLE_ERR_ARG; }
+            const uint32_t a = P->pack_order_offsets[i], b = P->pack_order_offsets[i + 1];
+            std::vector<uint32_t> perm(P->pack_order_perm + a, P->pack_order_perm + b), chk(perm);
+            std::sort(chk.begin(), chk.end());
+            bool ok = b - a == PL.cl_np[c];
+            for (uint32_t t = 0; ok && t < chk.size(); ++t) ok = chk[t] == t;
+            if (!ok) { set_error("pack order of cluster " + std::to_string(c) + " is not a permutation of its " + std::to_string(PL.cl_np[c]) + " packs"); return RATTLE_ERR_ARG; }
+            cl_perm[c] = perm;
+        }
+        return 0;
+    }
+
+    // ---- correct.cpp:328-370 pack building: ids and strands only, the bases stay where they are; then this rank's share
+    int plan(const uint32_t *coff, const int32_t *mid, const uint8_t *mrev) {
+        RT_TRY(plan_packs(off, n_reads, n_clusters, coff, mid, mrev, P, nranks, PL));
+        n_packs = (uint32_t)PL.pk_cid.size();
+        counters[2] = n_packs;
+        RT_TRY(set_pack_orders());
+        pk_dead.assign(n_packs, 0); pk_cons.resize(n_packs); pk_has.assign(n_packs, 0);
+        cl_cons.resize(n_clusters); cl_has.assign(n_clusters, 0);
+        S1.first.assign(1, 0);
+        for (uint32_t p = 0; p < n_packs; ++p) {
+            if ((int)PL.pk_owner[p] != rank) continue;
+            mine.push_back(p);
+            r.insert(r.end(), PL.members.begin() + PL.first[p], PL.members.begin() + PL.first[p + 1]);
+            S1.first.push_back((uint32_t)r.size());
+        }
+        nm = (uint32_t)mine.size();
+        // (RATTLE_BIG_CLUSTER_PACKS / RATTLE_BIG_MIN_PACKS override the two thresholds: tests force the split on small inputs)
+        const uint32_t BIG = std::max(2, getenv("RATTLE_BIG_CLUSTER_PACKS") ? atoi(getenv("RATTLE_BIG_CLUSTER_PACKS")) : 48);
+        const uint64_t big_min = getenv("RATTLE_BIG_MIN_PACKS") ? (uint64_t)atoll(getenv("RATTLE_BIG_MIN_PACKS")) : 1024;
+        big.assign(n_clusters, 0);
+        uint64_t big_packs = 0;
+        for (uint32_t c = 0; c < n_clusters; ++c) if (PL.cl_np[c] >= BIG) big_packs += PL.cl_np[c];
+        if (big_packs >= big_min) for (uint32_t c = 0; c < n_clusters; ++c) { big[c] = PL.cl_np[c] >= BIG; any_big |= big[c] != 0; }
+        return 0;
+    }
+
+    // only A, C, G, T, U are defined for the vote (an unordered_map key set in the reference)
+    int check_bases() {
+        bool ok[256] = {false};
+        ok['A'] = ok['C'] = ok['G'] = ok['T'] = ok['U'] = true;
+        std::atomic<int> bad(0);
+        const size_t chunk = 4096, n1 = r.size();
+        parallel_for((n1 + chunk - 1) / chunk, P->n_threads, [&](size_t c) {
+            for (size_t q = c * chunk; q < std::min<size_t>(n1, (c + 1) * chunk); ++q)
+                for (uint64_t b = off[r[q].rid]; b < off[r[q].rid + 1]; ++b)
+                    if (!ok[seq[b]]) { bad = 1; return; }
+        });
+        if (bad) { set_error("correct: read contains a base other than A, C, G, T, U"); return RATTLE_ERR_ARG; }
+        return 0;
+    }
+
+    // members of packs that are never queued: uncorrected as they are (rank 0), those of the max_pack_cells rule reported
+    void unqueued_reads() {
+        if (rank != 0) return;
         for (size_t i = 0; i < PL.small.size(); ++i) {
             uncorrected.push_back(oriented_read(seq, qual, off, PL.small[i], 0, 0));
             unc_cid.push_back(PL.small_cid[i]); unc_pack.push_back(0xFFFFFFFFu);
@@ -436,21 +446,8 @@ int correct_driver(rattle_ctx *ctx, const uint8_t *seq, const uint8_t *qual, con
         }
     }
 
-    std::vector<uint8_t> pk_dead(n_packs, 0);       // stage at which a pack was given up (this rank's packs: exact; others: from the exchange)
-    std::vector<std::string> pk_cons(n_packs);       // pack consensus (POA #2), filled for every pack by the exchanges
-    std::vector<uint8_t> pk_has(n_packs, 0);
-    std::vector<std::string> cl_cons(n_clusters);
-    std::vector<uint8_t> cl_has(n_clusters, 0);
-    dbuf<uint8_t> d_os, d_oq;                        // corrected reads, compacted on the device
-    std::thread d2h;
-    hipError_t d2h_err = hipSuccess;
-    struct joiner { std::thread &t; ~joiner() { if (t.joinable()) t.join(); } } d2h_join{d2h};      // also on error returns
-    std::vector<uint32_t> cor_pack;
-
-    // ---- reads -> HBM once (both groups gather from them)
-    dbuf<uint8_t> d_rseq, d_rqual;
-    const uint8_t *dev_seq = nullptr, *dev_qual = nullptr;
-    auto upload_reads = [&]() -> int {
+    // ---- reads -> HBM once
+    int upload_reads() {
         const uint64_t total_in = off[n_reads];
         if (ctx->staged_seq_key == seq && ctx->staged_qual_key == qual && ctx->staged_n == n_reads && ctx->staged_total == total_in && off[0] == 0) {
             dev_seq = ctx->d_staged_seq.p; dev_qual = ctx->d_staged_qual.p;       // resident (rattle_hip_stage_reads)
@@ -462,140 +459,144 @@ int correct_driver(rattle_ctx *ctx, const uint8_t *seq, const uint8_t *qual, con
             dev_seq = d_rseq.p; dev_qual = d_rqual.p;
         }
         return 0;
-    };
-    // ---- stage 1 of one group: oriented pack members gathered (:343-346), POA #1 (correct.cpp:398-405) + fix ends +
-    // correction (:407-409); lengths back to the host
-    auto stage1_group = [&](int g, uint64_t *cnt) -> int {
-        s1group &X = G[g];
-        const uint32_t n1 = (uint32_t)X.r.size();
-        X.olen.assign(n1 + 1, 0); X.tfront.assign(n1 + 1, 0); X.tback.assign(n1 + 1, 0);
-        if (X.ks.empty()) return 0;
+    }
+
+    // ---- stage 1: oriented pack members gathered (:343-346), POA #1 (correct.cpp:398-405) + fix ends + correction (:407-409);
+    // lengths back to the host
+    int stage1() {
+        const uint32_t n1 = (uint32_t)r.size();
+        olen.assign(n1 + 1, 0); tfront.assign(n1 + 1, 0); tback.assign(n1 + 1, 0);
         std::vector<gather_desc> desc(n1);
-        X.S.off.assign(n1 + 1, 0);
+        S1.off.assign(n1 + 1, 0);
         for (uint32_t q = 0; q < n1; ++q) {
-            const uint32_t len = (uint32_t)(off[X.r[q].rid + 1] - off[X.r[q].rid]);
-            desc[q] = gather_desc{off[X.r[q].rid], X.S.off[q], len, X.r[q].rev};
-            X.S.off[q + 1] = X.S.off[q] + len;
+            const uint32_t len = (uint32_t)(off[r[q].rid + 1] - off[r[q].rid]);
+            desc[q] = gather_desc{off[r[q].rid], S1.off[q], len, r[q].rev};
+            S1.off[q + 1] = S1.off[q] + len;
         }
         phase_timer T("correct: stage 1", &ctx->stage_ms[1]);
-        RT_TRY(run_stage(ctx, X.S, desc, {gather_part{0, n1, dev_seq, dev_qual}}, 1, P, order, cnt));
-        RT_HIP(hipMemcpyAsync(X.olen.data(), X.S.olen.p, (size_t)n1 * 4, hipMemcpyDeviceToHost, st));
-        RT_HIP(hipMemcpyAsync(X.tfront.data(), X.S.tfront.p, (size_t)n1 * 4, hipMemcpyDeviceToHost, st));
-        RT_HIP(hipMemcpyAsync(X.tback.data(), X.S.tback.p, (size_t)n1 * 4, hipMemcpyDeviceToHost, st));
+        RT_TRY(run_stage(ctx, S1, desc, {gather_part{0, n1, dev_seq, dev_qual}}, 1, P, order, counters));
+        RT_HIP(hipMemcpyAsync(olen.data(), S1.olen.p, (size_t)n1 * 4, hipMemcpyDeviceToHost, st));
+        RT_HIP(hipMemcpyAsync(tfront.data(), S1.tfront.p, (size_t)n1 * 4, hipMemcpyDeviceToHost, st));
+        RT_HIP(hipMemcpyAsync(tback.data(), S1.tback.p, (size_t)n1 * 4, hipMemcpyDeviceToHost, st));
         RT_HIP(hipStreamSynchronize(st));
-        X.S.seq.release(); X.S.qual.release(); X.S.col.release();
-        for (uint32_t kk = 0; kk < X.ks.size(); ++kk)
-            if (X.S.skipped[kk]) {                    // POA #1 did not fit: the pack's reads stay as they are
-                pk_dead[mine[X.ks[kk]]] = 1;
-                for (uint32_t q = X.S.first[kk]; q < X.S.first[kk + 1]; ++q) { X.olen[q] = 0; X.tfront[q] = 0; X.tback[q] = 0; }
+        S1.seq.release(); S1.qual.release(); S1.col.release();
+        for (uint32_t k = 0; k < nm; ++k)
+            if (S1.skipped[k]) {                      // POA #1 did not fit: the pack's reads stay as they are
+                pk_dead[mine[k]] = 1;
+                for (uint32_t q = S1.first[k]; q < S1.first[k + 1]; ++q) { olen[q] = 0; tfront[q] = 0; tback[q] = 0; }
             }
         return 0;
-    };
-    // ---- after both groups: skip entries, corrected reads in pack order (:413-425) compacted on the device and downloaded
+    }
+
+    // where member q of my pack k lies in the stage-1 row matrix: kernel D left the corrected read at the start of its row
+    uint64_t row_of(uint32_t k, uint32_t q) const { return S1.moff[k] + (uint64_t)(q - S1.first[k]) * S1.width[k]; }
+
+    // ---- after stage 1: skip entries, corrected reads in pack order (:413-425) compacted on the device and downloaded
     // behind the later stages, reads whose corrected sequence came out empty
-    auto stage1_finish = [&]() -> int {
+    int stage1_finish() {
         for (uint32_t k = 0; k < nm; ++k) {
-            const s1group &X = G[g_of[k]];
-            const uint32_t kk = k_in[k];
-            if (!X.S.skipped[kk]) continue;
+            if (!S1.skipped[k]) continue;
             skips.push_back(skip_t{PL.pk_cid[mine[k]], PL.pk_local[mine[k]], 1u, {}});
-            for (uint32_t q = X.S.first[kk]; q < X.S.first[kk + 1]; ++q) skips.back().rids.push_back(X.r[q].rid);
+            for (uint32_t q = S1.first[k]; q < S1.first[k + 1]; ++q) skips.back().rids.push_back(r[q].rid);
         }
         {
             phase_timer T("correct: corrected reads D2H");
-            std::vector<gather_desc> od[1];
+            std::vector<gather_desc> od;
             std::vector<int32_t> o_rid, o_cid;
             uint64_t tot = 0;
-            for (uint32_t k = 0; k < nm; ++k) {
-                const int g = g_of[k];
-                const s1group &X = G[g];
-                const uint32_t kk = k_in[k];
-                for (uint32_t q = X.S.first[kk]; q < X.S.first[kk + 1]; ++q) {
-                    if (X.olen[q] == 0) continue;
-                    od[g].push_back(gather_desc{X.S.moff[kk] + (uint64_t)(q - X.S.first[kk]) * X.S.width[kk], tot, X.olen[q], 0u});
-                    o_rid.push_back(X.r[q].rid); o_cid.push_back(PL.pk_cid[mine[k]]);
+            for (uint32_t k = 0; k < nm; ++k)
+                for (uint32_t q = S1.first[k]; q < S1.first[k + 1]; ++q) {
+                    if (olen[q] == 0) continue;
+                    od.push_back(gather_desc{row_of(k, q), tot, olen[q], 0u});
+                    o_rid.push_back(r[q].rid); o_cid.push_back(PL.pk_cid[mine[k]]);
                     cor_pack.push_back(mine[k]);
-                    tot += X.olen[q];
+                    tot += olen[q];
                 }
-            }
             rattle_read_set &C = R->corrected;
-            const size_t nc = o_rid.size();
-            C.n = (uint32_t)nc;
-            C.read_id = (int32_t *)malloc(std::max<size_t>(1, nc) * 4); C.cluster_id = (int32_t *)malloc(std::max<size_t>(1, nc) * 4);
-            C.n_reads = (int32_t *)malloc(std::max<size_t>(1, nc) * 4); C.off = (uint64_t *)malloc((nc + 1) * 8);
-            C.seq = (char *)malloc(tot + 1); C.qual = (char *)malloc(tot + 1);
-            C.seq[tot] = 0; C.qual[tot] = 0;
-            {
-                for (size_t i = 0; i < nc; ++i) { C.off[i] = od[0][i].dst; C.read_id[i] = o_rid[i]; C.cluster_id[i] = o_cid[i]; C.n_reads[i] = 0; }
-            }
+            const size_t nc = od.size();
+            alloc_read_set(C, (uint32_t)nc, tot);
+            for (size_t i = 0; i < nc; ++i) { C.off[i] = od[i].dst; C.read_id[i] = o_rid[i]; C.cluster_id[i] = o_cid[i]; C.n_reads[i] = 0; }
             C.off[nc] = tot;
             if (nc) {
-                make_room(ctx, 2 * (tot + 64) + od[0].size() * sizeof(gather_desc));
+                make_room(ctx, 2 * (tot + 64) + nc * sizeof(gather_desc));
                 RT_TRY(d_os.reserve(tot + 64)); RT_TRY(d_oq.reserve(tot + 64));
-                for (int g = 0; g < 1; ++g) {
-                    if (od[g].empty()) continue;
-                    dbuf<gather_desc> d_od;
-                    RT_TRY(d_od.reserve(od[g].size()));
-                    RT_HIP(hipMemcpyAsync(d_od.p, od[g].data(), od[g].size() * sizeof(gather_desc), hipMemcpyHostToDevice, st));
-                    RT_TRY(launch_gather(ctx, d_od.p, (uint32_t)od[g].size(), G[g].S.rowc.p, G[g].S.rowq.p, d_os.p, d_oq.p));
-                    RT_HIP(hipStreamSynchronize(st));
-                    d_od.release();
-                }
+                dbuf<gather_desc> d_od;
+                RT_TRY(d_od.reserve(nc));
+                RT_HIP(hipMemcpyAsync(d_od.p, od.data(), nc * sizeof(gather_desc), hipMemcpyHostToDevice, st));
+                RT_TRY(launch_gather(ctx, d_od.p, (uint32_t)nc, S1.rowc.p, S1.rowq.p, d_os.p, d_oq.p));
+                RT_HIP(hipStreamSynchronize(st));
+                d_od.release();
                 // the download (2 GB at 1e6 reads, pageable destination) runs on a helper thread and the
                 // copy engine while the following POA stages compute
-                char *dst_s = C.seq, *dst_q = C.qual;
-                const uint8_t *src_s = d_os.p, *src_q = d_oq.p;
-                const int dev = ctx->device;
-                const rattle_read_set *ready_set = &R->corrected;
-                const uint32_t *ready_pack = cor_pack.data();
-                auto ready_fn = P->corrected_ready;
-                void *ready_user = P->corrected_ready_user;
-                d2h = std::thread([=, &d2h_err]() {
-                    hipError_t e = hipSetDevice(dev);
-                    if (e == hipSuccess) e = hipMemcpy(dst_s, src_s, tot, hipMemcpyDeviceToHost);
-                    if (e == hipSuccess) e = hipMemcpy(dst_q, src_q, tot, hipMemcpyDeviceToHost);
+                // (nothing it reads -- the set, d_os / d_oq, cor_pack -- changes before it is joined)
+                d2h = std::thread([this, tot]() {
+                    const rattle_read_set &C = R->corrected;
+                    hipError_t e = hipSetDevice(ctx->device);
+                    if (e == hipSuccess) e = hipMemcpy(C.seq, d_os.p, tot, hipMemcpyDeviceToHost);
+                    if (e == hipSuccess) e = hipMemcpy(C.qual, d_oq.p, tot, hipMemcpyDeviceToHost);
                     d2h_err = e;
                     // the corrected reads are final from here on: the caller may start writing them out while POA #2 / #3 run
-                    if (e == hipSuccess && ready_fn) ready_fn(ready_user, ready_set, ready_pack);
+                    if (e == hipSuccess && P->corrected_ready) P->corrected_ready(P->corrected_ready_user, &C, cor_pack.data());
                 });
             }
         }
         // reads whose corrected sequence came out empty: uncorrected, as fix_msa_ends left them (:289-293)
-        for (uint32_t k = 0; k < nm; ++k) {
-            const s1group &X = G[g_of[k]];
-            const uint32_t kk = k_in[k];
-            for (uint32_t q = X.S.first[kk]; q < X.S.first[kk + 1]; ++q)
-                if (X.olen[q] == 0) {
-                    uncorrected.push_back(oriented_read(seq, qual, off, X.r[q], X.tfront[q], X.tback[q]));
+        for (uint32_t k = 0; k < nm; ++k)
+            for (uint32_t q = S1.first[k]; q < S1.first[k + 1]; ++q)
+                if (olen[q] == 0) {
+                    uncorrected.push_back(oriented_read(seq, qual, off, r[q], tfront[q], tback[q]));
                     unc_cid.push_back(PL.pk_cid[mine[k]]); unc_pack.push_back(mine[k]);
                 }
-        }
         return 0;
-    };
+    }
 
-    std::vector<uint32_t> slot_of(n_packs, 0xFFFFFFFFu);   // my pack -> index in `mine`
-    for (uint32_t k = 0; k < nm; ++k) slot_of[mine[k]] = k;
+    // the download is over (the stage-1 rows are no longer needed once it is)
+    int join_download() {
+        if (d2h.joinable()) d2h.join();
+        if (d2h_err == hipSuccess) return 0;
+        set_error(std::string("corrected reads download: ") + hipGetErrorString(d2h_err));
+        return RATTLE_ERR_HIP;
+    }
 
     // the live packs of a cluster in the order their consensi enter POA #3
-    auto group_of = [&](uint32_t c, std::vector<uint32_t> &g) {
+    void group_of(uint32_t c, std::vector<uint32_t> &g) const {
         g.clear();
         for (uint32_t t = 0; t < PL.cl_np[c]; ++t) {
             const uint32_t p = PL.cl_p0[c] + (cl_perm.empty() || cl_perm[c].empty() ? t : cl_perm[c][t]);
             if (pk_has[p]) g.push_back(p);
         }
-    };
-    // exchange the results of one stage: pack consensi (kind 0) and cluster consensi (kind 1), dead flags included
-    // (my_rc / my_msg: this rank's own failure so far -- the main flow passes local_rc, the side flow its own)
-    auto exchange_stage = [&](std::vector<uint8_t> &mine_bytes, const int my_rc, const std::string &my_msg) -> int {
+    }
+
+    // The POA #3 groups of the big (or of the other) clusters that fall to this rank, once their pack consensi are in: a
+    // group is sequential in its g packs, cost g^2 x length, LPT over ranks.  A cluster with one live pack takes that pack's
+    // consensus as it is.  n_all: the groups of all ranks.
+    std::vector<uint32_t> poa3_groups(bool of_big, size_t *n_all = nullptr) {
+        std::vector<uint32_t> all, own, g, my;
+        std::vector<uint64_t> cost;
+        for (uint32_t c = 0; c < n_clusters; ++c) {
+            if ((big[c] != 0) != of_big || PL.cl_np[c] == 0) continue;
+            group_of(c, g);
+            if (g.size() > 1) { all.push_back(c); cost.push_back((uint64_t)g.size() * g.size() * pk_cons[g[0]].size()); }
+            else if (g.size() == 1) { cl_cons[c] = pk_cons[g[0]]; cl_has[c] = 1; }
+        }
+        lpt_assign(cost, nranks, own);
+        for (size_t i = 0; i < all.size(); ++i) if ((int)own[i] == rank) my.push_back(all[i]);
+        if (n_all) *n_all = all.size();
+        return my;
+    }
+
+    // exchange the results of one stage: pack consensi (kind 0) and cluster consensi (kind 1), dead flags included; a rank
+    // that has failed sends the failure record instead, and every rank returns an error
+    int exchange_stage(std::vector<uint8_t> &mine_bytes) {
         std::vector<std::vector<uint8_t>> all;
         if (nranks > 1) {
-            if (my_rc) { mine_bytes.clear(); put_rec(mine_bytes, 0xFFFFFFFFu, 0xFFFFFFFFu, nullptr, 0); }      // failure record
+            if (local_rc) { mine_bytes.clear(); put_rec(mine_bytes, 0xFFFFFFFFu, 0xFFFFFFFFu, nullptr, 0); }      // failure record
             RT_TRY(xchg_allgatherv(ctx, mine_bytes, all));
-            if (my_rc) { set_error(my_msg); return my_rc; }
-            for (int r = 0; r < nranks; ++r) {
+            if (local_rc) { set_error(local_msg); return local_rc; }
+            for (int rk = 0; rk < nranks; ++rk) {
                 uint32_t id = 0, flag = 0;
-                if (all[r].size() >= 12) { memcpy(&id, all[r].data(), 4); memcpy(&flag, all[r].data() + 4, 4); }
-                if (id == 0xFFFFFFFFu && flag == 0xFFFFFFFFu) { set_error("correct_reads failed on rank " + std::to_string(r)); return RATTLE_ERR_HIP; }
+                if (all[rk].size() >= 12) { memcpy(&id, all[rk].data(), 4); memcpy(&flag, all[rk].data() + 4, 4); }
+                if (id == 0xFFFFFFFFu && flag == 0xFFFFFFFFu) { set_error("correct_reads failed on rank " + std::to_string(rk)); return RATTLE_ERR_HIP; }
             }
         } else if (xchg_recording(ctx)) RT_TRY(xchg_allgatherv(ctx, mine_bytes, all));      // (measurement aid, common.h)
         else { all.resize(1); all[0].swap(mine_bytes); }
@@ -612,13 +613,14 @@ int correct_driver(rattle_ctx *ctx, const uint8_t *seq, const uint8_t *qual, con
             }
         }
         return 0;
-    };
-    // POA #2 over a list of my packs (indices in `mine`, all of ONE stage-1 group) + POA #3 over a list of clusters (groups of pack
-    // consensi from the host) in one device pass on context `cx`; results into `bytes`, skipped packs into `sk`, work counters into `cnt`
-    auto cons_pass = [&](rattle_ctx *cx, const char *name, const std::vector<uint32_t> &slots2, const std::vector<uint32_t> &clusters3,
-                         std::vector<uint8_t> &bytes, std::vector<skip_t> &sk, uint64_t *cnt) -> int {
+    }
+
+    // POA #3 over a list of clusters (groups of pack consensi, from the host) + POA #2 over a list of my packs (indices in `mine`;
+    // their corrected reads, from the stage-1 rows) in one device pass, timed into stage_ms[ms_slot]; results into `bytes`,
+    // skipped groups and packs onto the skip list -- in the order the sequential flow meets them: 2a, then 3a before 2b, then 3b
+    int cons_pass(const char *name, int ms_slot, const std::vector<uint32_t> &slots2, const std::vector<uint32_t> &clusters3, std::vector<uint8_t> &bytes) {
         if (slots2.empty() && clusters3.empty()) return 0;
-        phase_timer T(name, !strcmp(name, "correct: stage 2a") ? &ctx->stage_ms[2] : !strcmp(name, "correct: stage 2b+3a") ? &ctx->stage_ms[3] : !strcmp(name, "correct: stage 3b") ? &ctx->stage_ms[4] : nullptr);
+        phase_timer T(name, &ctx->stage_ms[ms_slot]);
         cons_stage C;
         stage &S = C.S;
         std::vector<gather_desc> d;
@@ -634,149 +636,132 @@ int correct_driver(rattle_ctx *ctx, const uint8_t *seq, const uint8_t *qual, con
             S.first.push_back((uint32_t)S.off.size() - 1);
         }
         const uint32_t n3 = (uint32_t)d.size();
-        const s1group *X = slots2.empty() ? nullptr : &G[g_of[slots2[0]]];
         for (uint32_t k : slots2) {                  // my pack k's corrected reads, length-sorted
-            const uint32_t kk = k_in[k];
             rows.clear();
-            for (uint32_t q = X->S.first[kk]; q < X->S.first[kk + 1]; ++q) if (X->olen[q]) rows.push_back(q);
-            std::stable_sort(rows.begin(), rows.end(), [&](uint32_t a, uint32_t b) { return X->olen[a] > X->olen[b]; });
+            for (uint32_t q = S1.first[k]; q < S1.first[k + 1]; ++q) if (olen[q]) rows.push_back(q);
+            std::stable_sort(rows.begin(), rows.end(), [&](uint32_t a, uint32_t b) { return olen[a] > olen[b]; });
             for (uint32_t q : rows) {
-                d.push_back(gather_desc{X->S.moff[kk] + (uint64_t)(q - X->S.first[kk]) * X->S.width[kk], S.off.back(), X->olen[q], 0u});
-                S.off.push_back(S.off.back() + X->olen[q]);
+                d.push_back(gather_desc{row_of(k, q), S.off.back(), olen[q], 0u});
+                S.off.push_back(S.off.back() + olen[q]);
             }
             S.first.push_back((uint32_t)S.off.size() - 1);
         }
         dbuf<uint8_t> d_in;
-        make_room(cx, C.h_in.size() + 64);
+        make_room(ctx, C.h_in.size() + 64);
         RT_TRY(d_in.reserve(C.h_in.size() + 64));
-        if (!C.h_in.empty()) RT_HIP(hipMemcpyAsync(d_in.p, C.h_in.data(), C.h_in.size(), hipMemcpyHostToDevice, cx->stream));
-        RT_TRY(run_stage(cx, S, d, {gather_part{0, n3, d_in.p, nullptr}, gather_part{n3, (uint32_t)d.size() - n3, X ? X->S.rowc.p : nullptr, nullptr}}, 2, P, order, cnt));
-        RT_TRY(fetch_consensi(cx, C));
+        if (!C.h_in.empty()) RT_HIP(hipMemcpyAsync(d_in.p, C.h_in.data(), C.h_in.size(), hipMemcpyHostToDevice, st));
+        RT_TRY(run_stage(ctx, S, d, {gather_part{0, n3, d_in.p, nullptr}, gather_part{n3, (uint32_t)d.size() - n3, slots2.empty() ? nullptr : S1.rowc.p, nullptr}},
+                         2, P, order, counters));
+        RT_TRY(fetch_consensi(ctx, C));
         uint32_t slot = 0;
         for (uint32_t c : clusters3) {
             if (S.skipped[slot]) {
-                sk.push_back(skip_t{(int32_t)c, 0u, 3u, {}});
+                skips.push_back(skip_t{(int32_t)c, 0u, 3u, {}});
                 put_rec(bytes, c, 1u | (3u << 1), nullptr, 0);
             } else put_rec(bytes, c, 1u, (const char *)C.cons.data() + S.coff[slot], C.len[slot]);
             ++slot;
         }
         for (uint32_t k : slots2) {
-            const uint32_t p = mine[k], kk = k_in[k];
+            const uint32_t p = mine[k];
             if (S.skipped[slot]) {
-                sk.push_back(skip_t{PL.pk_cid[p], PL.pk_local[p], 2u, {}});
-                for (uint32_t q = X->S.first[kk]; q < X->S.first[kk + 1]; ++q) sk.back().rids.push_back(X->r[q].rid);
+                skips.push_back(skip_t{PL.pk_cid[p], PL.pk_local[p], 2u, {}});
+                for (uint32_t q = S1.first[k]; q < S1.first[k + 1]; ++q) skips.back().rids.push_back(r[q].rid);
                 put_rec(bytes, p, 2u << 1, nullptr, 0);
             } else put_rec(bytes, p, 0u, (const char *)C.cons.data() + S.coff[slot], C.len[slot]);
             ++slot;
         }
         return 0;
-    };
-    // the POA #3 groups of the big clusters that fall to this rank (LPT over ranks), once their pack consensi are in
-    auto big_groups = [&](std::vector<uint32_t> &g3a) {
-        std::vector<uint32_t> g3a_all, own, g;
-        std::vector<uint64_t> cost;
-        for (uint32_t c = 0; c < n_clusters; ++c) {
-            if (!big[c]) continue;
-            group_of(c, g);
-            if (g.size() > 1) { g3a_all.push_back(c); cost.push_back((uint64_t)g.size() * g.size() * pk_cons[g[0]].size()); }
-            else if (g.size() == 1) { cl_cons[c] = pk_cons[g[0]]; cl_has[c] = 1; }
-        }
-        lpt_assign(cost, nranks, own);
-        for (size_t i = 0; i < g3a_all.size(); ++i) if ((int)own[i] == rank) g3a.push_back(g3a_all[i]);
-    };
+    }
 
-    uint64_t cnt_main[8] = {0};
-    std::vector<skip_t> sk_2a, sk_3a, sk_2b, sk_3b;
-    std::vector<uint8_t> bytes_3b;
-    if (nm) LOCAL_TRY(upload_reads());
-    if (nm) LOCAL_TRY(stage1_group(0, cnt_main));
-    if (nm && local_rc == 0) LOCAL_TRY(stage1_finish());
-    d_rseq.release(); d_rqual.release();
-    std::vector<uint8_t> bytes;
-    // packs given up in stage 1 are announced with the first exchange
-    for (uint32_t k = 0; k < nm; ++k) if (pk_dead[mine[k]] == 1) put_rec(bytes, mine[k], 1u << 1, nullptr, 0);
-    // stage 2a: my packs of the big clusters
-    std::vector<uint32_t> s2a, s2b;
-    for (uint32_t k = 0; k < nm; ++k) if (!pk_dead[mine[k]]) (big[PL.pk_cid[mine[k]]] ? s2a : s2b).push_back(k);
-    LOCAL_TRY(cons_pass(ctx, "correct: stage 2a", s2a, {}, bytes, sk_2a, cnt_main));
-    if (any_big) { RT_TRY(exchange_stage(bytes, local_rc, local_msg)); bytes.clear(); }
-    // stage 2b+3a: POA #3 groups of the big clusters (LPT over ranks), then my packs of all other clusters
-    std::vector<uint32_t> g3a;
-    big_groups(g3a);
-    LOCAL_TRY(cons_pass(ctx, "correct: stage 2b+3a", s2b, g3a, bytes, sk_3a, cnt_main));
-    RT_TRY(exchange_stage(bytes, local_rc, local_msg));
-    if (!nm || local_rc) {
-        if (d2h.joinable()) d2h.join();
-        if (R->corrected.off) { rattle_read_set &C = R->corrected; free(C.read_id); free(C.cluster_id); free(C.n_reads); free(C.off); free(C.seq); free(C.qual); C = rattle_read_set(); }
-        fill_set(R->corrected, {}, {}, {});
-        cor_pack.clear();
-    }
-    {
-        if (d2h.joinable()) d2h.join();                  // the stage-1 rows are no longer needed once the download is done
-        if (d2h_err != hipSuccess) {
-            set_error(std::string("corrected reads download: ") + hipGetErrorString(d2h_err));
-            if (nranks == 1) return RATTLE_ERR_HIP;
-            local_step(RATTLE_ERR_HIP);
-        }
-        G[0].S.release();
-        // stage 3b: POA #3 of the other clusters with more than one live pack
-        std::vector<uint32_t> g3b_all, g3b, own, g;
-        std::vector<uint64_t> cost;
+    // ---- the three read sets, the pack of every read, the skip list, the counters
+    void assemble() {
+        if (!nm) fill_set(R->corrected, {}, {}, {});      // (else: stage1_finish)
+        std::vector<hread> consensi;
+        std::vector<int32_t> con_cid, con_n;
         for (uint32_t c = 0; c < n_clusters; ++c) {
-            if (big[c] || PL.cl_np[c] == 0) continue;
-            group_of(c, g);
-            if (g.size() > 1) { g3b_all.push_back(c); cost.push_back((uint64_t)g.size() * g.size() * pk_cons[g[0]].size()); }
-            else if (g.size() == 1) { cl_cons[c] = pk_cons[g[0]]; cl_has[c] = 1; }
+            if (!cl_has[c]) continue;
+            int total = 0;
+            for (uint32_t p = PL.cl_p0[c]; p < PL.cl_p0[c] + PL.cl_np[c]; ++p) if (pk_has[p]) total += (int)(PL.first[p + 1] - PL.first[p]);
+            const std::string &s = cl_cons[c];
+            consensi.push_back(hread{s, std::string(s.size(), 'K'), -1});
+            con_cid.push_back((int32_t)c);
+            con_n.push_back(total);
         }
-        lpt_assign(cost, nranks, own);
-        for (size_t i = 0; i < g3b_all.size(); ++i) if ((int)own[i] == rank) g3b.push_back(g3b_all[i]);
-        LOCAL_TRY(cons_pass(ctx, "correct: stage 3b", {}, g3b, bytes_3b, sk_3b, cnt_main));
-        // several ranks: this exchange always takes place, so that every rank leaves with the same verdict (the caller's
-        // next collective is the gather of the corrected reads)
-        if (!g3b_all.empty() || nranks > 1 || xchg_recording(ctx)) RT_TRY(exchange_stage(bytes_3b, local_rc, local_msg));
-    }
-    // skipped packs of the consensus stages in the order the sequential flow meets them: 2a, then 3a before 2b (one pass), then 3b
-    for (std::vector<skip_t> *v : {&sk_2a, &sk_3a, &sk_2b, &sk_3b}) for (skip_t &x : *v) skips.push_back(std::move(x));
-    counters[0] += cnt_main[0];
-    counters[1] += cnt_main[1];
-    counters[5] += cnt_main[5]; counters[6] += cnt_main[6]; counters[7] += cnt_main[7];
-    if (d2h.joinable()) d2h.join();
-    d_os.release(); d_oq.release();
-#undef LOCAL_TRY
-
-    std::vector<hread> consensi;
-    std::vector<int32_t> con_cid, con_n;
-    for (uint32_t c = 0; c < n_clusters; ++c) {
-        if (!cl_has[c]) continue;
-        int total = 0;
-        for (uint32_t p = PL.cl_p0[c]; p < PL.cl_p0[c] + PL.cl_np[c]; ++p) if (pk_has[p]) total += (int)(PL.first[p + 1] - PL.first[p]);
-        const std::string &s = cl_cons[c];
-        consensi.push_back(hread{s, std::string(s.size(), 'K'), -1});
-        con_cid.push_back((int32_t)c);
-        con_n.push_back(total);
-    }
-    fill_set(R->uncorrected, uncorrected, unc_cid, {});
-    fill_set(R->consensi, consensi, con_cid, con_n);
-    R->corrected_pack = (uint32_t *)malloc(std::max<size_t>(1, cor_pack.size()) * 4);
-    if (!cor_pack.empty()) memcpy(R->corrected_pack, cor_pack.data(), cor_pack.size() * 4);
-    R->uncorrected_pack = (uint32_t *)malloc(std::max<size_t>(1, unc_pack.size()) * 4);
-    if (!unc_pack.empty()) memcpy(R->uncorrected_pack, unc_pack.data(), unc_pack.size() * 4);
-    {
+        fill_set(R->uncorrected, uncorrected, unc_cid, {});
+        fill_set(R->consensi, consensi, con_cid, con_n);
+        R->corrected_pack = result_array<uint32_t>(cor_pack.size());
+        if (!cor_pack.empty()) memcpy(R->corrected_pack, cor_pack.data(), cor_pack.size() * 4);
+        R->uncorrected_pack = result_array<uint32_t>(unc_pack.size());
+        if (!unc_pack.empty()) memcpy(R->uncorrected_pack, unc_pack.data(), unc_pack.size() * 4);
         rattle_skip_list &K = R->skipped;
         const size_t n = skips.size();
         K.n = (uint32_t)n;
-        K.cluster_id = (int32_t *)malloc(std::max<size_t>(1, n) * 4); K.pack = (uint32_t *)malloc(std::max<size_t>(1, n) * 4);
-        K.stage = (uint32_t *)malloc(std::max<size_t>(1, n) * 4); K.read_off = (uint64_t *)malloc((n + 1) * 8);
+        K.cluster_id = result_array<int32_t>(n); K.pack = result_array<uint32_t>(n); K.stage = result_array<uint32_t>(n);
+        K.read_off = (uint64_t *)malloc((n + 1) * 8);
         uint64_t tot = 0;
         for (size_t i = 0; i < n; ++i) { K.cluster_id[i] = skips[i].cid; K.pack[i] = skips[i].pack; K.stage[i] = skips[i].stage; K.read_off[i] = tot; tot += skips[i].rids.size(); }
         K.read_off[n] = tot;
-        K.read_id = (int32_t *)malloc(std::max<uint64_t>(1, tot) * 4);
+        K.read_id = result_array<int32_t>(tot);
         for (size_t i = 0; i < n; ++i) if (!skips[i].rids.empty()) memcpy(K.read_id + K.read_off[i], skips[i].rids.data(), skips[i].rids.size() * 4);
         counters[3] = n;
         counters[4] = tot;
+        memcpy(R->counters, counters, sizeof(counters));
     }
-    memcpy(R->counters, counters, sizeof(counters));
+};
+
+}  // namespace
+
+// a step of this rank's own work: not run after an earlier one failed
+#define LOCAL_TRY(call) do { if (J.local_rc == 0) RT_TRY(J.own_error(call)); } while (0)
+
+int correct_driver(rattle_ctx *ctx, const uint8_t *seq, const uint8_t *qual, const uint64_t *off, uint32_t n_reads,
+                   uint32_t n_clusters, const uint32_t *coff, const int32_t *mid, const uint8_t *mrev,
+                   const rattle_correct_params *P, rattle_correction **out) {
+    char order[8] = {0};
+    memcpy(order, P->vote_order[0] ? P->vote_order : "U-GTCA", 6);
+    for (int i = 0; i < 6; ++i)
+        if (!order[i] || !strchr("ACGTU-", order[i])) { set_error("vote_order must be a permutation of ACGTU-"); return RATTLE_ERR_ARG; }
+    rattle_correction *R = (rattle_correction *)calloc(1, sizeof(rattle_correction));
+    *out = R;
+    phase_timer T_all("correct: total");
+    correct_job J{ctx, seq, qual, off, n_reads, n_clusters, P, order, R, ctx->xchg.rank, ctx->xchg.nranks, ctx->stream};
+    RT_TRY(J.plan(coff, mid, mrev));
+    LOCAL_TRY(ensure_post_constants(ctx));
+    LOCAL_TRY(J.check_bases());
+    J.unqueued_reads();
+    if (J.nm) {
+        LOCAL_TRY(J.upload_reads());
+        LOCAL_TRY(J.stage1());
+        LOCAL_TRY(J.stage1_finish());                // starts the download of the corrected reads
+    }
+    J.d_rseq.release(); J.d_rqual.release();
+    std::vector<uint8_t> bytes, bytes_3b;
+    std::vector<uint32_t> s2a, s2b;                  // my live packs of the big clusters / of all others
+    for (uint32_t k = 0; k < J.nm; ++k) {
+        const uint32_t p = J.mine[k];
+        if (J.pk_dead[p]) put_rec(bytes, p, 1u << 1, nullptr, 0);      // given up in stage 1: announced with the first exchange
+        else (J.big[J.PL.pk_cid[p]] ? s2a : s2b).push_back(k);
+    }
+    // stage 2a: my packs of the big clusters
+    LOCAL_TRY(J.cons_pass("correct: stage 2a", 2, s2a, {}, bytes));
+    if (J.any_big) { RT_TRY(J.exchange_stage(bytes)); bytes.clear(); }
+    // stage 2b+3a: POA #3 groups of the big clusters, my packs of all other clusters
+    const std::vector<uint32_t> g3a = J.poa3_groups(true);
+    LOCAL_TRY(J.cons_pass("correct: stage 2b+3a", 3, s2b, g3a, bytes));
+    RT_TRY(J.exchange_stage(bytes));
+    RT_TRY(J.own_error(J.join_download()));
+    J.S1.release();                                  // the stage-1 rows are no longer needed once the download is done
+    // stage 3b: POA #3 of the other clusters with more than one live pack
+    size_t n3b = 0;
+    const std::vector<uint32_t> g3b = J.poa3_groups(false, &n3b);
+    LOCAL_TRY(J.cons_pass("correct: stage 3b", 4, {}, g3b, bytes_3b));
+    // several ranks: this exchange always takes place, so that every rank leaves with the same verdict (the caller's
+    // next collective is the gather of the corrected reads)
+    if (n3b || J.nranks > 1 || xchg_recording(ctx)) RT_TRY(J.exchange_stage(bytes_3b));
+    J.d_os.release(); J.d_oq.release();
+    J.assemble();
     return 0;
 }
+#undef LOCAL_TRY
 
 }  // namespace rattle

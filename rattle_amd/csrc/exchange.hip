@@ -317,15 +317,6 @@ piece_view take_set(const uint8_t *b, size_t &at) {
     return V;
 }
 
-void alloc_set(rattle_read_set &S, uint32_t n, uint64_t tot) {
-    S.n = n;
-    const size_t m = std::max<size_t>(1, n);
-    S.read_id = (int32_t *)malloc(m * 4); S.cluster_id = (int32_t *)malloc(m * 4); S.n_reads = (int32_t *)malloc(m * 4);
-    S.off = (uint64_t *)malloc(((size_t)n + 1) * 8);
-    S.seq = (char *)malloc(tot + 1); S.qual = (char *)malloc(tot + 1);
-    S.seq[tot] = 0; S.qual[tot] = 0;
-}
-
 // merge the pieces' records in key order (stable: equal keys keep piece order, then record order)
 void merge_sets(const std::vector<piece_view> &V, rattle_read_set &S, uint32_t **pack_out) {
     std::vector<rec_ref> refs;
@@ -352,7 +343,7 @@ void merge_sets(const std::vector<piece_view> &V, rattle_read_set &S, uint32_t *
             refs.swap(sorted);
         } else std::stable_sort(refs.begin(), refs.end(), [](const rec_ref &a, const rec_ref &b) { return a.key < b.key; });
     }
-    alloc_set(S, (uint32_t)refs.size(), tot);
+    alloc_read_set(S, (uint32_t)refs.size(), tot);
     uint32_t *pk = (uint32_t *)malloc(std::max<size_t>(1, refs.size()) * 4);
     uint64_t at = 0;
     for (size_t i = 0; i < refs.size(); ++i) {
@@ -377,6 +368,15 @@ void merge_sets(const std::vector<piece_view> &V, rattle_read_set &S, uint32_t *
 }
 
 }  // namespace
+
+void alloc_read_set(rattle_read_set &S, uint32_t n, uint64_t tot) {
+    S.n = n;
+    const size_t m = std::max<size_t>(1, n);
+    S.read_id = (int32_t *)malloc(m * 4); S.cluster_id = (int32_t *)malloc(m * 4); S.n_reads = (int32_t *)malloc(m * 4);
+    S.off = (uint64_t *)malloc(((size_t)n + 1) * 8);
+    S.seq = (char *)malloc(tot + 1); S.qual = (char *)malloc(tot + 1);
+    S.seq[tot] = 0; S.qual[tot] = 0;
+}
 
 int correction_gather(rattle_ctx *ctx, const rattle_correction *L, int root, rattle_correction **merged) {
     exchange &X = ctx->xchg;
@@ -452,7 +452,7 @@ int correction_gather(rattle_ctx *ctx, const rattle_correction *L, int root, rat
     // consensi are complete on every rank
     {
         const rattle_read_set &S = L->consensi;
-        alloc_set(R->consensi, S.n, S.off[S.n]);
+        alloc_read_set(R->consensi, S.n, S.off[S.n]);
         memcpy(R->consensi.read_id, S.read_id, (size_t)S.n * 4); memcpy(R->consensi.cluster_id, S.cluster_id, (size_t)S.n * 4);
         memcpy(R->consensi.n_reads, S.n_reads, (size_t)S.n * 4); memcpy(R->consensi.off, S.off, ((size_t)S.n + 1) * 8);
         memcpy(R->consensi.seq, S.seq, S.off[S.n]); memcpy(R->consensi.qual, S.qual, S.off[S.n]);

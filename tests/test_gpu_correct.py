@@ -47,6 +47,41 @@ def test_correct_big_cluster_stage_split_matches_oracle(gpu_ctx, oracle, monkeyp
         assert int(got[3][0]) == int(want[3][0])
 
 
+def test_correct_calls_on_one_context_carry_no_state(gpu_ctx, oracle, monkeypatch):
+    """Three `correct` calls in a row on one context: default thresholds (no big clusters: stage 2a is empty and its
+    exchange does not take place), the forced big-cluster split, defaults again.  Every call equals the oracle, and the
+    first and the third are equal down to the skip list and the counters: nothing of a call -- or of the 2a path -- may
+    survive into the next.  min_reads = 17 leaves whole clusters out of the queue (correct.cpp:360)."""
+    seqs, quals, _, _ = synth.reads(300, 4, 1, True, seed=4)
+    headers = [b"@r%d" % i for i in range(len(seqs))]
+    clusters, _ = cluster_command(gpu_ctx, seqs, list(range(len(seqs))))
+    split, min_reads = 25, 17
+
+    def queued_packs(n):                                 # correct.cpp:331-360: strided sub-packs, queued if > min_reads
+        nf = (n - 1) // split + 1
+        return sum(len(range(j, n, nf)) > min_reads for j in range(nf))
+
+    n_packs = [queued_packs(len(mem)) for _, mem in clusters]
+    assert 0 in n_packs and max(n_packs) >= 3 and any(0 < n < 3 for n in n_packs), n_packs
+    want = oracle.correct(headers, seqs, quals, hps.encode(clusters), split=split, min_reads=min_reads)
+
+    def run():
+        out = correct_command(gpu_ctx, headers, seqs, quals, clusters, split=split, min_reads=min_reads, with_skipped=True)
+        assert out[0] == want[0], "corrected.fq differs"
+        assert out[1] == want[1], "uncorrected.fq differs"
+        assert out[2] == want[2], "consensi.fq differs"
+        assert int(out[3][0]) == int(want[3][0])
+        return out[0], out[1], out[2], [int(x) for x in out[3][:5]], out[4]
+
+    first = run()
+    monkeypatch.setenv("RATTLE_BIG_CLUSTER_PACKS", "3")
+    monkeypatch.setenv("RATTLE_BIG_MIN_PACKS", "0")
+    run()
+    monkeypatch.delenv("RATTLE_BIG_CLUSTER_PACKS")
+    monkeypatch.delenv("RATTLE_BIG_MIN_PACKS")
+    assert run() == first
+
+
 def test_correct_toyset_subset_matches_reference_fixture(gpu_ctx, toyset, toyset_clusters):
     """40 toyset clusters (6..200 reads) against toyset/rna/output/consensi.fq, with the old
     fixture build's vote order (see tests/test_oracle_correct.py)."""
