@@ -376,6 +376,26 @@ int launch_pair_count(rattle_ctx *ctx, uint32_t n_pairs);
 // pair_index.hip : the count pass over an inverted k-mer index of the evaluation's seeds (survivors grouped by candidate)
 int group_survivors_by_cand(rattle_ctx *ctx, uint32_t n, uint64_t n_cands);
 int launch_pair_count_index(rattle_ctx *ctx, uint32_t n_pairs, const uint32_t *h_seed, uint32_t ns, uint32_t nc, bool many);
+// poa.hip : the words of kernel C's counter block (poa_args::counters, POA_CNT_WORDS on the device); poa_device_run hands the first
+// POA_CNT_PUBLIC of them back in h_cnt.  The only place that says which slot is what.  The measurement builds reuse slots by number:
+// POA_PREDSTAT 4 .. 6, POA_PROFILE 2 and 4 .. 7, POA_BARPROF 8 .. 15 (and POA_CNT_BARPROF ..), POA_HIST 16 + d and 80 + d.
+enum poa_counter {
+    POA_CNT_CELLS = 0,         // DP cells of the reference's work (counted once, by the pass that finishes the pack)
+    POA_CNT_SEQS = 1,          // sequences aligned
+    POA_CNT_NODES = 2,         // graph nodes of the finished packs
+    POA_CNT_ROWS = 3,          // DP rows
+    POA_CNT_SYNC = 8,          // 8 .. 10: the wait a wavefront of the team kernels gave up (POA_ERR_SYNC): who and where; saw | wants; rows | columns
+    POA_CNT_STRIPS = 10,       // alignments over the full rows as strips (PK 8).  Collides with the third word of POA_CNT_SYNC: a strip count
+                               // and a sync diagnosis of the same call overwrite / add to each other (known; moving it changes behaviour)
+    POA_CNT_CELLS_DONE = 11,   // DP cells the device computed (every pass)
+    POA_CNT_BAND_OK = 12,      // alignments with a certified band
+    POA_CNT_BAND_FAIL = 13,    // ... with a failed certificate
+    POA_CNT_BAND_DIAG = 14,    // 14, 15: the last alignment that lost its band: rows | length; sequence of its pack | best score in the band
+    POA_CNT_PUBLIC = 16,       // words of h_cnt
+    POA_CNT_BARPROF = 16,      // POA_BARPROF: wave 1's segments
+    POA_CNT_PROFILE = 32,      // + 8 x class: POA_PROFILE's phase ticks (poa_args::prof)
+    POA_CNT_WORDS = 160
+};
 // poa.hip : device-resident POA over packs (sequences, offsets, column output in HBM)
 int poa_device_run(rattle_ctx *ctx, const uint8_t *d_seq, const uint64_t *d_off, const uint64_t *h_off, uint32_t n_seqs,
                    const uint32_t *h_pack_first, uint32_t n_packs, uint32_t *d_col, uint32_t *d_width, uint32_t *h_width,

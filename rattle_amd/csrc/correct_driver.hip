@@ -241,7 +241,7 @@ int run_stage(rattle_ctx *ctx, stage &S, const std::vector<gather_desc> &desc, c
     RT_HIP(hipMemcpyAsync(S.d_first.p, S.first.data(), (size_t)(np + 1) * 4, hipMemcpyHostToDevice, st));
     for (const gather_part &g : parts)
         RT_TRY(launch_gather(ctx, d_desc.p + g.begin, g.count, g.src_seq, mode == 1 ? g.src_qual : nullptr, S.seq.p, mode == 1 ? S.qual.p : nullptr));
-    unsigned long long h_cnt[16];
+    unsigned long long h_cnt[POA_CNT_PUBLIC];
     {
         phase_timer T("  stage: POA");
         // POA #2 / #3 align corrected reads / pack consensi: their graphs are almost chains -- rows that depend on each other
@@ -251,9 +251,9 @@ int run_stage(rattle_ctx *ctx, stage &S, const std::vector<gather_desc> &desc, c
         RT_TRY(poa_device_run(ctx, S.seq.p, S.d_off.p, S.off.data(), n, S.first.data(), np, S.col.p, S.d_width.p, S.width.data(), h_cnt, &S.skipped));
     }
     d_desc.release();
-    counters[0] += h_cnt[0];
-    counters[1] += h_cnt[1];
-    counters[5] += h_cnt[11]; counters[6] += h_cnt[12]; counters[7] += h_cnt[13];      // DP cells computed; alignments with a certified band / a failed certificate
+    counters[0] += h_cnt[POA_CNT_CELLS];
+    counters[1] += h_cnt[POA_CNT_SEQS];
+    counters[5] += h_cnt[POA_CNT_CELLS_DONE]; counters[6] += h_cnt[POA_CNT_BAND_OK]; counters[7] += h_cnt[POA_CNT_BAND_FAIL];      // DP cells computed; alignments with a certified band / a failed certificate
     // layout of the row matrices and per-column arrays
     S.moff.assign(np, 0); S.coff.assign(np, 0);
     uint64_t cells = 0, cols = 0;

@@ -1151,9 +1151,9 @@ __device__ void dp_rows_mt(poa_ws &S, dp_xchg &X, const poa_args &A, uint32_t n,
     // which = 1: predecessor rows, 2: left mailbox, 3: right neighbour's back-pressure
     auto give_up = [&](const uint32_t which, const uint32_t row, const uint32_t seen, const uint32_t want) __attribute__((always_inline)) {
         if (lane == 0 && atomicExch((uint32_t *)&Y.abort, 1u) == 0u) {
-            A.counters[8] = which | ((unsigned long long)t << 8) | ((unsigned long long)w << 16) | ((unsigned long long)row << 32);
-            A.counters[9] = seen | ((unsigned long long)want << 32);
-            A.counters[10] = n | ((unsigned long long)Lp << 32);
+            A.counters[POA_CNT_SYNC] = which | ((unsigned long long)t << 8) | ((unsigned long long)w << 16) | ((unsigned long long)row << 32);
+            A.counters[POA_CNT_SYNC + 1] = seen | ((unsigned long long)want << 32);
+            A.counters[POA_CNT_SYNC + 2] = n | ((unsigned long long)Lp << 32);
         }
         dead = 1u;
     };
@@ -1313,7 +1313,7 @@ __device__ void dp_rows_mt(poa_ws &S, dp_xchg &X, const poa_args &A, uint32_t n,
                 for (int u = 0; u < NP; ++u) { HM[u] = pk_splat(0); FM[u] = pk_splat(POA_G - POA_E); }
             }
             // (lane 0 of a column block w > 0 reads the word LEFT of the block, hq[-1], from block w - 1's record: that store is ordered before
-            // this load only through the mailbox waits of earlier rows, which holds when ring_reach + 1 >= teams + ring_slack -- plan_class
+            // this load only through the mailbox waits of earlier rows, which holds when ring_reach + 1 >= teams + ring_slack -- poa_run::lds_plan
             // sizes the ring so, or takes the barrier form)
             auto far_fetch = [&](uint32_t prow) __attribute__((always_inline)) {
                 uint32_t x[NP];
@@ -2588,7 +2588,7 @@ __global__ __launch_bounds__(64 * NW * pk_teams(RING, PK), poa_min_waves(CPL, NW
                     }
                 }
 #ifdef POA_PREDSTAT
-                atomicAdd(&A.counters[4], ps_in); atomicAdd(&A.counters[5], ps_far); atomicAdd(&A.counters[6], ps_prev);
+                atomicAdd(&A.counters[4], ps_in); atomicAdd(&A.counters[5], ps_far); atomicAdd(&A.counters[6], ps_prev);      // (POA_PREDSTAT reuses the spare public slots 4 .. 6, see poa_counter)
 #endif
                 if (PK != 2) for (uint32_t t = tid; t < Lp; t += NT) S.sq[t] = t < L ? s[t] : 0;       // long rows read the sequence in place
                 __syncthreads();
@@ -2791,7 +2791,7 @@ __global__ __launch_bounds__(64 * NW * pk_teams(RING, PK), poa_min_waves(CPL, NW
                 if constexpr (PK == 8) {
                     if (!band_on) {
                         // (diagnosis for RATTLE_TIMING: which alignment lost the band, and by how much)
-                        if (tid == 0) { A.counters[14] = (unsigned long long)n | ((unsigned long long)L << 32); A.counters[15] = (unsigned long long)(q - q0) | ((unsigned long long)X.best[0] << 32); }
+                        if (tid == 0) { A.counters[POA_CNT_BAND_DIAG] = (unsigned long long)n | ((unsigned long long)L << 32); A.counters[POA_CNT_BAND_DIAG + 1] = (unsigned long long)(q - q0) | ((unsigned long long)X.best[0] << 32); }
                         S.err = POA_ERR_BAND; break;
                     }
                 }
@@ -3449,18 +3449,18 @@ __global__ __launch_bounds__(64 * NW * pk_teams(RING, PK), poa_min_waves(CPL, NW
             // the reference's work is counted once, by the pass that finishes the pack (a pack that outgrows its slot or loses its band is run
             // again from the start); what the device computed is counted every time
             if (!S.err) {
-                atomicAdd(&A.counters[0], cells);
-                atomicAdd(&A.counters[1], (unsigned long long)(q1 - q0));
+                atomicAdd(&A.counters[POA_CNT_CELLS], cells);
+                atomicAdd(&A.counters[POA_CNT_SEQS], (unsigned long long)(q1 - q0));
 #ifndef POA_PROFILE
-                atomicAdd(&A.counters[2], (unsigned long long)S.n_nodes);
+                atomicAdd(&A.counters[POA_CNT_NODES], (unsigned long long)S.n_nodes);
 #endif
-                atomicAdd(&A.counters[3], rows);
+                atomicAdd(&A.counters[POA_CNT_ROWS], rows);
             }
 #ifdef POA_PROFILE
             atomicAdd(&A.counters[2], t_tie);          // tie resolution (part of counters[6])
 #endif
-            atomicAdd(&A.counters[11], cells_done);
-            if constexpr (PK == 8) { atomicAdd(&A.counters[12], (unsigned long long)n_band_ok); atomicAdd(&A.counters[13], (unsigned long long)n_band_fail); atomicAdd(&A.counters[10], (unsigned long long)n_strip_aln); }
+            atomicAdd(&A.counters[POA_CNT_CELLS_DONE], cells_done);
+            if constexpr (PK == 8) { atomicAdd(&A.counters[POA_CNT_BAND_OK], (unsigned long long)n_band_ok); atomicAdd(&A.counters[POA_CNT_BAND_FAIL], (unsigned long long)n_band_fail); atomicAdd(&A.counters[POA_CNT_STRIPS], (unsigned long long)n_strip_aln); }
 #ifdef POA_PROFILE
             (void)t_topo; (void)t_dp; (void)t_tb; (void)t_add;                              // counters[4]: ties << 32 | ties that needed the exact sort
             atomicAdd(&A.counters[5], t_dp);           // DP rows
@@ -3506,7 +3506,7 @@ struct poa_variant {
 #define POA_VARIANT(CPL, RING, NW, PK) {CPL, RING, NW, PK, &launch_poa<CPL, RING, NW, PK>, &max_blocks_per_cu<CPL, RING, NW, PK>}
 #define POA_CLASSES 8
 #define POA_GROUPS 24                          // + the shallow packs of classes 4 .. 7 (8 .. 11), the LONG-CHAIN packs of classes 0 .. 3 (12 .. 15) and the packs of
-                                               // classes 0 .. 3 the exact band is tried on (16 .. 19; long chains: 20 .. 23) as groups of their own (poa_device_run)
+                                               // classes 0 .. 3 the exact band is tried on (16 .. 19; long chains: 20 .. 23) as groups of their own (poa_run::classify)
 #ifndef POA_BAND_SPREAD
 #define POA_BAND_SPREAD 400                    // the band holds columns - length + 2 t + 1 <= 504 cells per row: a pack whose lengths differ by more than this cannot stay in it
 #endif
@@ -3522,7 +3522,7 @@ static const poa_variant k_latency[POA_CLASSES] = {POA_VARIANT(4, POA_RING_4x4, 
                                                    POA_VARIANT(8, POA_LONG_RING, 16, 2) /* longer than 8192: int32 cells, 8192-column segments one after the other */};
 static const poa_variant k_long_noring = POA_VARIANT(8, 0, 16, 2);      // ... row-major segments without a ring when the graph's bitmaps leave no LDS for it
 static const poa_variant k_noring[3] = {POA_VARIANT(16, 0, 4, 0), POA_VARIANT(24, 0, 4, 0), POA_VARIANT(32, 0, 4, 0)};      // when the ring no longer fits LDS (huge graphs)
-// the packed classes (up to 2560 columns), by load: see choose_variants in poa_device_run
+// the packed classes (up to 2560 columns), by load: see poa_run::choose_variants
 static const poa_variant k_dense[4] = {POA_VARIANT(4, POA_RING_4x4, 4, 1), POA_VARIANT(6, POA_RING_4x6, 4, 1), POA_VARIANT(8, 8, 4, 1), POA_VARIANT(10, 8, 4, 1)};
 // teams of wavefronts (dp_rows_mt; the second argument is the number of TEAMS, the ring is sized at launch): four teams for a pack
 // that has a CU to itself, two when up to four or five packs share one; one team = the lean skewed pipeline (tests, measurements)
@@ -3537,30 +3537,20 @@ static const poa_variant k_band1 = POA_VARIANT(4, 8, 1, 8), k_band4 = POA_VARIAN
 // Every switch kernel C's host side takes from the environment (tests and measurements only; read once per call, so a test may change
 // them between calls): one place, one struct.
 struct poa_env {
-    const char *timeline = nullptr;      // RATTLE_POA_TIMELINE=<file>: when each pack's workgroup started and finished it
-    const char *mode = nullptr;          // RATTLE_POA_MODE = dense | mt4 | mt2 | mt1 | band: one form of the row loop for the packed classes
-    int band = -1;                       // RATTLE_POA_BAND = 0 | 1: the exact band for near-chain graphs off / on for every call (default: on where the caller announces such graphs)
-    const char *profile_json = nullptr;  // RATTLE_POA_PROFILE_JSON=<file> (POA_PROFILE builds): phase shares per class
-    uint32_t node_cap = 0;               // RATTLE_POA_NODE_CAP: first-pass node capacity (tests lower it to force re-runs)
-    uint64_t budget_mb = 0;              // RATTLE_POA_BUDGET_MB: arena budget (tests shrink it to exercise the skip path)
-    uint32_t debug = 0;                  // RATTLE_POA_DEBUG: bit 0 full sort for ties, bit 1 traceback without the LDS chain, bit 2 ... without jump tables
-    uint32_t mt_slots = 0;               // RATTLE_POA_MT_SLOTS: ring slots of the team kernels (tests: a short ring, many predecessors from HBM)
-    int streams = 0;                     // RATTLE_POA_STREAMS: streams the classes of a pass are dealt onto
-    bool timing = false;                 // RATTLE_TIMING: one line per class and pass
-    int head_start_us = 30;              // RATTLE_POA_HEAD_START_US: see poa_head_start (0: none)
-    bool noring = false;                 // RATTLE_POA_NORING=1: classes 4 .. 7 take their forms without a ring, as if the bitmaps left no LDS for one (tests)
-    poa_env() {
-        timeline = getenv("RATTLE_POA_TIMELINE"); mode = getenv("RATTLE_POA_MODE"); profile_json = getenv("RATTLE_POA_PROFILE_JSON");
-        if (const char *v = getenv("RATTLE_POA_NODE_CAP")) node_cap = (uint32_t)std::max(64, atoi(v));
-        if (const char *v = getenv("RATTLE_POA_BUDGET_MB")) budget_mb = (uint64_t)atoll(v);
-        if (const char *v = getenv("RATTLE_POA_DEBUG")) debug = (uint32_t)atoi(v);
-        if (const char *v = getenv("RATTLE_POA_BAND")) band = atoi(v) != 0;
-        if (const char *v = getenv("RATTLE_POA_MT_SLOTS")) mt_slots = (uint32_t)std::max(1, atoi(v));
-        if (const char *v = getenv("RATTLE_POA_STREAMS")) streams = atoi(v);
-        timing = getenv("RATTLE_TIMING") != nullptr;
-        if (const char *v = getenv("RATTLE_POA_HEAD_START_US")) head_start_us = std::max(0, std::min(1000, atoi(v)));
-        if (const char *v = getenv("RATTLE_POA_NORING")) noring = atoi(v) != 0;
-    }
+    static int num(const char *name, int dflt) { const char *v = getenv(name); return v ? atoi(v) : dflt; }
+    const char *timeline = getenv("RATTLE_POA_TIMELINE");      // <file>: when each pack's workgroup started and finished it
+    const char *mode = getenv("RATTLE_POA_MODE");               // dense | mt4 | mt2 | mt1 | band: one form of the row loop for the packed classes
+    int band = getenv("RATTLE_POA_BAND") ? num("RATTLE_POA_BAND", 0) != 0 : -1;      // 0 | 1: the exact band for near-chain graphs off / on for every call (default: on where the caller announces such graphs)
+    const char *profile_json = getenv("RATTLE_POA_PROFILE_JSON");      // <file> (POA_PROFILE builds): phase shares per class
+    uint32_t node_cap = getenv("RATTLE_POA_NODE_CAP") ? (uint32_t)std::max(64, num("RATTLE_POA_NODE_CAP", 0)) : 0;      // first-pass node capacity (tests lower it to force re-runs)
+    uint64_t budget_mb = getenv("RATTLE_POA_BUDGET_MB") ? (uint64_t)atoll(getenv("RATTLE_POA_BUDGET_MB")) : 0;      // arena budget (tests shrink it to exercise the skip path)
+    uint32_t debug = (uint32_t)num("RATTLE_POA_DEBUG", 0);      // bit 0 full sort for ties, bit 1 traceback without the LDS chain, bit 2 ... without jump tables
+    uint32_t mt_slots = getenv("RATTLE_POA_MT_SLOTS") ? (uint32_t)std::max(1, num("RATTLE_POA_MT_SLOTS", 0)) : 0;      // ring slots of the team kernels (tests: a short ring, many predecessors from HBM)
+    int streams = num("RATTLE_POA_STREAMS", 0);                 // streams the classes of a pass are dealt onto
+    bool timing = getenv("RATTLE_TIMING") != nullptr;           // one line per class and pass
+    int head_start_us = std::max(0, std::min(1000, num("RATTLE_POA_HEAD_START_US", 30)));      // see poa_head_start (0: none)
+    bool noring = num("RATTLE_POA_NORING", 0) != 0;             // =1: classes 4 .. 7 take their forms without a ring, as if the bitmaps left no LDS for one (tests)
+    int64_t band_lds = getenv("RATTLE_POA_BAND_LDS") ? (int64_t)(uint32_t)num("RATTLE_POA_BAND_LDS", 0) : -1;      // the band's LDS bytes (measurements)
 };
 
 // A pass launches its groups on several streams at once, and the device places their workgroups in whatever order the queues reach it.
@@ -3576,122 +3566,123 @@ __global__ void poa_head_start(uint32_t ticks) {
     while (wall_clock64() - t0 < ticks) __builtin_amdgcn_s_sleep(16);
 }
 
-// Device-resident core: sequences, offsets and the per-base column output live in HBM; the host only
-// plans (lengths / pack boundaries) and reads back pack widths, statuses and counters.
-// skipped != nullptr: packs that do not fit the device are flagged there (1) instead of failing the call;
-// their width is 0 and their columns are undefined.
-int poa_device_run(rattle_ctx *ctx, const uint8_t *d_seq_in, const uint64_t *d_off_in, const uint64_t *off, uint32_t n_seqs,
-                   const uint32_t *pack_first, uint32_t n_packs, uint32_t *d_col_out, uint32_t *d_width_out, uint32_t *h_width_out,
-                   unsigned long long *h_cnt, std::vector<uint8_t> *skipped) {
-    hipStream_t st = ctx->stream;
-    const poa_env ENV;
-    for (int i = 0; i < 16; ++i) h_cnt[i] = 0;
-    if (skipped) skipped->assign(n_packs, 0);
-    if (n_packs == 0 || n_seqs == 0) { for (uint32_t p = 0; p < n_packs; ++p) h_width_out[p] = 0; return 0; }
-    if (pack_first[0] != 0 || pack_first[n_packs] != n_seqs) { set_error("pack_first must cover [0, n_seqs]"); return RATTLE_ERR_ARG; }
+// length class of a read: 1024 / 1536 / 2048 / 2560 / 4096 / 6144 / 8192 columns, or longer (segmented int32 rows)
+static inline int poa_length_class(uint32_t len) { int cls = 0; while (cls < POA_CLASSES - 1 && len > k_class_cols[cls]) ++cls; return cls; }
+// the LDS every form has in front of its ring or band: the sequence, the two node bitmaps and the stack
+static inline uint32_t poa_lds_front(uint32_t lds_seq, uint32_t ncap) { return lds_seq + (2u * poa_bit_words(ncap) + POA_STACK) * 4u; }
+// one group's plan: what is left of it, its capacities, and the instance, slot and LDS of the pass about to start
+struct cls_plan {
+    std::vector<uint32_t> todo;
+    uint32_t node_cap = 10240u;                // first-round capacity (RATTLE_POA_NODE_CAP: tests lower it to force re-runs)
+    uint64_t cell_cap = 24ull << 20;           // elements per matrix
+    poa_args A;
+    uint64_t per_slot = 0;
+    size_t shm = 0;
+    uint32_t n_slots = 0;
+    int bpc = 1;
+    int rounds = 0;                            // passes this class has taken
+    bool clamped = false;                      // cell_cap was cut to what one slot can get: packs that still fail are skipped
+    bool no_teams = false;                     // a pack of this group failed with POA_ERR_SYNC: its retries take the barrier form
+    bool no_band = false;                      // packs of this group failed with POA_ERR_BAND: what is left of the group takes the full rows
+    const poa_variant *V = nullptr;
+};
 
-    const char *mode_s = ENV.mode;
-    const int force_mode = !mode_s ? 0 : mode_s[0] == 'd' ? 1 : !strcmp(mode_s, "mt4") ? 3 : !strcmp(mode_s, "mt2") ? 4 : !strcmp(mode_s, "mt1") ? 5 : !strcmp(mode_s, "band") ? 6 : 0;
+// One call of poa_device_run: its inputs, the plan of every group and the device buffers (freed on every way out).  poa_device_run
+// calls the steps in the order they stand here.
+struct poa_run {
+    rattle_ctx *ctx;
+    hipStream_t st;
+    const uint8_t *d_seq; const uint64_t *d_off, *off; uint32_t n_seqs;      // poa_device_run's arguments
+    const uint32_t *pack_first; uint32_t n_packs;
+    uint32_t *d_col, *d_width, *h_width_out; unsigned long long *h_cnt; std::vector<uint8_t> *skipped;
+    const poa_env ENV;
+    const int force_mode = !ENV.mode ? 0 : ENV.mode[0] == 'd' ? 1 : !strcmp(ENV.mode, "mt4") ? 3 : !strcmp(ENV.mode, "mt2") ? 4 : !strcmp(ENV.mode, "mt1") ? 5 : !strcmp(ENV.mode, "band") ? 6 : 0;
     // the exact band: where the caller announces near-chain graphs (POA #2 / #3), unless a form is forced; RATTLE_POA_BAND overrides both ways
     const bool use_band = force_mode == 6 || (ENV.band >= 0 ? ENV.band == 1 && (force_mode == 0 || force_mode == 1) : force_mode == 0 && ctx->poa_shallow_graphs);
-    // length class of each pack: 1024 / 1536 / 2048 / 2560 / 4096 / 6144 columns, or longer (segmented int32 rows)
-    std::vector<uint64_t> pbases(n_packs);
-    std::vector<uint32_t> pmaxL(n_packs);
-    std::vector<uint32_t> by_class[POA_GROUPS];      // groups 0 .. 7: the column classes; 8 .. 11: the SHALLOW packs of classes 4 .. 7 (smaller slots, more of them)
-    for (uint32_t p = 0; p < n_packs; ++p) {
-        uint32_t m = 0, mn = 0xFFFFFFFFu;
-        for (uint32_t q = pack_first[p]; q < pack_first[p + 1]; ++q) {
-            const uint32_t len = (uint32_t)(off[q + 1] - off[q]);
-            m = std::max<uint32_t>(m, len);
-            if (len) mn = std::min(mn, len);
+    std::vector<uint64_t> pbases; std::vector<uint32_t> pmaxL;      // bases of each pack, and its longest read
+    cls_plan C[POA_GROUPS];                        // groups 0 .. 7: the column classes; 8 .. 11: the SHALLOW packs of classes 4 .. 7 (smaller slots, more of them); ...
+    size_t group_packs[POA_GROUPS] = {0};          // packs of each group at the start
+    uint32_t n_cu = 1;
+    uint64_t budget = 0;                           // bytes the arena may take
+    uint64_t want_bytes = 0;                       // ... and takes in the pass about to start
+    uint32_t live_per_cu = 1, chain_per_cu = 1;    // packs per CU the pass about to start will keep resident (all classes; the long-chain groups)
+    dbuf<uint32_t> d_pf, d_queue, d_status, d_heads;
+    dbuf<unsigned long long> d_cnt, d_tl;
+    std::vector<uint32_t> h_status;
+    unsigned long long h_hist[POA_CNT_WORDS] = {0}, h_prof[POA_CLASSES * 8] = {0}, h_seg[4] = {0};      // what the POA_HIST / POA_PROFILE / POA_BARPROF builds read back
+    // work of a pack as the share of the budget and the dealing onto streams estimate it: bases x longest read / threads of its workgroup
+    double pack_work(uint32_t p, const poa_variant *V) const { return (double)pbases[p] * (double)pmaxL[p] / (64.0 * V->nw); }
+    // the group of every pack
+    int classify() {
+        pbases.resize(n_packs);
+        pmaxL.resize(n_packs);
+        for (uint32_t p = 0; p < n_packs; ++p) {
+            uint32_t m = 0, mn = 0xFFFFFFFFu;
+            for (uint32_t q = pack_first[p]; q < pack_first[p + 1]; ++q) {
+                const uint32_t len = (uint32_t)(off[q + 1] - off[q]);
+                m = std::max<uint32_t>(m, len);
+                if (len) mn = std::min(mn, len);
+            }
+            pbases[p] = off[pack_first[p + 1]] - off[pack_first[p]];
+            pmaxL[p] = m;
+            if (m > POA_MAX_LEN) {
+                if (skipped) { (*skipped)[p] = 1; continue; }
+                set_error("sequence longer than " + std::to_string(POA_MAX_LEN) + " nt in a POA pack");
+                return RATTLE_ERR_ARG;
+            }
+            int cls = poa_length_class(m);
+            // a long-read pack's slot is its DP record: hundreds of MB to GBs, sized by the rows its graph will reach -- which depends
+            // on its depth (~1.15 + 0.02 x reads nodes per base, measured at 10 % error).  The shallow packs of a long class get a
+            // group of their own, so that the deep ones do not dictate everybody's slot (config 5: 47 slots of 1.15 GB for 747 packs)
+            if (cls >= 4 && pack_first[p + 1] - pack_first[p] <= POA_SHALLOW_READS) cls += 4;
+            // a POA #3 group of a many-pack cluster (hundreds of pack consensi, correct.cpp:520-532) is ONE workgroup's serial work for the
+            // whole pass (0.8 s at 1e6 reads in round 4, beside thousands of POA #2 packs in the dense form): such packs form groups of their
+            // own, whose form is chosen by THEIR number -- teams of wavefronts, the shortest row there is -- not by the crowd's
+            const bool band_pack = use_band && cls < 4 && m - std::min(m, mn) <= POA_BAND_SPREAD;      // (lengths only: what the graphs look like the kernel finds out)
+            if (cls < 4 && pack_first[p + 1] - pack_first[p] > POA_CHAIN_SEQS) cls += 12;
+            if (band_pack) cls += cls >= 12 ? 8 : 16;
+            C[cls].todo.push_back(p);
         }
-        pbases[p] = off[pack_first[p + 1]] - off[pack_first[p]];
-        pmaxL[p] = m;
-        if (m > POA_MAX_LEN) {
-            if (skipped) { (*skipped)[p] = 1; continue; }
-            set_error("sequence longer than " + std::to_string(POA_MAX_LEN) + " nt in a POA pack");
-            return RATTLE_ERR_ARG;
-        }
-        int cls = 0;
-        while (cls < POA_CLASSES - 1 && m > k_class_cols[cls]) ++cls;
-        // a long-read pack's slot is its DP record: hundreds of MB to GBs, sized by the rows its graph will reach -- which depends
-        // on its depth (~1.15 + 0.02 x reads nodes per base, measured at 10 % error).  The shallow packs of a long class get a
-        // group of their own, so that the deep ones do not dictate everybody's slot (config 5: 47 slots of 1.15 GB for 747 packs)
-        if (cls >= 4 && pack_first[p + 1] - pack_first[p] <= POA_SHALLOW_READS) cls += 4;
-        // a POA #3 group of a many-pack cluster (hundreds of pack consensi, correct.cpp:520-532) is ONE workgroup's serial work for the
-        // whole pass (0.8 s at 1e6 reads in round 4, beside thousands of POA #2 packs in the dense form): such packs form groups of their
-        // own, whose form is chosen by THEIR number -- teams of wavefronts, the shortest row there is -- not by the crowd's
-        const bool band_pack = use_band && cls < 4 && m - std::min(m, mn) <= POA_BAND_SPREAD;      // (lengths only: what the graphs look like the kernel finds out)
-        if (cls < 4 && pack_first[p + 1] - pack_first[p] > POA_CHAIN_SEQS) cls += 12;
-        if (band_pack) cls += cls >= 12 ? 8 : 16;
-        by_class[cls].push_back(p);
+        for (int c = 0; c < POA_GROUPS; ++c) { group_packs[c] = C[c].todo.size(); if (ENV.node_cap) C[c].node_cap = ENV.node_cap; }
+        return 0;
     }
-
-    dbuf<uint32_t> d_pf, d_queue, d_status;
-    dbuf<unsigned long long> d_cnt;
-    RT_TRY(d_pf.reserve(n_packs + 1)); RT_TRY(d_queue.reserve(n_packs)); RT_TRY(d_status.reserve(n_packs)); RT_TRY(d_cnt.reserve(160));
-    struct view { const uint8_t *p; } d_seq{d_seq_in};
-    struct viewo { const uint64_t *p; } d_off{d_off_in};
-    struct viewc { uint32_t *p; } d_col{d_col_out}, d_width{d_width_out};
-    RT_HIP(hipMemcpyAsync(d_pf.p, pack_first, (n_packs + 1) * 4, hipMemcpyHostToDevice, st));
-    RT_HIP(hipMemsetAsync(d_cnt.p, 0, 160 * 8, st));
-    RT_HIP(hipMemsetAsync(d_status.p, 0xFF, n_packs * 4, st));
-    RT_HIP(hipMemsetAsync(d_width.p, 0, n_packs * 4, st));         // skipped packs keep width 0 (kernel D then leaves them alone)
-    std::vector<uint32_t> h_status(n_packs);
-#ifdef POA_HIST
-    unsigned long long h_hist[160] = {0};
-#endif
-#ifdef POA_PROFILE
-    unsigned long long h_prof[POA_CLASSES * 8] = {0};
-#endif
-#ifdef POA_BARPROF
-    unsigned long long h_seg[4] = {0};
-#endif
-
-    size_t free_b = 0, total_b = 0;
-    RT_HIP(hipMemGetInfo(&free_b, &total_b));
-    free_b += ctx->poa_arena_bytes;            // the cached arena is ours to reuse
-    hipDeviceProp_t prop;
-    RT_HIP(hipGetDeviceProperties(&prop, ctx->device));
-    const uint32_t n_cu = (uint32_t)std::max(1, prop.multiProcessorCount);
-    int rc = 0;
-    if (!ctx->poa_go) {
-        RT_HIP(hipEventCreateWithFlags(&ctx->poa_go, hipEventDisableTiming));
-        for (int i = 0; i < 16; ++i) {
-            RT_HIP(hipStreamCreateWithFlags(&ctx->poa_st[i], hipStreamNonBlocking));
-            RT_HIP(hipEventCreateWithFlags(&ctx->poa_ev[i], hipEventDisableTiming));
+    // the call's device buffers, the arena budget, and (once per context) the streams and events of the passes
+    int setup() {
+        RT_TRY(d_pf.reserve(n_packs + 1)); RT_TRY(d_queue.reserve(n_packs)); RT_TRY(d_status.reserve(n_packs)); RT_TRY(d_cnt.reserve(POA_CNT_WORDS));
+        RT_HIP(hipMemcpyAsync(d_pf.p, pack_first, (n_packs + 1) * 4, hipMemcpyHostToDevice, st));
+        RT_HIP(hipMemsetAsync(d_cnt.p, 0, POA_CNT_WORDS * 8, st));
+        RT_HIP(hipMemsetAsync(d_status.p, 0xFF, n_packs * 4, st));
+        RT_HIP(hipMemsetAsync(d_width, 0, n_packs * 4, st));           // skipped packs keep width 0 (kernel D then leaves them alone)
+        h_status.resize(n_packs);
+        size_t free_b = 0, total_b = 0;
+        RT_HIP(hipMemGetInfo(&free_b, &total_b));
+        free_b += ctx->poa_arena_bytes;            // the cached arena is ours to reuse
+        hipDeviceProp_t prop;
+        RT_HIP(hipGetDeviceProperties(&prop, ctx->device));
+        n_cu = (uint32_t)std::max(1, prop.multiProcessorCount);
+        if (!ctx->poa_go) {
+            RT_HIP(hipEventCreateWithFlags(&ctx->poa_go, hipEventDisableTiming));
+            for (int i = 0; i < 16; ++i) {
+                RT_HIP(hipStreamCreateWithFlags(&ctx->poa_st[i], hipStreamNonBlocking));
+                RT_HIP(hipEventCreateWithFlags(&ctx->poa_ev[i], hipEventDisableTiming));
+            }
         }
+        RT_TRY(d_heads.reserve(32));
+        // RATTLE_POA_TIMELINE=<file>: when each pack's workgroup started and finished it (measurement aid: how full the device is over a pass)
+        if (ENV.timeline) { RT_TRY(d_tl.reserve(2 * (size_t)n_packs)); RT_HIP(hipMemsetAsync(d_tl.p, 0, 16 * (size_t)n_packs, st)); }
+        // pass 0: many slots with a modest arena; later passes: failed packs with larger arenas.
+        // The column classes of one pass run concurrently on their own streams.
+        // (RATTLE_POA_BUDGET_MB: tests shrink the arena to exercise the skip path)
+        budget = ENV.budget_mb ? ENV.budget_mb << 20 : (uint64_t)(free_b * 0.85);
+        return 0;
     }
-    dbuf<uint32_t> d_heads;
-    RT_TRY(d_heads.reserve(32));
-    // RATTLE_POA_TIMELINE=<file>: when each pack's workgroup started and finished it (measurement aid: how full the device is over a pass)
-    const char *tl_path = ENV.timeline;
-    dbuf<unsigned long long> d_tl;
-    if (tl_path) { RT_TRY(d_tl.reserve(2 * (size_t)n_packs)); RT_HIP(hipMemsetAsync(d_tl.p, 0, 16 * (size_t)n_packs, st)); }
-    struct cls_plan {
-        std::vector<uint32_t> todo;
-        uint32_t node_cap = 10240u;                // first-round capacity (RATTLE_POA_NODE_CAP: tests lower it to force re-runs)
-        uint64_t cell_cap = 24ull << 20;           // elements per matrix
-        poa_args A;
-        uint64_t per_slot = 0;
-        size_t shm = 0;
-        uint32_t n_slots = 0;
-        int bpc = 1;
-        int rounds = 0;                            // passes this class has taken
-        bool clamped = false;                      // cell_cap was cut to what one slot can get: packs that still fail are skipped
-        bool no_teams = false;                     // a pack of this group failed with POA_ERR_SYNC: its retries take the barrier form
-        bool no_band = false;                      // packs of this group failed with POA_ERR_BAND: what is left of the group takes the full rows
-        const poa_variant *V = nullptr;
-    } C[POA_GROUPS];
-    for (int c = 0; c < POA_GROUPS; ++c) { C[c].todo = by_class[c]; if (ENV.node_cap) C[c].node_cap = ENV.node_cap; }
     // The kernel of a class is chosen per PASS from how full the device will be (round 3's verdict: one wavefront / column split
     // per class, chosen by read length only, collapsed to 0.08 of the issue roofline whenever fewer packs were resident than the
     // device has places -- 1e5 reads, the toyset, stages 2a / 3a / 3b, every rank of an 8-GPU job, the re-run of a few packs):
     // the barrier form keeps the most packs resident (seven or eight per CU: record words in the ring, 2 bytes per cell); the teams of
     // wavefronts give a pack that has (most of) a CU to itself the shortest row there is (dp_rows_mt).
     // tests / measurements: RATTLE_POA_MODE = dense | mt4 | mt2 | mt1 forces one form for the packed classes
-    uint32_t live_per_cu = 1, chain_per_cu = 1;    // packs per CU the pass about to start will keep resident (all classes; the long-chain groups)
-    auto choose_variants = [&]() {
+    void choose_variants() {
         uint64_t live = 0, chains = 0;
         for (int c = 0; c < POA_GROUPS; ++c) (poa_group_chain(c) ? chains : live) += C[c].todo.size();
         live_per_cu = (uint32_t)std::max<uint64_t>(1, (live + n_cu - 1) / n_cu);
@@ -3718,17 +3709,40 @@ int poa_device_run(rattle_ctx *ctx, const uint8_t *d_seq_in, const uint64_t *d_o
             if (C[c].no_teams && gc < 4) C[c].V = &k_dense[gc];
             if (poa_group_band(c) && !C[c].no_band) C[c].V = (poa_group_chain(c) ? c8 : l8) > 32 ? &k_band1 : &k_band4;      // (packs per CU in eighths: more than four -> one wavefront per pack)
         }
-    };
-    // pass 0: many slots with a modest arena; later passes: failed packs with larger arenas.
-    // The column classes of one pass run concurrently on their own streams.
-    // (RATTLE_POA_BUDGET_MB: tests shrink the arena to exercise the skip path)
-    const uint64_t budget = ENV.budget_mb ? ENV.budget_mb << 20 : (uint64_t)(free_b * 0.85);
-    // slot layout of class c for its current capacities; returns bytes per slot
-    auto plan_class = [&](int c, uint64_t tb, uint32_t tl) {
-        cls_plan &P = C[c];
+    }
+    // node and cell capacities of group g's first pass, for its largest pack (tb bases) and longest read (tl)
+    void first_pass_caps(int g, uint64_t tb, uint32_t tl) {
+        cls_plan &P = C[g];
+        // first-pass capacity: a pack of ~200 reads at 10 % error grows to ~5 nodes per base of its
+        // longest read; packs that still outgrow it are re-run with 4x nodes
+        P.node_cap = std::max<uint32_t>(P.node_cap, (uint32_t)std::min<uint64_t>(7ull * tl, 1u << 20));
+        // the DP record is the arena: 7 nodes per base of the longest read (measured: ~4.5 at the end of a 200-read pack
+        // at 10 % error), not a fixed floor -- a third of the memory, and of the seconds the allocation takes
+        P.cell_cap = (uint64_t)(std::min<uint64_t>(std::max<uint64_t>(7ull * tl, 2048), tb + 1) + 64) * (tl + 32);
+        if (P.V->pk == 8) {
+            // near-chain graphs: a few nodes beyond the longest sequence (3 x covers every pack of the bench's POA #2 / #3 four times over;
+            // a graph that outgrows it is no chain, and its pack goes to the full rows anyway); the record is the band's: 256 cells per row
+            P.node_cap = (uint32_t)std::min<uint64_t>(std::max<uint64_t>(3ull * tl, 1024), 1u << 20);
+            P.cell_cap = ((uint64_t)std::min<uint64_t>(P.node_cap, tb + 1) + 64) * (((uint64_t)tl + 511) / 512 * 512);      // (the band needs 512 cells per row at most; the full rows as strips of 512 columns the whole width)
+        }
+        if (poa_group_class(g) >= 4) {
+            // long reads: rows by depth, pack by pack (x 1.25 of the measured growth; a pack that still outgrows its slot is re-run)
+            uint64_t nmax = 0, cmax = 0;
+            for (uint32_t p : P.todo) {
+                const uint32_t reads = std::min<uint32_t>(pack_first[p + 1] - pack_first[p], 200u);
+                const uint64_t rows = std::min<uint64_t>(pbases[p] + 1, (uint64_t)(pmaxL[p] * (1.15 + 0.02 * reads) * 1.25) + 256);
+                nmax = std::max(nmax, rows);
+                cmax = std::max(cmax, (rows + 64) * (pmaxL[p] + 32));
+            }
+            P.node_cap = (uint32_t)std::min<uint64_t>(std::max<uint64_t>(nmax, 2048), 1u << 20);
+            P.cell_cap = cmax;
+        }
+    }
+    // slot layout of group g for its current capacities and instance: the capacities and offsets of P.A, the bytes per slot
+    void slot_layout(int g, uint64_t tb, uint32_t tl) {
+        cls_plan &P = C[g];
         const uint32_t cpl = P.V->cpl;
-        const int gc = poa_group_class(c);
-        const bool long_rows = gc == POA_CLASSES - 1;    // int32 cells, sequence read in place (no LDS copy)
+        const bool long_rows = poa_group_class(g) == POA_CLASSES - 1;    // int32 cells, sequence read in place (no LDS copy)
         uint32_t ncap = (uint32_t)std::min<uint64_t>(P.node_cap, tb + 1);
         ncap = (ncap + 31u) & ~31u;
         const uint32_t ecap = (uint32_t)std::min<uint64_t>(tb + 1, 0x7FFFFFFFull);
@@ -3738,7 +3752,7 @@ int poa_device_run(rattle_ctx *ctx, const uint8_t *d_seq_in, const uint64_t *d_o
         const uint64_t ccap = std::min<uint64_t>(P.cell_cap, (uint64_t)(ncap + 1) * qcap);
         poa_args &A = P.A;
         uint64_t o = 0;
-        auto take = [&](uint64_t bytes) { uint64_t r = o; o += (bytes + 255) & ~(uint64_t)255; return r; };
+        auto take = [&o](uint64_t bytes) { uint64_t r = o; o += (bytes + 255) & ~(uint64_t)255; return r; };
         A.o_nrec = take((uint64_t)ncap * 16); A.o_nal = take((uint64_t)ncap * 16); A.o_edges = take((uint64_t)ecap * 8);
         A.o_rank = take((uint64_t)ncap * 4); A.o_order = take((uint64_t)ncap * 4); A.o_order2 = take((uint64_t)ncap * 4);
         A.o_srank = take((uint64_t)ncap * 4); A.o_rowmax = take(((uint64_t)ncap + 1) * 16); A.o_lh = take(((uint64_t)ncap + 1) * 16); A.o_nn = take(((uint64_t)qcap + 16) * 8);
@@ -3754,17 +3768,33 @@ int poa_device_run(rattle_ctx *ctx, const uint8_t *d_seq_in, const uint64_t *d_o
         }
         A.o_aln = take((uint64_t)acap * 8); A.o_ainfo = take((uint64_t)acap * 16); A.o_spill = take((uint64_t)scap * 4);
         P.per_slot = o;
+        A.node_cap = ncap; A.edge_cap = ecap; A.cell_cap = ccap; A.aln_cap = acap; A.spill_cap = scap;
+        A.seq_cap = long_rows ? 16u : qcap;        // the sequence's LDS copy
         A.debug = ENV.debug;
+    }
+    // dynamic LDS of instance V with group g's capacities, ring and band
+    size_t lds_bytes(int g, const poa_variant *V) const {
+        const poa_args &A = C[g].A;
+        if (V->pk == 8) return (size_t)poa_lds_front(A.seq_cap, A.node_cap) + (size_t)A.band + 64;
+        if (V->pk == 7) return (size_t)poa_lds_front(A.seq_cap, A.node_cap) + (size_t)A.ring_slots * mt_slot_bytes((int)V->cpl, (int)V->nw) + 64;
+        return (size_t)A.seq_cap + poa_region_bytes(A.node_cap, (int)V->cpl, (int)V->ring, (int)V->nw, (int)V->pk) + 64;
+    }
+    // LDS plan of group g behind slot_layout: the teams' ring or the band's bytes, the instance without a ring (or the dense form) when the
+    // chosen one does not fit LDS, and the launch's dynamic LDS
+    void lds_plan(int g) {
+        cls_plan &P = C[g];
+        poa_args &A = P.A;
+        const int gc = poa_group_class(g);
+        const uint32_t ncap = A.node_cap, lds_seq = A.seq_cap;
         A.band = 0;
-        const uint32_t lds_seq = long_rows ? 16u : qcap;
         A.ring_slots = A.ring_reach = A.ring_slack = 0;
         bool mt_ring_ok = true;
         if (P.V->pk == 7) {
             // dp_rows_mt: the ring takes the LDS a workgroup can have when `live_per_cu` packs share a CU (up to 24 slots); `slack` rows may be in flight behind the reader (two rounds of the teams when there is room, one otherwise),
             // `reach` = slots - slack rows back are served from the ring, the rest from the record in HBM
             const uint32_t teams = P.V->ring, slotb = mt_slot_bytes((int)P.V->cpl, (int)P.V->nw);
-            const uint32_t fixed = lds_seq + (2u * poa_bit_words(ncap) + POA_STACK) * 4u + 64u + 3072u;      // + the kernel's static LDS
-            uint32_t ppc = std::max<uint32_t>(1, std::min<uint32_t>(poa_group_chain(c) ? chain_per_cu : live_per_cu, teams == 4 ? 1u : teams == 2 ? (MT2_MINWAVES >= 6 && P.V->cpl == 4 ? 3u : 2u) : 4u));      // (registers: 16 wavefronts of 128 per CU)
+            const uint32_t fixed = poa_lds_front(lds_seq, ncap) + 64u + 3072u;      // + the kernel's static LDS
+            uint32_t ppc = std::max<uint32_t>(1, std::min<uint32_t>(poa_group_chain(g) ? chain_per_cu : live_per_cu, teams == 4 ? 1u : teams == 2 ? (MT2_MINWAVES >= 6 && P.V->cpl == 4 ? 3u : 2u) : 4u));      // (registers: 16 wavefronts of 128 per CU)
             uint32_t slots = 0, slack = 0;
             for (; ppc >= 1; --ppc) {
                 const uint32_t room = 160u * 1024 / ppc;
@@ -3785,136 +3815,111 @@ int poa_device_run(rattle_ctx *ctx, const uint8_t *d_seq_in, const uint64_t *d_o
         if (P.V->pk == 8) {
             // the band's LDS behind the bitmaps and the stack: 8 ring slots of 4 columns per lane (4 when eight do not leave ten workgroups of one
             // wavefront a place on a CU), the selector table, junk words; between two DPs the tie labels and the traceback's tables
-            const uint32_t fixed = lds_seq + (2u * poa_bit_words(ncap) + POA_STACK) * 4u + 64u + 1024u;
+            const uint32_t qcap = lds_seq, fixed = poa_lds_front(lds_seq, ncap) + 64u + 1024u;
             uint32_t slots = 8;
             if (P.V->nw == 1 && 10u * (fixed + band_lds_bytes(slots, 4, qcap)) > 160u * 1024) slots = 4;
             A.band = std::max(band_lds_bytes(slots, 4, qcap), band_lds_bytes(2, 8, qcap));      // (eight columns per lane: the last resort, with a ring of two rows)
-            if (const char *v = getenv("RATTLE_POA_BAND_LDS")) A.band = (uint32_t)atoi(v);      // (measurements)
+            if (ENV.band_lds >= 0) A.band = (uint32_t)ENV.band_lds;      // (measurements)
         }
-        auto lds_bytes = [&](const poa_variant *V) {
-            if (V->pk == 8) return (size_t)lds_seq + (2u * poa_bit_words(ncap) + POA_STACK) * 4u + (size_t)A.band + 64;
-            if (V->pk == 7) return (size_t)lds_seq + (2u * poa_bit_words(ncap) + POA_STACK) * 4u + (size_t)A.ring_slots * mt_slot_bytes((int)V->cpl, (int)V->nw) + 64;
-            return (size_t)lds_seq + poa_region_bytes(ncap, (int)V->cpl, (int)V->ring, (int)V->nw, (int)V->pk) + 64;
-        };
         // a retry pass with a huge graph: the node bitmaps leave no room for a ready-made ring -- fall back to the dense form (2 bytes per cell)
-        if (gc < 4 && P.V->pk != 1 && P.V->pk != 8 && (lds_bytes(P.V) > 158u * 1024 || !mt_ring_ok)) { P.V = &k_dense[gc]; A.ring_slots = A.ring_reach = A.ring_slack = 0; A.o_planm = take(0); A.band = 0; }
-        if ((gc == 4 || gc == 5 || gc == 6) && (lds_bytes(P.V) > 158u * 1024 || ENV.noring)) P.V = &k_noring[gc - 4];
-        if (gc == POA_CLASSES - 1 && (lds_bytes(P.V) > 158u * 1024 || ENV.noring)) P.V = &k_long_noring;
-        P.shm = lds_bytes(P.V);
-        A.node_cap = ncap; A.edge_cap = ecap; A.cell_cap = ccap; A.aln_cap = acap; A.spill_cap = scap; A.seq_cap = lds_seq;
-        return o;
-    };
-    auto give_up = [&](cls_plan &P) -> int {       // the class's remaining packs do not fit this device
+        if (gc < 4 && P.V->pk != 1 && P.V->pk != 8 && (lds_bytes(g, P.V) > 158u * 1024 || !mt_ring_ok)) { P.V = &k_dense[gc]; A.ring_slots = A.ring_reach = A.ring_slack = 0; A.o_planm = P.per_slot; A.band = 0; }      // (o_planm: empty, at the end of the slot)
+        if ((gc == 4 || gc == 5 || gc == 6) && (lds_bytes(g, P.V) > 158u * 1024 || ENV.noring)) P.V = &k_noring[gc - 4];
+        if (gc == POA_CLASSES - 1 && (lds_bytes(g, P.V) > 158u * 1024 || ENV.noring)) P.V = &k_long_noring;
+        P.shm = lds_bytes(g, P.V);
+    }
+    uint64_t plan_group(int g, uint64_t tb, uint32_t tl) { slot_layout(g, tb, tl); lds_plan(g); return C[g].per_slot; }
+    int give_up(cls_plan &P) {       // the class's remaining packs do not fit this device
         if (!skipped) { set_error("poa: " + std::to_string(P.todo.size()) + " pack(s) exceed the device arena"); return RATTLE_ERR_HIP; }
         for (uint32_t p : P.todo) (*skipped)[p] = 1;
         P.todo.clear();
         return 0;
-    };
-    for (int pass = 0; pass < 64 && rc == 0; ++pass) {
-        bool any = false;
-        uint64_t want_bytes = 0;
-        choose_variants();
-        for (int c = 0; c < POA_GROUPS && rc == 0; ++c) {
+    }
+    // capacities, slot and LDS of every group with packs left, and the slots it could fill; *any: whether there is one
+    int size_pass(bool *any) {
+        *any = false;
+        want_bytes = 0;
+        for (int c = 0; c < POA_GROUPS; ++c) {
             cls_plan &P = C[c];
             P.n_slots = 0;
             if (P.todo.empty()) continue;
-            if (P.rounds >= 6) { rc = give_up(P); continue; }
-            std::sort(P.todo.begin(), P.todo.end(), [&](uint32_t a, uint32_t b) { return pbases[a] != pbases[b] ? pbases[a] > pbases[b] : a < b; });
+            if (P.rounds >= 6) { RT_TRY(give_up(P)); continue; }
+            std::sort(P.todo.begin(), P.todo.end(), [this](uint32_t a, uint32_t b) { return pbases[a] != pbases[b] ? pbases[a] > pbases[b] : a < b; });
             uint64_t tb = 0; uint32_t tl = 0;
             for (uint32_t p : P.todo) { tb = std::max(tb, pbases[p]); tl = std::max(tl, pmaxL[p]); }
-            if (P.rounds == 0 && !ENV.node_cap) {
-                // first-pass capacity: a pack of ~200 reads at 10 % error grows to ~5 nodes per base of its
-                // longest read; packs that still outgrow it are re-run with 4x nodes
-                P.node_cap = std::max<uint32_t>(P.node_cap, (uint32_t)std::min<uint64_t>(7ull * tl, 1u << 20));
-                // the DP record is the arena: 7 nodes per base of the longest read (measured: ~4.5 at the end of a 200-read pack
-                // at 10 % error), not a fixed floor -- a third of the memory, and of the seconds the allocation takes
-                P.cell_cap = (uint64_t)(std::min<uint64_t>(std::max<uint64_t>(7ull * tl, 2048), tb + 1) + 64) * (tl + 32);
-                if (P.V->pk == 8) {
-                    // near-chain graphs: a few nodes beyond the longest sequence (3 x covers every pack of the bench's POA #2 / #3 four times over;
-                    // a graph that outgrows it is no chain, and its pack goes to the full rows anyway); the record is the band's: 256 cells per row
-                    P.node_cap = (uint32_t)std::min<uint64_t>(std::max<uint64_t>(3ull * tl, 1024), 1u << 20);
-                    P.cell_cap = ((uint64_t)std::min<uint64_t>(P.node_cap, tb + 1) + 64) * (((uint64_t)tl + 511) / 512 * 512);      // (the band needs 512 cells per row at most; the full rows as strips of 512 columns the whole width)
-                }
-                if (poa_group_class(c) >= 4) {
-                    // long reads: rows by depth, pack by pack (x 1.25 of the measured growth; a pack that still outgrows its slot is re-run)
-                    uint64_t nmax = 0, cmax = 0;
-                    for (uint32_t p : P.todo) {
-                        const uint32_t reads = std::min<uint32_t>(pack_first[p + 1] - pack_first[p], 200u);
-                        const uint64_t rows = std::min<uint64_t>(pbases[p] + 1, (uint64_t)(pmaxL[p] * (1.15 + 0.02 * reads) * 1.25) + 256);
-                        nmax = std::max(nmax, rows);
-                        cmax = std::max(cmax, (rows + 64) * (pmaxL[p] + 32));
-                    }
-                    P.node_cap = (uint32_t)std::min<uint64_t>(std::max<uint64_t>(nmax, 2048), 1u << 20);
-                    P.cell_cap = cmax;
-                }
-            }
-            uint64_t per = plan_class(c, tb, tl);
+            if (P.rounds == 0 && !ENV.node_cap) first_pass_caps(c, tb, tl);
+            uint64_t per = plan_group(c, tb, tl);
             if (per > budget) {
                 // one slot does not fit the HBM that is left: cut the DP record to what does fit; a pack that
                 // still fails with that is beyond this device (skip-and-report, or an error for the MSA entry)
                 const uint64_t cell_b2 = poa_group_class(c) == POA_CLASSES - 1 ? 9 : 4;       // twice the bytes per cell
                 const uint64_t fixed = per - (P.A.cell_cap * cell_b2 + 1) / 2;
-                if (P.clamped || fixed + (1ull << 20) >= budget) { rc = give_up(P); continue; }
+                if (P.clamped || fixed + (1ull << 20) >= budget) { RT_TRY(give_up(P)); continue; }
                 P.cell_cap = (budget - fixed - (1ull << 20)) * 2 / cell_b2;
                 P.clamped = true;
-                per = plan_class(c, tb, tl);
-                if (per > budget) { rc = give_up(P); continue; }
+                per = plan_group(c, tb, tl);
+                if (per > budget) { RT_TRY(give_up(P)); continue; }
             }
-            any = true;
+            *any = true;
             P.bpc = P.V->max_blocks(P.shm);
             uint32_t places = n_cu * (uint32_t)P.bpc;
             P.n_slots = std::min<uint32_t>((uint32_t)P.todo.size(), places);
             want_bytes += P.per_slot * P.n_slots;
         }
-        if (rc || !any) break;
-        if (want_bytes > budget) {
-            // Memory decides how many packs of each group run at once.  A group lasts about (its work) / (its slots), so the pass
-            // is shortest when every group gets slots in proportion to its work: T = sum(work x bytes per slot) / budget,
-            // slots = work / T (config 5: the deep 8 - 20 kb packs are a few per cent of the packs and most of the work; a cut in
-            // proportion to the number of packs left them 4 slots and the pass to one class).  Work of a pack as below: bases x
-            // longest read / threads.  Groups capped by their pack count or by the device hand their share back (two rounds).
-            double work[POA_GROUPS] = {0};
-            uint32_t cap[POA_GROUPS] = {0};
-            bool fixed[POA_GROUPS] = {false};
-            for (int c = 0; c < POA_GROUPS; ++c) if (C[c].n_slots) {
-                cap[c] = C[c].n_slots;
-                for (uint32_t p : C[c].todo) work[c] += (double)pbases[p] * (double)pmaxL[p] / (64.0 * C[c].V->nw);
+        return 0;
+    }
+    // Memory decides how many packs of each group run at once.  A group lasts about (its work) / (its slots), so the pass
+    // is shortest when every group gets slots in proportion to its work: T = sum(work x bytes per slot) / budget,
+    // slots = work / T (config 5: the deep 8 - 20 kb packs are a few per cent of the packs and most of the work; a cut in
+    // proportion to the number of packs left them 4 slots and the pass to one class).  Work of a pack: pack_work.
+    // Groups capped by their pack count or by the device hand their share back (two rounds).
+    void share_budget() {
+        if (want_bytes <= budget) return;
+        double work[POA_GROUPS] = {0};
+        uint32_t cap[POA_GROUPS] = {0};
+        bool fixed[POA_GROUPS] = {false};
+        for (int c = 0; c < POA_GROUPS; ++c) if (C[c].n_slots) {
+            cap[c] = C[c].n_slots;
+            for (uint32_t p : C[c].todo) work[c] += pack_work(p, C[c].V);
+        }
+        for (int round = 0; round < 3; ++round) {
+            double wm = 0, left = (double)budget;
+            for (int c = 0; c < POA_GROUPS; ++c) if (cap[c]) {
+                if (fixed[c]) left -= (double)C[c].per_slot * C[c].n_slots;
+                else wm += work[c] * (double)C[c].per_slot;
             }
-            for (int round = 0; round < 3; ++round) {
-                double wm = 0, left = (double)budget;
-                for (int c = 0; c < POA_GROUPS; ++c) if (cap[c]) {
-                    if (fixed[c]) left -= (double)C[c].per_slot * C[c].n_slots;
-                    else wm += work[c] * (double)C[c].per_slot;
-                }
-                if (wm <= 0 || left <= 0) break;
-                const double T = wm / left;
-                for (int c = 0; c < POA_GROUPS; ++c) if (cap[c] && !fixed[c]) {
-                    const double want = work[c] / T;
-                    if (want >= cap[c]) { C[c].n_slots = cap[c]; fixed[c] = true; }
-                    else C[c].n_slots = std::max<uint32_t>(1, (uint32_t)want);
-                }
-            }
-            want_bytes = 0;
-            for (int c = POA_GROUPS - 1; c >= 0; --c) if (C[c].n_slots) {
-                if (want_bytes + C[c].per_slot * C[c].n_slots > budget) {
-                    C[c].n_slots = (uint32_t)((budget - want_bytes) / C[c].per_slot);     // may become 0: deferred to a later pass
-                }
-                want_bytes += C[c].per_slot * C[c].n_slots;
+            if (wm <= 0 || left <= 0) break;
+            const double T = wm / left;
+            for (int c = 0; c < POA_GROUPS; ++c) if (cap[c] && !fixed[c]) {
+                const double want = work[c] / T;
+                if (want >= cap[c]) { C[c].n_slots = cap[c]; fixed[c] = true; }
+                else C[c].n_slots = std::max<uint32_t>(1, (uint32_t)want);
             }
         }
-        phase_timer T_round("    poa pass (arena+kernels)");
-        if (ctx->poa_arena_bytes < want_bytes) {
-            if (ctx->poa_arena) (void)hipFree(ctx->poa_arena);
-            ctx->poa_arena = nullptr; ctx->poa_arena_bytes = 0;
-            // allocating (and freeing) tens of GB costs seconds (the driver clears the memory, ~20 ms per GB): take a tenth
-            // more so that the next stage, whose packs differ a little, does not trigger another round of it
-            uint64_t take_bytes = std::min<uint64_t>(budget, want_bytes + want_bytes / 10);
-            if (hipMalloc((void **)&ctx->poa_arena, take_bytes) != hipSuccess) {
-                take_bytes = want_bytes;
-                if (hipMalloc((void **)&ctx->poa_arena, take_bytes) != hipSuccess) { set_error("poa: arena allocation failed"); rc = RATTLE_ERR_HIP; break; }
+        want_bytes = 0;
+        for (int c = POA_GROUPS - 1; c >= 0; --c) if (C[c].n_slots) {
+            if (want_bytes + C[c].per_slot * C[c].n_slots > budget) {
+                C[c].n_slots = (uint32_t)((budget - want_bytes) / C[c].per_slot);     // may become 0: deferred to a later pass
             }
-            ctx->poa_arena_bytes = take_bytes;
+            want_bytes += C[c].per_slot * C[c].n_slots;
         }
+    }
+    // the context's arena holds want_bytes
+    int ensure_arena() {
+        if (ctx->poa_arena_bytes >= want_bytes) return 0;
+        if (ctx->poa_arena) (void)hipFree(ctx->poa_arena);
+        ctx->poa_arena = nullptr; ctx->poa_arena_bytes = 0;
+        // allocating (and freeing) tens of GB costs seconds (the driver clears the memory, ~20 ms per GB): take a tenth
+        // more so that the next stage, whose packs differ a little, does not trigger another round of it
+        uint64_t take_bytes = std::min<uint64_t>(budget, want_bytes + want_bytes / 10);
+        if (hipMalloc((void **)&ctx->poa_arena, take_bytes) != hipSuccess) {
+            take_bytes = want_bytes;
+            if (hipMalloc((void **)&ctx->poa_arena, take_bytes) != hipSuccess) { set_error("poa: arena allocation failed"); return RATTLE_ERR_HIP; }
+        }
+        ctx->poa_arena_bytes = take_bytes;
+        return 0;
+    }
+    // every running group's queue and its part of the arena, and its line of the timing output
+    int upload_queues(int pass) {
         hipError_t e = hipMemsetAsync(d_heads.p, 0, 128, st);
         uint64_t aoff = 0;
         uint32_t qoff = 0;
@@ -3923,10 +3928,10 @@ int poa_device_run(rattle_ctx *ctx, const uint8_t *d_seq_in, const uint64_t *d_o
             if (!P.n_slots) continue;
             e = hipMemcpyAsync(d_queue.p + qoff, P.todo.data(), P.todo.size() * 4, hipMemcpyHostToDevice, st);
             poa_args &A = P.A;
-            A.seq = d_seq.p; A.off = d_off.p; A.pack_first = d_pf.p; A.queue = d_queue.p + qoff; A.n_queue = (uint32_t)P.todo.size();
+            A.seq = d_seq; A.off = d_off; A.pack_first = d_pf.p; A.queue = d_queue.p + qoff; A.n_queue = (uint32_t)P.todo.size();
             A.queue_head = d_heads.p + c; A.arena = ctx->poa_arena + aoff; A.slot_stride = P.per_slot;
-            A.out_col = d_col.p; A.out_width = d_width.p; A.status = d_status.p; A.counters = d_cnt.p; A.prof = d_cnt.p + 32 + 8 * poa_group_class(c);
-            A.timeline = tl_path ? d_tl.p : nullptr;
+            A.out_col = d_col; A.out_width = d_width; A.status = d_status.p; A.counters = d_cnt.p; A.prof = d_cnt.p + POA_CNT_PROFILE + 8 * poa_group_class(c);
+            A.timeline = ENV.timeline ? d_tl.p : nullptr;
             aoff += P.per_slot * P.n_slots;
             qoff += (uint32_t)P.todo.size();
             if (ENV.timing)
@@ -3935,7 +3940,12 @@ int poa_device_run(rattle_ctx *ctx, const uint8_t *d_seq_in, const uint64_t *d_o
                         P.V->pk == 7 ? "teams" : "ring", P.V->ring, P.V->pk == 7 ? (", ring " + std::to_string(A.ring_slots) + " reach " + std::to_string(A.ring_reach)).c_str() : "", pass, P.todo.size(), P.n_slots,
                         P.per_slot / 1e6, P.bpc, c, P.V->pk, P.V->pk == 8 ? (" band " + std::to_string(A.band)).c_str() : "");      // (group, PK and the band's LDS bytes: which instance ran, for the tests)
         }
-        if (e != hipSuccess) { set_error(std::string("poa setup: ") + hipGetErrorString(e)); rc = RATTLE_ERR_HIP; break; }
+        if (e != hipSuccess) { set_error(std::string("poa setup: ") + hipGetErrorString(e)); return RATTLE_ERR_HIP; }
+        return 0;
+    }
+    // the groups of the pass onto the streams, and their statuses back
+    int launch_pass() {
+        hipError_t e;
         {
             ktimer T(ctx, K_POA, 0);
             e = hipEventRecord(ctx->poa_go, st);
@@ -3943,15 +3953,14 @@ int poa_device_run(rattle_ctx *ctx, const uint8_t *d_seq_in, const uint64_t *d_o
             // default) that HIP streams share: seven classes on seven streams left the 6144-column class waiting behind the
             // 8192-column one for its whole run (config 5, profiles/round3_*).  So the classes are dealt onto at most four
             // streams, longest estimated run first onto the least loaded stream; a stream runs its classes in that order.
-            // Estimate: a pack costs bases x longest read / threads of its workgroup; a class lasts as long as its longest
-            // pack or its total over its slots.
+            // Estimate: a pack costs pack_work; a class lasts as long as its longest pack or its total over its slots.
             double est[POA_GROUPS] = {0};
             int order[POA_GROUPS], n_run = 0;
             for (int c = 0; c < POA_GROUPS; ++c) {
                 cls_plan &P = C[c];
                 if (!P.n_slots) continue;
                 double tot = 0, longest = 0;
-                for (uint32_t p : P.todo) { const double w = (double)pbases[p] * (double)pmaxL[p] / (64.0 * P.V->nw); tot += w; longest = std::max(longest, w); }
+                for (uint32_t p : P.todo) { const double w = pack_work(p, P.V); tot += w; longest = std::max(longest, w); }
                 est[c] = std::max(longest, tot / P.n_slots);
                 order[n_run++] = c;
             }
@@ -3993,8 +4002,20 @@ int poa_device_run(rattle_ctx *ctx, const uint8_t *d_seq_in, const uint64_t *d_o
         }
         if (e == hipSuccess) e = hipMemcpyAsync(h_status.data(), d_status.p, n_packs * 4, hipMemcpyDeviceToHost, st);
         if (e == hipSuccess) e = hipStreamSynchronize(st);
-        if (e != hipSuccess) { set_error(std::string("poa_kernel: ") + hipGetErrorString(e)); rc = RATTLE_ERR_HIP; break; }
-        for (int c = 0; c < POA_GROUPS && rc == 0; ++c) {
+        if (e != hipSuccess) { set_error(std::string("poa_kernel: ") + hipGetErrorString(e)); return RATTLE_ERR_HIP; }
+        return 0;
+    }
+    // what a wavefront of dp_rows_mt left in POA_CNT_SYNC when it gave up a wait: who, for what, at which row (full: and in a pack of which size)
+    std::string sync_diagnosis(bool full) const {
+        unsigned long long dbg[3] = {0, 0, 0};
+        (void)hipMemcpy(dbg, d_cnt.p + POA_CNT_SYNC, sizeof(dbg), hipMemcpyDeviceToHost);
+        const std::string who = "wait " + std::to_string(dbg[0] & 0xFF) + " of team " + std::to_string((dbg[0] >> 8) & 0xFF) + " block " + std::to_string((dbg[0] >> 16) & 0xFF) + " at row " + std::to_string(dbg[0] >> 32);
+        const std::string saw = std::to_string((int32_t)(dbg[1] & 0xFFFFFFFFu)), wants = std::to_string((int32_t)(dbg[1] >> 32));
+        return full ? who + ": saw " + saw + ", wants " + wants + "; rows " + std::to_string(dbg[2] & 0xFFFFFFFFu) + ", columns " + std::to_string(dbg[2] >> 32) : who + " (saw " + saw + ", wants " + wants + ")";
+    }
+    // the statuses of the pass: which packs of each group run again, in which form and with which capacities
+    int judge_pass() {
+        for (int c = 0; c < POA_GROUPS; ++c) {
             cls_plan &P = C[c];
             if (!P.n_slots) continue;
             ++P.rounds;
@@ -4005,28 +4026,18 @@ int poa_device_run(rattle_ctx *ctx, const uint8_t *d_seq_in, const uint64_t *d_o
             for (uint32_t p : P.todo) {
                 const uint32_t s = h_status[p];
                 if (s == POA_OK) continue;
-                if (s == POA_ERR_NODES || s == POA_ERR_CELLS || s == POA_ERR_SPILL || s == POA_ERR_ALN) ++cap_retry;
-                if (s == POA_ERR_NODES || s == POA_ERR_CELLS || s == POA_ERR_SPILL || s == POA_ERR_ALN) again.push_back(p);
+                if (s == POA_ERR_NODES || s == POA_ERR_CELLS || s == POA_ERR_SPILL || s == POA_ERR_ALN) { ++cap_retry; again.push_back(p); }
                 else if (s == POA_ERR_BAND) { again.push_back(p); band_retry = true; }
                 else if (s == POA_ERR_SYNC && !P.no_teams) {
                     // a wavefront of the team kernels gave up a bounded wait (a debugger stop, a trap handler, a throttled device, or a
                     // protocol error): the pack is dropped and run again in the barrier form, which cannot time out
                     again.push_back(p); sync_retry = true;
-                    if (ENV.timing) {
-                        unsigned long long dbg[3] = {0, 0, 0};
-                        (void)hipMemcpy(dbg, d_cnt.p + 8, sizeof(dbg), hipMemcpyDeviceToHost);
-                        fprintf(stderr, "[rattle]     poa: pack %u gave up wait %llu of team %llu block %llu at row %llu (saw %d, wants %d): again in the barrier form\n", p, dbg[0] & 0xFF, (dbg[0] >> 8) & 0xFF,
-                                (dbg[0] >> 16) & 0xFF, dbg[0] >> 32, (int32_t)(dbg[1] & 0xFFFFFFFFu), (int32_t)(dbg[1] >> 32));
-                    }
+                    if (ENV.timing) fprintf(stderr, "[rattle]     poa: pack %u gave up %s: again in the barrier form\n", p, sync_diagnosis(false).c_str());
                 } else {
                     std::string msg = "poa_kernel: pack " + std::to_string(p) + " failed with status " + std::to_string(s);
-                    if (s == POA_ERR_SYNC) {       // a wavefront of dp_rows_mt gave up waiting: say who, for what, at which row
-                        unsigned long long dbg[3] = {0, 0, 0};
-                        (void)hipMemcpy(dbg, d_cnt.p + 8, sizeof(dbg), hipMemcpyDeviceToHost);
-                        msg += " (wait " + std::to_string(dbg[0] & 0xFF) + " of team " + std::to_string((dbg[0] >> 8) & 0xFF) + " block " + std::to_string((dbg[0] >> 16) & 0xFF) + " at row " + std::to_string(dbg[0] >> 32) +
-                               ": saw " + std::to_string((int32_t)(dbg[1] & 0xFFFFFFFFu)) + ", wants " + std::to_string((int32_t)(dbg[1] >> 32)) + "; rows " + std::to_string(dbg[2] & 0xFFFFFFFFu) + ", columns " + std::to_string(dbg[2] >> 32) + ")";
-                    }
-                    set_error(msg); rc = RATTLE_ERR_HIP; break;
+                    if (s == POA_ERR_SYNC) msg += " (" + sync_diagnosis(true) + ")";
+                    set_error(msg);
+                    return RATTLE_ERR_HIP;
                 }
             }
             P.todo.swap(again);
@@ -4035,7 +4046,7 @@ int poa_device_run(rattle_ctx *ctx, const uint8_t *d_seq_in, const uint64_t *d_o
                 // what is left of this group runs over the full rows from here on, with the capacities of a first pass of those forms
                 if (ENV.timing) {
                     unsigned long long dbg[2] = {0, 0};
-                    (void)hipMemcpy(dbg, d_cnt.p + 14, sizeof(dbg), hipMemcpyDeviceToHost);
+                    (void)hipMemcpy(dbg, d_cnt.p + POA_CNT_BAND_DIAG, sizeof(dbg), hipMemcpyDeviceToHost);
                     fprintf(stderr, "[rattle]     poa: %zu pack(s) of group %d have an alignment without a certified band (or outgrew the band's slot): again over the full rows (the last one: sequence %llu of its pack, %llu nt against %llu rows, best score in the band %llu)\n",
                             P.todo.size(), c, dbg[1] & 0xFFFFFFFFu, dbg[0] >> 32, dbg[0] & 0xFFFFFFFFu, dbg[1] >> 32);
                 }
@@ -4043,58 +4054,56 @@ int poa_device_run(rattle_ctx *ctx, const uint8_t *d_seq_in, const uint64_t *d_o
                 continue;
             }
             if (!P.todo.empty()) {
-                if (P.clamped) { rc = give_up(P); continue; }
+                if (P.clamped) { RT_TRY(give_up(P)); continue; }
                 P.node_cap = std::min<uint32_t>(P.node_cap * 4, 1u << 20); P.cell_cap *= 8;
             }
         }
+        return 0;
     }
-    d_heads.release();
-    if (rc == 0) {
+    // widths and counters back to the host; the timeline file and the read-outs of the measurement builds
+    int finish() {
         size_t left = 0;
         for (int c = 0; c < POA_GROUPS; ++c) left += C[c].todo.size();
-        if (left) { set_error("poa: " + std::to_string(left) + " pack(s) exceed the device arena"); rc = RATTLE_ERR_HIP; }
-    }
-    if (rc == 0) {
-        hipError_t e = hipMemcpyAsync(h_width_out, d_width.p, n_packs * 4, hipMemcpyDeviceToHost, st);
-        if (e == hipSuccess) e = hipMemcpyAsync(h_cnt, d_cnt.p, 128, hipMemcpyDeviceToHost, st);
+        if (left) { set_error("poa: " + std::to_string(left) + " pack(s) exceed the device arena"); return RATTLE_ERR_HIP; }
+        hipError_t e = hipMemcpyAsync(h_width_out, d_width, n_packs * 4, hipMemcpyDeviceToHost, st);
+        if (e == hipSuccess) e = hipMemcpyAsync(h_cnt, d_cnt.p, POA_CNT_PUBLIC * 8, hipMemcpyDeviceToHost, st);
 #ifdef POA_PROFILE
-        if (e == hipSuccess) e = hipMemcpyAsync(h_prof, d_cnt.p + 32, sizeof(h_prof), hipMemcpyDeviceToHost, st);
+        if (e == hipSuccess) e = hipMemcpyAsync(h_prof, d_cnt.p + POA_CNT_PROFILE, sizeof(h_prof), hipMemcpyDeviceToHost, st);
 #endif
 #ifdef POA_BARPROF
-        if (e == hipSuccess) e = hipMemcpyAsync(h_seg, d_cnt.p + 16, sizeof(h_seg), hipMemcpyDeviceToHost, st);
+        if (e == hipSuccess) e = hipMemcpyAsync(h_seg, d_cnt.p + POA_CNT_BARPROF, sizeof(h_seg), hipMemcpyDeviceToHost, st);
 #endif
 #ifdef POA_HIST
-        if (e == hipSuccess) e = hipMemcpyAsync(h_hist, d_cnt.p, 160 * 8, hipMemcpyDeviceToHost, st);
+        if (e == hipSuccess) e = hipMemcpyAsync(h_hist, d_cnt.p, POA_CNT_WORDS * 8, hipMemcpyDeviceToHost, st);
 #endif
         if (e == hipSuccess) e = hipStreamSynchronize(st);
-        if (e != hipSuccess) { set_error(std::string("poa readback: ") + hipGetErrorString(e)); rc = RATTLE_ERR_HIP; }
-    }
-    if (rc == 0 && ENV.timing && (h_cnt[12] || h_cnt[13] || h_cnt[10]))
-        fprintf(stderr, "[rattle]     poa band: %llu alignments with a certified band, %llu failed certificates, %llu alignments over the full rows as strips; cells computed %.3g of %.3g\n", h_cnt[12], h_cnt[13], h_cnt[10],
-                (double)h_cnt[11], (double)h_cnt[0]);
-    if (rc == 0 && tl_path) {
-        std::vector<unsigned long long> tl(2 * (size_t)n_packs);
-        if (hipMemcpy(tl.data(), d_tl.p, 16 * (size_t)n_packs, hipMemcpyDeviceToHost) == hipSuccess) {
-            if (FILE *f = fopen(tl_path, "a")) {
-                fprintf(f, "# pass: pack class reads bases start end (ticks of 10 ns)\n");
-                for (uint32_t p = 0; p < n_packs; ++p) {
-                    int cls = 0;
-                    while (cls < POA_CLASSES - 1 && pmaxL[p] > k_class_cols[cls]) ++cls;
-                    fprintf(f, "%u %d %u %llu %llu %llu\n", p, cls, pack_first[p + 1] - pack_first[p], (unsigned long long)pbases[p], tl[2 * p], tl[2 * p + 1]);
+        if (e != hipSuccess) { set_error(std::string("poa readback: ") + hipGetErrorString(e)); return RATTLE_ERR_HIP; }
+        if (ENV.timing && (h_cnt[POA_CNT_BAND_OK] || h_cnt[POA_CNT_BAND_FAIL] || h_cnt[POA_CNT_STRIPS]))
+            fprintf(stderr, "[rattle]     poa band: %llu alignments with a certified band, %llu failed certificates, %llu alignments over the full rows as strips; cells computed %.3g of %.3g\n", h_cnt[POA_CNT_BAND_OK], h_cnt[POA_CNT_BAND_FAIL], h_cnt[POA_CNT_STRIPS],
+                    (double)h_cnt[POA_CNT_CELLS_DONE], (double)h_cnt[POA_CNT_CELLS]);
+        if (ENV.timeline) {
+            std::vector<unsigned long long> tl(2 * (size_t)n_packs);
+            if (hipMemcpy(tl.data(), d_tl.p, 16 * (size_t)n_packs, hipMemcpyDeviceToHost) == hipSuccess) {
+                if (FILE *f = fopen(ENV.timeline, "a")) {
+                    fprintf(f, "# pass: pack class reads bases start end (ticks of 10 ns)\n");
+                    for (uint32_t p = 0; p < n_packs; ++p)
+                        fprintf(f, "%u %d %u %llu %llu %llu\n", p, poa_length_class(pmaxL[p]), pack_first[p + 1] - pack_first[p], (unsigned long long)pbases[p], tl[2 * p], tl[2 * p + 1]);
+                    fclose(f);
                 }
-                fclose(f);
             }
         }
+        if (skipped) for (uint32_t p = 0; p < n_packs; ++p) if ((*skipped)[p]) h_width_out[p] = 0;
+        print_measurements();
+        ctx->stats[K_POA].bytes += 6ull * h_cnt[POA_CNT_CELLS];
+        return 0;
     }
-    d_pf.release(); d_queue.release(); d_status.release(); d_cnt.release();
-    if (rc) return rc;
-    if (skipped) for (uint32_t p = 0; p < n_packs; ++p) if ((*skipped)[p]) h_width_out[p] = 0;
+    // the read-outs of the POA_HIST / POA_PROFILE / POA_BARPROF builds (which reuse counter slots by number, see poa_counter)
+    void print_measurements() {
 #ifdef POA_HIST
-    fprintf(stderr, "[rattle] predecessor row distance histogram (first in-edge | further in-edges), d = 1..62, 63+:\n");
-    for (int d = 1; d < 64; ++d) fprintf(stderr, "  d%-2d %12llu %12llu\n", d, h_hist[16 + d], h_hist[80 + d]);
+        fprintf(stderr, "[rattle] predecessor row distance histogram (first in-edge | further in-edges), d = 1..62, 63+:\n");
+        for (int d = 1; d < 64; ++d) fprintf(stderr, "  d%-2d %12llu %12llu\n", d, h_hist[16 + d], h_hist[80 + d]);
 #endif
 #ifdef POA_PROFILE
-    {
         // phase breakdown per column class (ticks of the 100 MHz wall clock, summed over the class's workgroups)
         static const char *names[8] = {"plan", "dp_rows", "ties", "traceback", "add_alignment", "merge_order", "final_sort_columns", "pack_total"};
         FILE *jf = ENV.profile_json ? fopen(ENV.profile_json, "a") : nullptr;
@@ -4105,22 +4114,50 @@ int poa_device_run(rattle_ctx *ctx, const uint8_t *d_seq_in, const uint64_t *d_o
             for (int i = 0; i < 7; ++i) fprintf(stderr, " %s %.1f", names[i], 100.0 * (double)q[i] / (double)q[7]);
             fprintf(stderr, "  (total %.3f block-seconds)\n", (double)q[7] * 1e-8);
             if (jf) {
-                fprintf(jf, "{\"class\": %d, \"cols\": %u, \"n_packs\": %zu, \"block_seconds\": %.6f", c, c < POA_CLASSES - 1 ? k_class_cols[c] : 0u, by_class[c].size() + (c >= 4 ? by_class[c + 4].size() : 0), (double)q[7] * 1e-8);
+                fprintf(jf, "{\"class\": %d, \"cols\": %u, \"n_packs\": %zu, \"block_seconds\": %.6f", c, c < POA_CLASSES - 1 ? k_class_cols[c] : 0u, group_packs[c] + (c >= 4 ? group_packs[c + 4] : 0), (double)q[7] * 1e-8);
                 for (int i = 0; i < 7; ++i) fprintf(jf, ", \"%s_pct\": %.2f", names[i], 100.0 * (double)q[i] / (double)q[7]);
                 fprintf(jf, "}\n");
             }
         }
         if (jf) fclose(jf);
-    }
 #endif
 #ifdef POA_BARPROF
-    fprintf(stderr, "[rattle] barrier cycles / dp cycles per wave: %.3f %.3f %.3f %.3f  (dp cycles per row, wave 0: %.0f)\n", (double)h_cnt[8] / h_cnt[12], (double)h_cnt[9] / h_cnt[13],
-            (double)h_cnt[10] / h_cnt[14], (double)h_cnt[11] / h_cnt[15], (double)h_cnt[12] / (double)h_cnt[3]);
-    fprintf(stderr, "[rattle] wave 1, cycles per row: predecessors %.0f, scores+prefix+scan %.0f, barrier %.0f, after barrier %.0f (of %.0f)\n", (double)h_seg[0] / h_cnt[3],
-            (double)h_seg[1] / h_cnt[3], (double)h_cnt[9] / h_cnt[3], (double)h_seg[2] / h_cnt[3], (double)h_cnt[13] / h_cnt[3]);
+        fprintf(stderr, "[rattle] barrier cycles / dp cycles per wave: %.3f %.3f %.3f %.3f  (dp cycles per row, wave 0: %.0f)\n", (double)h_cnt[8] / h_cnt[12], (double)h_cnt[9] / h_cnt[13],
+                (double)h_cnt[10] / h_cnt[14], (double)h_cnt[11] / h_cnt[15], (double)h_cnt[12] / (double)h_cnt[3]);
+        fprintf(stderr, "[rattle] wave 1, cycles per row: predecessors %.0f, scores+prefix+scan %.0f, barrier %.0f, after barrier %.0f (of %.0f)\n", (double)h_seg[0] / h_cnt[3],
+                (double)h_seg[1] / h_cnt[3], (double)h_cnt[9] / h_cnt[3], (double)h_seg[2] / h_cnt[3], (double)h_cnt[13] / h_cnt[3]);
 #endif
-    ctx->stats[K_POA].bytes += 6ull * h_cnt[0];
-    return 0;
+    }
+};
+
+// Device-resident core: sequences, offsets and the per-base column output live in HBM; the host only
+// plans (lengths / pack boundaries) and reads back pack widths, statuses and counters.
+// skipped != nullptr: packs that do not fit the device are flagged there (1) instead of failing the call;
+// their width is 0 and their columns are undefined.
+int poa_device_run(rattle_ctx *ctx, const uint8_t *d_seq_in, const uint64_t *d_off_in, const uint64_t *off, uint32_t n_seqs,
+                   const uint32_t *pack_first, uint32_t n_packs, uint32_t *d_col_out, uint32_t *d_width_out, uint32_t *h_width_out,
+                   unsigned long long *h_cnt, std::vector<uint8_t> *skipped) {
+    for (int i = 0; i < POA_CNT_PUBLIC; ++i) h_cnt[i] = 0;
+    if (skipped) skipped->assign(n_packs, 0);
+    if (n_packs == 0 || n_seqs == 0) { for (uint32_t p = 0; p < n_packs; ++p) h_width_out[p] = 0; return 0; }
+    if (pack_first[0] != 0 || pack_first[n_packs] != n_seqs) { set_error("pack_first must cover [0, n_seqs]"); return RATTLE_ERR_ARG; }
+
+    poa_run R{ctx, ctx->stream, d_seq_in, d_off_in, off, n_seqs, pack_first, n_packs, d_col_out, d_width_out, h_width_out, h_cnt, skipped};
+    RT_TRY(R.classify());
+    RT_TRY(R.setup());
+    for (int pass = 0; pass < 64; ++pass) {
+        bool any = false;
+        R.choose_variants();
+        RT_TRY(R.size_pass(&any));
+        if (!any) break;
+        R.share_budget();
+        phase_timer T_round("    poa pass (arena+kernels)");
+        RT_TRY(R.ensure_arena());
+        RT_TRY(R.upload_queues(pass));
+        RT_TRY(R.launch_pass());
+        RT_TRY(R.judge_pass());
+    }
+    return R.finish();
 }
 
 // Host-buffer entry (rattle_hip_poa_msa): upload, run, read the per-base columns back and expand rows.
@@ -4133,7 +4170,6 @@ int poa_msa_run(rattle_ctx *ctx, const uint8_t *seq, const uint64_t *off, uint32
     R->row_offset = (uint64_t *)calloc((size_t)n_seqs + 1, sizeof(uint64_t));
     *out = R;
     if (n_packs == 0 || n_seqs == 0) { R->rows = (char *)calloc(1, 1); return 0; }
-    if (pack_first[0] != 0 || pack_first[n_packs] != n_seqs) { set_error("pack_first must cover [0, n_seqs]"); return RATTLE_ERR_ARG; }
     const uint64_t total = off[n_seqs];
     if (total && memchr(seq, 0, total)) { set_error("NUL byte in sequence"); return RATTLE_ERR_ARG; }
     dbuf<uint8_t> d_seq; dbuf<uint64_t> d_off; dbuf<uint32_t> d_col, d_width;
@@ -4141,7 +4177,7 @@ int poa_msa_run(rattle_ctx *ctx, const uint8_t *seq, const uint64_t *off, uint32
     RT_HIP(hipMemcpyAsync(d_seq.p, seq, total, hipMemcpyHostToDevice, st));
     RT_HIP(hipMemcpyAsync(d_off.p, off, (n_seqs + 1) * 8, hipMemcpyHostToDevice, st));
     std::vector<uint32_t> h_width(n_packs);
-    unsigned long long h_cnt[16];
+    unsigned long long h_cnt[POA_CNT_PUBLIC];
     int rc = poa_device_run(ctx, d_seq.p, d_off.p, off, n_seqs, pack_first, n_packs, d_col.p, d_width.p, h_width.data(), h_cnt, nullptr);
     if (rc == 0) {
         phase_timer T_d2h("    poa readback");
@@ -4152,7 +4188,7 @@ int poa_msa_run(rattle_ctx *ctx, const uint8_t *seq, const uint64_t *off, uint32
             if (e != hipSuccess) { set_error(std::string("poa readback: ") + hipGetErrorString(e)); rc = RATTLE_ERR_HIP; }
         }
     }
-    d_seq.release(); d_off.release(); d_col.release(); d_width.release();
+    d_seq.release(); d_off.release(); d_col.release(); d_width.release();      // (before the host expands the rows)
     if (rc) return rc;
 
     // expand rows on the host (one task per pack): row = '-' * width with each base at its column
@@ -4177,7 +4213,7 @@ int poa_msa_run(rattle_ctx *ctx, const uint8_t *seq, const uint64_t *off, uint32
     });
     for (int i = 0; i < 8; ++i) R->counters[i] = h_cnt[i];
 #if !defined(POA_PROFILE) && !defined(POA_PREDSTAT)
-    R->counters[4] = h_cnt[11]; R->counters[5] = h_cnt[12]; R->counters[6] = h_cnt[13];      // DP cells computed; alignments with a certified band / a failed certificate
+    R->counters[4] = h_cnt[POA_CNT_CELLS_DONE]; R->counters[5] = h_cnt[POA_CNT_BAND_OK]; R->counters[6] = h_cnt[POA_CNT_BAND_FAIL];      // DP cells computed; alignments with a certified band / a failed certificate
 #endif
     return 0;
 }
