@@ -362,6 +362,46 @@ int rattle_hip_debug_evaluate(rattle_ctx *ctx, const rattle_cluster_params *para
                               uint32_t n_rects, rattle_debug_eval **out);
 void rattle_hip_debug_evaluate_free(rattle_debug_eval *e);
 
+/* Test hook: the post-MSA kernel (fix_msa_ends, column vote, per-read correction or pack consensus) ALONE on a given MSA, launched
+ * by the code `correct` launches it with, and everything it wrote.  The MSA is given the way the POA kernel hands it over: per pack
+ * its rows (sequences without gaps) and width, per base its MSA column.  In every pack of width > 0 the columns of a row must be
+ * strictly increasing and below the width, and the bases A, C, G, T or U; a pack of width 0 is what a skipped pack looks like (its
+ * columns are not read).  mode 1: after POA #1 (qualities required; reads corrected), mode 2: after POA #2 / #3 (pack consensus).
+ * Only min_occ, gap_occ, err_ratio and vote_order of params are read. */
+typedef struct {
+    uint32_t n_packs;
+    const uint32_t *pack_first;   /* [n_packs+1] row range of each pack, pack_first[0] == 0 */
+    const uint32_t *width;        /* [n_packs]   MSA columns */
+    const uint64_t *off;          /* [n_rows+1]  base range of each row, off[0] == 0 */
+    const uint8_t *seq;           /* bases of all rows back to back */
+    const uint8_t *qual;          /* their quality bytes; may be NULL in mode 2 */
+    const uint32_t *col;          /* [n_bases]   MSA column of every base */
+} rattle_debug_msa;
+
+typedef struct {
+    uint32_t n_packs, n_rows;
+    int mode;
+    uint64_t n_cols;              /* sum of the widths */
+    uint64_t *moff;               /* [n_packs] byte offset of the pack's rows x width matrix (a multiple of 16) */
+    uint64_t *coff;               /* [n_packs] offset of the pack's columns in the per-column arrays */
+    int32_t *rfirst, *rlast;      /* [n_rows]  voting window after fix_msa_ends: first / last column, width / -1 if the row was blanked
+                                               (rows of a pack of width 0: 0 / -1) */
+    uint32_t *tfront, *tback;     /* [n_rows]  bases fix_msa_ends erased at the front / at the back (mode 1, else NULL) */
+    uint32_t *olen;               /* [n_rows]  length of the corrected read (mode 1, else NULL) */
+    uint64_t *out_off;            /* [n_rows+1] corrected reads back to back (mode 1, else NULL) */
+    uint8_t *out_seq, *out_qual;
+    uint8_t *cons;                /* [n_cols]  column winner ('-' where nothing voted) */
+    uint8_t *flag;                /* [n_cols]  bit 0: winner's share >= gap_occ, bit 1: >= min_occ (mode 1, else NULL) */
+    uint8_t *sym;                 /* [n_cols]  phred_symbol of the winner's mean error (mode 1; meaningful where the winner is a base) */
+    double *err;                  /* [n_cols]  the winner's mean error (mode 1; meaningful where the winner is a base) */
+    uint32_t *cons_len;           /* [n_packs] length of the pack consensus (mode 2, else NULL) */
+    uint8_t *consensus;           /* [n_cols]  the winners without gaps, cons_len[p] bytes at coff[p] (mode 2, else NULL) */
+} rattle_debug_post;
+
+int rattle_hip_debug_post_msa(rattle_ctx *ctx, const rattle_correct_params *params, int mode /* 1 | 2 */, const rattle_debug_msa *in,
+                              rattle_debug_post **out);
+void rattle_hip_debug_post_msa_free(rattle_debug_post *p);
+
 /* ------------------------------------------------------------------------------------
  * Per-kernel timing measured with HIP events on the stream the kernels run on.
  * kernel: 0 kmer_extract, 1 bv_filter, 2 pair_score, 3 poa_align, 4 post_msa.  Accumulated since

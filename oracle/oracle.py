@@ -151,6 +151,42 @@ class Oracle(_Lib):
         return out_rows, out_s, out_q
 
 
+    def post_msa(self, rows, quals=None, min_occ=0.3, gap_occ=0.3, err_ratio=30.0, mode=1):
+        """The post-MSA half of one pack on explicit MSA rows (orc_post_msa): fix_msa_ends, the column vote and, in mode 1,
+        the per-read correction.  rows: bytes of equal length; quals: per row the quality bytes of its bases (None in mode 2).
+        Returns a dict: rows (fixed), rfirst / rlast, erased [n, 2] (bases erased by phase 1 / 2), winner (bytes), occ, total_occ,
+        err_bits (uint64), sym (mode 1, 0 where the winner is '-'), reads [(seq, qual)] and empty (mode 1), consensus."""
+        n, width = len(rows), len(rows[0])
+        assert n > 0 and all(len(r) == width for r in rows) and mode in (1, 2)
+        qoff = np.zeros(n + 1, np.uint64)
+        qcat = None
+        if quals is not None:
+            assert all(len(q) == width - r.count(b"-") for q, r in zip(quals, rows))
+            qoff[1:] = np.cumsum([len(q) for q in quals], dtype=np.uint64)
+            qcat = b"".join(quals)
+        else:
+            assert mode == 2
+        cells = n * width + 1
+        rb = C.create_string_buffer(cells); os_ = C.create_string_buffer(cells); oq = C.create_string_buffer(cells)
+        win = C.create_string_buffer(width + 1); cons = C.create_string_buffer(width + 1)
+        rfirst = np.zeros(n, np.int32); rlast = np.zeros(n, np.int32); erased = np.zeros((n, 2), np.uint32)
+        occ = np.zeros(width, np.int32); tot = np.zeros(width, np.int32); err = np.zeros(width, np.uint64)
+        sym = np.zeros(width, np.uint8); ooff = np.zeros(n + 1, np.uint64); empty = np.zeros(n, np.uint8)
+        clen = C.c_uint32()
+        self.lib.orc_post_msa(C.c_char_p(b"".join(rows)), C.c_uint32(n), C.c_uint32(width), C.c_char_p(qcat), _ptr(qoff, C.c_uint64),
+                              C.c_double(min_occ), C.c_double(gap_occ), C.c_double(err_ratio), C.c_int(mode), rb,
+                              _ptr(rfirst, C.c_int32), _ptr(rlast, C.c_int32), _ptr(erased, C.c_uint32), win, _ptr(occ, C.c_int32),
+                              _ptr(tot, C.c_int32), _ptr(err, C.c_uint64), _ptr(sym, C.c_uint8), os_, oq, _ptr(ooff, C.c_uint64),
+                              _ptr(empty, C.c_uint8), cons, C.byref(clen))
+        out = {"rows": [rb.raw[i * width:(i + 1) * width] for i in range(n)], "rfirst": rfirst, "rlast": rlast, "erased": erased,
+               "winner": win.raw[:width], "occ": occ, "total_occ": tot, "err_bits": err, "consensus": cons.raw[:clen.value]}
+        if mode == 1:
+            out["sym"] = sym
+            out["empty"] = empty.astype(bool)
+            out["reads"] = [(os_.raw[int(ooff[i]):int(ooff[i + 1])], oq.raw[int(ooff[i]):int(ooff[i + 1])]) for i in range(n)]
+        return out
+
+
 class Ref(_Lib):
     """The real reference TUs (oracle/_ref/libref.so), when built."""
 

@@ -139,6 +139,61 @@ void orc_fix_msa_ends(char *rows, uint32_t n, uint32_t width, char *seqs, char *
     }
 }
 
+// The post-MSA half of one pack (correct.cpp:407-409 after POA #1, :438-445 / :533-535 after POA #2 / #3) on an explicit MSA:
+// fix_msa_ends, generate_consensus_vector and, in mode 1, correct_read_pack.  rows: n rows of `width` bytes; quals: the quality
+// bytes of every row's bases at qoff[] (NULL in mode 2: 'K', what the reference gives a consensus).  Out: the fixed rows, every
+// row's window (first / last non-gap column, width / -1 if none) and the bases erased per phase [2n]; per column the winner, its
+// occ and total_occ, the bits of its mean error and (mode 1, winner not '-') the phred_symbol of it; the corrected reads
+// (mode 1; out_off [n+1], a read that came out empty is flagged) and the consensus.  The vote order is set_cv_order's.
+void orc_post_msa(const char *rows, uint32_t n, uint32_t width, const char *quals, const uint64_t *qoff, double min_occ, double gap_occ,
+                  double err_ratio, int mode, char *rows_out, int32_t *rfirst, int32_t *rlast, uint32_t *erased, char *winner,
+                  int32_t *occ, int32_t *total_occ, uint64_t *err_bits, uint8_t *sym, char *out_seq, char *out_qual, uint64_t *out_off,
+                  uint8_t *empty, char *cons, uint32_t *cons_len) {
+    read_set_t rs(n);
+    msa_t msa(n);
+    for (uint32_t i = 0; i < n; ++i) {
+        msa[i].assign(rows + (size_t)i * width, width);
+        for (char c : msa[i]) if (c != '-') rs[i].seq += c;
+        rs[i].header = std::to_string(i);
+        rs[i].ann = "+";
+        rs[i].quality = quals ? std::string(quals + qoff[i], quals + qoff[i + 1]) : std::string(rs[i].seq.size(), 'K');
+    }
+    std::vector<std::array<uint32_t, 2>> er;
+    fix_msa_ends(rs, msa, &er);
+    for (uint32_t i = 0; i < n; ++i) {
+        memcpy(rows_out + (size_t)i * width, msa[i].data(), width);
+        const size_t a = msa[i].find_first_not_of('-'), b = msa[i].find_last_not_of('-');
+        rfirst[i] = a == std::string::npos ? (int32_t)width : (int32_t)a;
+        rlast[i] = b == std::string::npos ? -1 : (int32_t)b;
+        erased[2 * i] = er[i][0]; erased[2 * i + 1] = er[i][1];
+    }
+    consensus_vector_t cv = generate_consensus_vector(rs, msa);
+    for (size_t k = 0; k < cv.consensus_nt.size(); ++k) {
+        const char w = cv.consensus_nt[k];
+        const pos_info_t &pi = cv.nt_info[k][cv_slot(w)];
+        winner[k] = w; occ[k] = pi.occ; total_occ[k] = pi.total_occ;
+        memcpy(&err_bits[k], &pi.err, 8);
+        sym[k] = mode == 1 && w != '-' ? (uint8_t)phred_symbol(pi.err) : 0;
+    }
+    const std::string c = strip_gaps(cv.consensus_nt);
+    memcpy(cons, c.data(), c.size());
+    *cons_len = (uint32_t)c.size();
+    if (mode != 1) return;
+    corrected_pack_t cp = correct_read_pack(rs, msa, min_occ, gap_occ, err_ratio);
+    std::vector<const read_t *> got(n, nullptr);
+    for (const read_t &r : cp.reads) got[std::stoul(r.header)] = &r;
+    uint64_t at = 0;
+    for (uint32_t i = 0; i < n; ++i) {
+        out_off[i] = at;
+        empty[i] = got[i] ? 0 : 1;
+        if (!got[i]) continue;
+        memcpy(out_seq + at, got[i]->seq.data(), got[i]->seq.size());
+        memcpy(out_qual + at, got[i]->quality.data(), got[i]->seq.size());
+        at += got[i]->seq.size();
+    }
+    out_off[n] = at;
+}
+
 void orc_free(void *p) { free(p); }
 
 // AVX2 int16 row fill of the POA matrices (orc_poa.hpp); returns whether this CPU can run it.

@@ -27,7 +27,9 @@ inline char phred_symbol(double p) { return (char)(-10 * log10(p) + 33); }      
 inline double phred_err(char c) { double q = c - 33; return pow(10.0, -q / 10.0); }   // utils.cpp:10-13
 
 // correct.cpp:32-92 (literal control flow, including the plain std::reverse of seq).
-inline void fix_msa_ends(read_set_t &reads, msa_t &aln) {
+// erased (optional, tests): per row, the bases erased in the first phase (from the left end) and in the second (from the right).
+inline void fix_msa_ends(read_set_t &reads, msa_t &aln, std::vector<std::array<uint32_t, 2>> *erased = nullptr) {
+    if (erased) erased->assign(aln.size(), std::array<uint32_t, 2>{{0, 0}});
     for (size_t i = 0; i < aln.size(); ++i) {
         std::string &row = aln[i];
         bool reversed = false;
@@ -53,6 +55,7 @@ inline void fix_msa_ends(read_set_t &reads, msa_t &aln) {
                     for (size_t j = pos; j < end_pos; ++j) row[j] = '-';
                     reads[i].quality.erase(0, sz);
                     reads[i].seq.erase(0, sz);
+                    if (erased) (*erased)[i][reversed ? 1 : 0] += (uint32_t)sz;
                     pos = end_pos;
                 } else {
                     std::reverse(row.begin(), row.end());

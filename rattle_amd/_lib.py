@@ -74,6 +74,22 @@ class DebugEval(C.Structure):
                 ("count_pass", C.c_int), ("filter_launches", C.c_uint64), ("oversize_pairs", C.c_uint64)]
 
 
+class DebugMsa(C.Structure):
+    _fields_ = [("n_packs", C.c_uint32), ("pack_first", C.POINTER(C.c_uint32)), ("width", C.POINTER(C.c_uint32)),
+                ("off", C.POINTER(C.c_uint64)), ("seq", C.POINTER(C.c_uint8)), ("qual", C.POINTER(C.c_uint8)),
+                ("col", C.POINTER(C.c_uint32))]
+
+
+class DebugPost(C.Structure):
+    _fields_ = [("n_packs", C.c_uint32), ("n_rows", C.c_uint32), ("mode", C.c_int), ("n_cols", C.c_uint64),
+                ("moff", C.POINTER(C.c_uint64)), ("coff", C.POINTER(C.c_uint64)), ("rfirst", C.POINTER(C.c_int32)),
+                ("rlast", C.POINTER(C.c_int32)), ("tfront", C.POINTER(C.c_uint32)), ("tback", C.POINTER(C.c_uint32)),
+                ("olen", C.POINTER(C.c_uint32)), ("out_off", C.POINTER(C.c_uint64)), ("out_seq", C.POINTER(C.c_uint8)),
+                ("out_qual", C.POINTER(C.c_uint8)), ("cons", C.POINTER(C.c_uint8)), ("flag", C.POINTER(C.c_uint8)),
+                ("sym", C.POINTER(C.c_uint8)), ("err", C.POINTER(C.c_double)), ("cons_len", C.POINTER(C.c_uint32)),
+                ("consensus", C.POINTER(C.c_uint8))]
+
+
 # int fn(void *user, const void *send, uint64 send_bytes, void *recv, const uint64 *recv_bytes)
 ALLGATHERV_FN = C.CFUNCTYPE(C.c_int, C.c_void_p, C.c_void_p, C.c_uint64, C.c_void_p, C.POINTER(C.c_uint64))
 
@@ -104,6 +120,8 @@ SIGNATURES = {
     "rattle_hip_debug_phred_symbol": (C.c_int, [C.c_double, _P(C.c_int), _P(C.c_int)]),
     "rattle_hip_debug_evaluate": (C.c_int, [C.c_void_p, _P(ClusterParams), C.c_int, _P(DebugRect), C.c_uint32, _P(_P(DebugEval))]),
     "rattle_hip_debug_evaluate_free": (None, [_P(DebugEval)]),
+    "rattle_hip_debug_post_msa": (C.c_int, [C.c_void_p, _P(CorrectParams), C.c_int, _P(DebugMsa), _P(_P(DebugPost))]),
+    "rattle_hip_debug_post_msa_free": (None, [_P(DebugPost)]),
     "rattle_hip_stage_reads": (C.c_int, [C.c_void_p, _u8p, _u8p, _u64p, C.c_uint32]),
     "rattle_hip_unstage_reads": (C.c_int, [C.c_void_p]),
     "rattle_hip_cluster_unsorted": (C.c_int, [C.c_void_p, _u8p, _u64p, C.c_uint32, C.c_int, _P(ClusterParams),

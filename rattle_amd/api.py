@@ -52,6 +52,18 @@ class Clusters:
         return out
 
 
+def msa_pack(rows: Sequence[bytes], quals: Optional[Sequence[bytes]] = None):
+    """MSA rows (bytes of one length, '-' for gaps) as a pack of Context.debug_post_msa: (width, sequences, the MSA column of
+    every base, qualities)."""
+    width = len(rows[0]) if len(rows) else 0
+    assert all(len(r) == width for r in rows)
+    mat = np.frombuffer(b"".join(rows), np.uint8).reshape(len(rows), width)
+    cols = [np.nonzero(m != ord("-"))[0].astype(np.uint32) for m in mat]
+    seqs = [m[c].tobytes() for m, c in zip(mat, cols)]
+    assert quals is None or all(len(q) == len(s) for q, s in zip(quals, seqs))
+    return width, seqs, cols, None if quals is None else list(quals)
+
+
 def correct_params(min_occ=0.3, gap_occ=0.3, err_ratio=30.0, split=200, min_reads=5, n_threads=0, vote_order: bytes = b"",
                    pack_order=None, max_pack_cells=0):
     """rattle_correct_params; pack_order = {cluster: [pack indices in the order their consensi enter POA #3]}.
@@ -481,6 +493,58 @@ class Context:
                "count_pass": {p for b, p in ((1, "seed"), (2, "search"), (4, "index")) if D.count_pass & b},
                "filter_launches": int(D.filter_launches), "oversize_pairs": int(D.oversize_pairs)}
         self.lib.rattle_hip_debug_evaluate_free(out)
+        return res
+
+    def debug_post_msa(self, packs, mode: int, min_occ=0.3, gap_occ=0.3, err_ratio=30.0, vote_order: bytes = b""):
+        """Kernel D alone on given MSAs (rattle_hip_debug_post_msa, a test hook), all packs in one launch.  packs: a list of
+        (width, sequences, columns per sequence, qualities per sequence or None), see msa_pack.  Returns a list with one dict per
+        pack: moff, coff, rfirst, rlast, cons (bytes, one per column); mode 1: tfront, tback, olen, reads [(seq, qual)], flag, sym,
+        err (float64; .view(uint64) for the bits); mode 2: consensus (bytes)."""
+        first = np.zeros(len(packs) + 1, np.uint32)
+        first[1:] = np.cumsum([len(p[1]) for p in packs])
+        width = np.array([p[0] for p in packs] + [0], np.uint32)
+        seqs = [s for p in packs for s in p[1]]
+        cat, off = pack_reads(seqs)
+        col = np.concatenate([np.asarray(c, np.uint32) for p in packs for c in p[2]] + [np.zeros(1, np.uint32)])
+        assert len(col) == len(cat) + 1, "one column per base"
+        have_q = [p[3] is not None for p in packs]
+        qcat = None
+        if any(have_q):
+            assert all(have_q), "qualities for every pack or for none"
+            qcat, qoff = pack_reads([q for p in packs for q in p[3]])
+            assert np.array_equal(off, qoff), "sequence and quality lengths differ"
+        M = _lib.DebugMsa(len(packs), _ptr(first, C.c_uint32), _ptr(width, C.c_uint32), _ptr(off, C.c_uint64),
+                          _ptr(cat, C.c_uint8) if len(cat) else None, _ptr(qcat, C.c_uint8) if qcat is not None and len(qcat) else None,
+                          _ptr(col, C.c_uint32))
+        P, _ = correct_params(min_occ, gap_occ, err_ratio, vote_order=vote_order)
+        out = C.POINTER(_lib.DebugPost)()
+        check(self.lib.rattle_hip_debug_post_msa(self.h, C.byref(P), mode, C.byref(M), C.byref(out)))
+        D = out.contents
+
+        def arr(ptr, n):
+            return np.ctypeslib.as_array(ptr, (max(int(n), 1),))[:int(n)].copy()
+
+        n, ncol, npk = D.n_rows, D.n_cols, D.n_packs
+        moff, coff = arr(D.moff, npk), arr(D.coff, npk)
+        rfirst, rlast, cons = arr(D.rfirst, n), arr(D.rlast, n), arr(D.cons, ncol)
+        if mode == 1:
+            tfront, tback, olen, ooff = arr(D.tfront, n), arr(D.tback, n), arr(D.olen, n), arr(D.out_off, n + 1)
+            oseq, oqual = arr(D.out_seq, ooff[n]).tobytes(), arr(D.out_qual, ooff[n]).tobytes()
+            flag, sym, err = arr(D.flag, ncol), arr(D.sym, ncol), arr(D.err, ncol)
+        else:
+            clen, consensus = arr(D.cons_len, npk), arr(D.consensus, ncol)
+        self.lib.rattle_hip_debug_post_msa_free(out)
+        res = []
+        for p in range(npk):
+            a, b = int(first[p]), int(first[p + 1])
+            c0, c1 = int(coff[p]), int(coff[p]) + int(width[p])
+            d = {"moff": int(moff[p]), "coff": c0, "rfirst": rfirst[a:b], "rlast": rlast[a:b], "cons": cons[c0:c1].tobytes()}
+            if mode == 1:
+                d.update(tfront=tfront[a:b], tback=tback[a:b], olen=olen[a:b], flag=flag[c0:c1], sym=sym[c0:c1], err=err[c0:c1],
+                         reads=[(oseq[int(ooff[q]):int(ooff[q + 1])], oqual[int(ooff[q]):int(ooff[q + 1])]) for q in range(a, b)])
+            else:
+                d["consensus"] = consensus[c0:c0 + int(clen[p])].tobytes()
+            res.append(d)
         return res
 
     def kernel_stats(self, kernel: int):

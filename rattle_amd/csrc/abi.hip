@@ -566,6 +566,41 @@ void rattle_hip_debug_evaluate_free(rattle_debug_eval *e) {
     free(e);
 }
 
+int rattle_hip_debug_post_msa(rattle_ctx *c, const rattle_correct_params *P, int mode, const rattle_debug_msa *in, rattle_debug_post **out) {
+    if (!c || !P || !in || !out || !in->pack_first || !in->off || (in->n_packs && !in->width)) { set_error("null argument"); return RATTLE_ERR_ARG; }
+    *out = nullptr;
+    if (mode != 1 && mode != 2) { set_error("mode must be 1 (after POA #1: correction) or 2 (after POA #2 / #3: consensus)"); return RATTLE_ERR_ARG; }
+    const uint32_t np = in->n_packs;
+    if (in->pack_first[0] != 0 || in->off[0] != 0) { set_error("pack_first and off must start at 0"); return RATTLE_ERR_ARG; }
+    for (uint32_t p = 0; p < np; ++p) if (in->pack_first[p + 1] < in->pack_first[p]) { set_error("pack_first decreases"); return RATTLE_ERR_ARG; }
+    const uint32_t n = in->pack_first[np];
+    for (uint32_t q = 0; q < n; ++q) if (in->off[q + 1] < in->off[q]) { set_error("off decreases"); return RATTLE_ERR_ARG; }
+    if (in->off[n] && (!in->seq || !in->col)) { set_error("null argument"); return RATTLE_ERR_ARG; }
+    if (mode == 1 && in->off[n] && !in->qual) { set_error("mode 1 needs the qualities"); return RATTLE_ERR_ARG; }
+    for (uint32_t p = 0; p < np; ++p) {
+        const uint32_t W = in->width[p];
+        if (W == 0) continue;                                    // a skipped pack: its columns are never read
+        if ((uint64_t)(in->pack_first[p + 1] - in->pack_first[p]) * W > (1ull << 32)) { set_error("pack too large for the test hook"); return RATTLE_ERR_ARG; }
+        for (uint32_t q = in->pack_first[p]; q < in->pack_first[p + 1]; ++q)
+            for (uint64_t b = in->off[q]; b < in->off[q + 1]; ++b) {
+                if (!strchr("ACGTU", in->seq[b]) || !in->seq[b]) { set_error("row " + std::to_string(q) + ": a base other than A, C, G, T, U"); return RATTLE_ERR_ARG; }
+                if (in->col[b] >= W) { set_error("row " + std::to_string(q) + ": column " + std::to_string(in->col[b]) + " is not below the pack's width " + std::to_string(W)); return RATTLE_ERR_ARG; }
+                if (b > in->off[q] && in->col[b] <= in->col[b - 1]) { set_error("row " + std::to_string(q) + ": columns are not strictly increasing"); return RATTLE_ERR_ARG; }
+            }
+    }
+    RT_TRY(use_device(c));
+    int rc = debug_post_msa(c, P, mode, in, out);
+    if (rc != 0 && *out) { rattle_hip_debug_post_msa_free(*out); *out = nullptr; }
+    return rc;
+}
+
+void rattle_hip_debug_post_msa_free(rattle_debug_post *d) {
+    if (!d) return;
+    free(d->moff); free(d->coff); free(d->rfirst); free(d->rlast); free(d->tfront); free(d->tback); free(d->olen); free(d->out_off);
+    free(d->out_seq); free(d->out_qual); free(d->cons); free(d->flag); free(d->sym); free(d->err); free(d->cons_len); free(d->consensus);
+    free(d);
+}
+
 int rattle_hip_kernel_stats(rattle_ctx *c, int kernel, double *ms, uint64_t *launches, uint64_t *bytes) {
     if (!c || kernel < 0 || kernel >= K_COUNT) { set_error("bad kernel id"); return RATTLE_ERR_ARG; }
     if (ms) *ms = c->stats[kernel].ms;

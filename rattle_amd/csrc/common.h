@@ -412,4 +412,7 @@ int cluster_driver(rattle_ctx *ctx, const rattle_cluster_params *P, const uint32
 int debug_evaluate(rattle_ctx *ctx, const rattle_cluster_params *P, int count_mode, const rattle_debug_rect *R, uint32_t n_rects,
                    rattle_debug_eval **out);
 
+// correct_driver.hip
+int debug_post_msa(rattle_ctx *ctx, const rattle_correct_params *P, int mode, const rattle_debug_msa *in, rattle_debug_post **out);
+
 }  // namespace rattle

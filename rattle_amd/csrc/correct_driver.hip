@@ -221,6 +221,48 @@ static void make_room(rattle_ctx *ctx, uint64_t bytes) {
     ctx->poa_arena = nullptr; ctx->poa_arena_bytes = 0;
 }
 
+// Kernel D over a stage whose sequences (S.seq, S.qual in mode 1, S.d_off), packs (S.first, S.d_first), MSA columns (S.col) and
+// widths (S.width, S.d_width) are in place: the layout of the row matrices and per-column arrays, their buffers, the launch.
+// The results stay on the device (S.rowc / S.rowq at S.moff, the per-column arrays at S.coff, the per-sequence arrays).
+int run_post_msa(rattle_ctx *ctx, stage &S, int mode, const rattle_correct_params *P, const char *order) {
+    hipStream_t st = ctx->stream;
+    const uint32_t n = S.n(), np = S.n_packs();
+    // layout of the row matrices and per-column arrays
+    S.moff.assign(np, 0); S.coff.assign(np, 0);
+    uint64_t cells = 0, cols = 0;
+    for (uint32_t p = 0; p < np; ++p) {
+        S.moff[p] = cells; S.coff[p] = cols;
+        cells += ((uint64_t)(S.first[p + 1] - S.first[p]) * S.width[p] + 15) & ~(uint64_t)15;
+        cols += S.width[p];
+    }
+    S.cells = cells; S.cols = cols;
+    phase_timer T("  stage: post-MSA kernel");
+    make_room(ctx, (mode == 1 ? 2 : 1) * (cells + 64) + 4 * (cols + 64) + 20ull * (n + 1));
+    RT_TRY(S.rowc.reserve(cells + 64)); RT_TRY(S.d_moff.reserve(np)); RT_TRY(S.d_coff.reserve(np));
+    RT_TRY(S.rfirst.reserve(n + 1)); RT_TRY(S.rlast.reserve(n + 1)); RT_TRY(S.ccons.reserve(cols + 64));
+    if (mode == 1) {
+        RT_TRY(S.rowq.reserve(cells + 64)); RT_TRY(S.tfront.reserve(n + 1)); RT_TRY(S.tback.reserve(n + 1)); RT_TRY(S.olen.reserve(n + 1));
+        RT_TRY(S.cflag.reserve(cols + 64)); RT_TRY(S.csym.reserve(cols + 64)); RT_TRY(S.cerr.reserve(cols + 8));
+    } else {
+        RT_TRY(S.cons_out.reserve(cols + 64)); RT_TRY(S.cons_len.reserve(np));
+    }
+    RT_HIP(hipMemcpyAsync(S.d_moff.p, S.moff.data(), (size_t)np * 8, hipMemcpyHostToDevice, st));
+    RT_HIP(hipMemcpyAsync(S.d_coff.p, S.coff.data(), (size_t)np * 8, hipMemcpyHostToDevice, st));
+    RT_TRY(ensure_post_constants(ctx));
+    post_args A;
+    memset(&A, 0, sizeof(A));
+    A.seq = S.seq.p; A.qual = S.qual.p; A.off = S.d_off.p; A.pack_first = S.d_first.p; A.col = S.col.p; A.width = S.d_width.p;
+    A.moff = S.d_moff.p; A.coff = S.d_coff.p; A.rowc = S.rowc.p; A.rowq = S.rowq.p; A.rfirst = S.rfirst.p; A.rlast = S.rlast.p;
+    A.tfront = S.tfront.p; A.tback = S.tback.p; A.olen = S.olen.p; A.ccons = S.ccons.p; A.cflag = S.cflag.p; A.csym = S.csym.p;
+    A.cerr = S.cerr.p; A.cons_out = S.cons_out.p; A.cons_len = S.cons_len.p; A.perr = ctx->d_perr.p; A.phred_lo = ctx->d_phred_lo.p;
+    A.exc_bits = ctx->d_exc_bits.p; A.exc_val = ctx->d_exc_val.p; A.phred_n0 = ctx->phred.n0; A.phred_cnt = (int32_t)ctx->phred.lo.size();
+    A.n_exc = (uint32_t)ctx->phred.exc_bits.size();
+    memcpy(A.order, order, 6);
+    A.min_occ = P->min_occ; A.gap_occ = P->gap_occ; A.err_ratio = P->err_ratio;
+    RT_TRY(launch_post_msa(ctx, A, np, mode));
+    return 0;
+}
+
 // gather the stage's sequences (descriptors built by the caller, dst offsets = st.off) and run POA + kernel D
 int run_stage(rattle_ctx *ctx, stage &S, const std::vector<gather_desc> &desc, const std::vector<gather_part> &parts,
               int mode, const rattle_correct_params *P, const char *order, uint64_t *counters) {
@@ -254,39 +296,7 @@ int run_stage(rattle_ctx *ctx, stage &S, const std::vector<gather_desc> &desc, c
     counters[0] += h_cnt[POA_CNT_CELLS];
     counters[1] += h_cnt[POA_CNT_SEQS];
     counters[5] += h_cnt[POA_CNT_CELLS_DONE]; counters[6] += h_cnt[POA_CNT_BAND_OK]; counters[7] += h_cnt[POA_CNT_BAND_FAIL];      // DP cells computed; alignments with a certified band / a failed certificate
-    // layout of the row matrices and per-column arrays
-    S.moff.assign(np, 0); S.coff.assign(np, 0);
-    uint64_t cells = 0, cols = 0;
-    for (uint32_t p = 0; p < np; ++p) {
-        S.moff[p] = cells; S.coff[p] = cols;
-        cells += ((uint64_t)(S.first[p + 1] - S.first[p]) * S.width[p] + 15) & ~(uint64_t)15;
-        cols += S.width[p];
-    }
-    S.cells = cells; S.cols = cols;
-    phase_timer T("  stage: post-MSA kernel");
-    make_room(ctx, (mode == 1 ? 2 : 1) * (cells + 64) + 4 * (cols + 64) + 20ull * (n + 1));
-    RT_TRY(S.rowc.reserve(cells + 64)); RT_TRY(S.d_moff.reserve(np)); RT_TRY(S.d_coff.reserve(np));
-    RT_TRY(S.rfirst.reserve(n + 1)); RT_TRY(S.rlast.reserve(n + 1)); RT_TRY(S.ccons.reserve(cols + 64));
-    if (mode == 1) {
-        RT_TRY(S.rowq.reserve(cells + 64)); RT_TRY(S.tfront.reserve(n + 1)); RT_TRY(S.tback.reserve(n + 1)); RT_TRY(S.olen.reserve(n + 1));
-        RT_TRY(S.cflag.reserve(cols + 64)); RT_TRY(S.csym.reserve(cols + 64)); RT_TRY(S.cerr.reserve(cols + 8));
-    } else {
-        RT_TRY(S.cons_out.reserve(cols + 64)); RT_TRY(S.cons_len.reserve(np));
-    }
-    RT_HIP(hipMemcpyAsync(S.d_moff.p, S.moff.data(), (size_t)np * 8, hipMemcpyHostToDevice, st));
-    RT_HIP(hipMemcpyAsync(S.d_coff.p, S.coff.data(), (size_t)np * 8, hipMemcpyHostToDevice, st));
-    post_args A;
-    memset(&A, 0, sizeof(A));
-    A.seq = S.seq.p; A.qual = S.qual.p; A.off = S.d_off.p; A.pack_first = S.d_first.p; A.col = S.col.p; A.width = S.d_width.p;
-    A.moff = S.d_moff.p; A.coff = S.d_coff.p; A.rowc = S.rowc.p; A.rowq = S.rowq.p; A.rfirst = S.rfirst.p; A.rlast = S.rlast.p;
-    A.tfront = S.tfront.p; A.tback = S.tback.p; A.olen = S.olen.p; A.ccons = S.ccons.p; A.cflag = S.cflag.p; A.csym = S.csym.p;
-    A.cerr = S.cerr.p; A.cons_out = S.cons_out.p; A.cons_len = S.cons_len.p; A.perr = ctx->d_perr.p; A.phred_lo = ctx->d_phred_lo.p;
-    A.exc_bits = ctx->d_exc_bits.p; A.exc_val = ctx->d_exc_val.p; A.phred_n0 = ctx->phred.n0; A.phred_cnt = (int32_t)ctx->phred.lo.size();
-    A.n_exc = (uint32_t)ctx->phred.exc_bits.size();
-    memcpy(A.order, order, 6);
-    A.min_occ = P->min_occ; A.gap_occ = P->gap_occ; A.err_ratio = P->err_ratio;
-    RT_TRY(launch_post_msa(ctx, A, np, mode));
-    return 0;
+    return run_post_msa(ctx, S, mode, P, order);
 }
 
 // Consensus stage (POA #2 of packs, POA #3 of clusters) whose input sequences come from the host: the pack
@@ -709,7 +719,92 @@ struct correct_job {
     }
 };
 
+// the vote slot order of a call: the caller's, or the reference's
+int vote_order_of(const rattle_correct_params *P, char order[8]) {
+    memset(order, 0, 8);
+    memcpy(order, P->vote_order[0] ? P->vote_order : "U-GTCA", 6);
+    for (int i = 0; i < 6; ++i)
+        if (!order[i] || !strchr("ACGTU-", order[i])) { set_error("vote_order must be a permutation of ACGTU-"); return RATTLE_ERR_ARG; }
+    return 0;
+}
+
 }  // namespace
+
+// Test hook: kernel D alone on a given MSA (sequences + the column of every base, as kernel C leaves them), through the
+// stage and the launch path of the driver (run_post_msa), and everything it wrote.  The input was validated by the caller
+// (abi.hip): columns strictly increasing and below the width in every pack of width > 0, bases in ACGTU.
+int debug_post_msa(rattle_ctx *ctx, const rattle_correct_params *P, int mode, const rattle_debug_msa *in, rattle_debug_post **out) {
+    char order[8];
+    RT_TRY(vote_order_of(P, order));
+    hipStream_t st = ctx->stream;
+    const uint32_t np = in->n_packs, n = in->pack_first[np];
+    stage S;
+    S.first.assign(in->pack_first, in->pack_first + np + 1);
+    S.off.assign(in->off, in->off + n + 1);
+    S.width.assign(in->width, in->width + np);
+    S.skipped.assign(np, 0);
+    const uint64_t total = S.off[n];
+    RT_TRY(S.seq.reserve(total + 64)); RT_TRY(S.d_off.reserve(n + 1)); RT_TRY(S.col.reserve(total + 64));
+    RT_TRY(S.d_width.reserve(np + 1)); RT_TRY(S.d_first.reserve(np + 1));
+    if (mode == 1) RT_TRY(S.qual.reserve(total + 64));
+    if (total) {
+        RT_HIP(hipMemcpyAsync(S.seq.p, in->seq, total, hipMemcpyHostToDevice, st));
+        RT_HIP(hipMemcpyAsync(S.col.p, in->col, total * 4, hipMemcpyHostToDevice, st));
+        if (mode == 1) RT_HIP(hipMemcpyAsync(S.qual.p, in->qual, total, hipMemcpyHostToDevice, st));
+    }
+    RT_HIP(hipMemcpyAsync(S.d_off.p, S.off.data(), (size_t)(n + 1) * 8, hipMemcpyHostToDevice, st));
+    RT_HIP(hipMemcpyAsync(S.d_first.p, S.first.data(), (size_t)(np + 1) * 4, hipMemcpyHostToDevice, st));
+    if (np) RT_HIP(hipMemcpyAsync(S.d_width.p, S.width.data(), (size_t)np * 4, hipMemcpyHostToDevice, st));
+    RT_TRY(run_post_msa(ctx, S, mode, P, order));
+
+    rattle_debug_post *D = (rattle_debug_post *)calloc(1, sizeof(rattle_debug_post));
+    *out = D;
+    D->n_packs = np; D->n_rows = n; D->n_cols = S.cols; D->mode = mode;
+    D->moff = result_array<uint64_t>(np); D->coff = result_array<uint64_t>(np);
+    if (np) { memcpy(D->moff, S.moff.data(), (size_t)np * 8); memcpy(D->coff, S.coff.data(), (size_t)np * 8); }
+    D->rfirst = result_array<int32_t>(n); D->rlast = result_array<int32_t>(n);
+    D->cons = result_array<uint8_t>(S.cols);
+    std::vector<uint8_t> rowc, rowq;
+    auto fetch = [st](void *dst, const void *src, size_t bytes) { return bytes ? hipMemcpyAsync(dst, src, bytes, hipMemcpyDeviceToHost, st) : hipSuccess; };
+    if (np) {
+        RT_HIP(fetch(D->rfirst, S.rfirst.p, (size_t)n * 4)); RT_HIP(fetch(D->rlast, S.rlast.p, (size_t)n * 4));
+        RT_HIP(fetch(D->cons, S.ccons.p, S.cols));
+    }
+    if (mode == 1) {
+        D->tfront = result_array<uint32_t>(n); D->tback = result_array<uint32_t>(n); D->olen = result_array<uint32_t>(n);
+        D->flag = result_array<uint8_t>(S.cols); D->sym = result_array<uint8_t>(S.cols); D->err = result_array<double>(S.cols);
+        rowc.resize(S.cells + 1); rowq.resize(S.cells + 1);
+        if (np) {
+            RT_HIP(fetch(D->tfront, S.tfront.p, (size_t)n * 4)); RT_HIP(fetch(D->tback, S.tback.p, (size_t)n * 4));
+            RT_HIP(fetch(D->olen, S.olen.p, (size_t)n * 4));
+            RT_HIP(fetch(D->flag, S.cflag.p, S.cols)); RT_HIP(fetch(D->sym, S.csym.p, S.cols)); RT_HIP(fetch(D->err, S.cerr.p, S.cols * 8));
+            RT_HIP(fetch(rowc.data(), S.rowc.p, S.cells)); RT_HIP(fetch(rowq.data(), S.rowq.p, S.cells));
+        }
+    } else {
+        D->cons_len = result_array<uint32_t>(np); D->consensus = result_array<uint8_t>(S.cols);
+        if (np) { RT_HIP(fetch(D->cons_len, S.cons_len.p, (size_t)np * 4)); RT_HIP(fetch(D->consensus, S.cons_out.p, S.cols)); }
+    }
+    RT_HIP(hipStreamSynchronize(st));
+    // a pack of width 0 (or without rows) leaves the kernel before the windows are written: reported as the empty window
+    for (uint32_t p = 0; p < np; ++p)
+        if (S.width[p] == 0) for (uint32_t q = S.first[p]; q < S.first[p + 1]; ++q) { D->rfirst[q] = 0; D->rlast[q] = -1; }
+    if (mode == 1) {
+        // the corrected read lies at the start of its row, as stage1_finish gathers it (row_of)
+        D->out_off = (uint64_t *)malloc(((size_t)n + 1) * 8);
+        uint64_t tot = 0;
+        for (uint32_t q = 0; q < n; ++q) { D->out_off[q] = tot; tot += D->olen[q]; }
+        D->out_off[n] = tot;
+        D->out_seq = result_array<uint8_t>(tot); D->out_qual = result_array<uint8_t>(tot);
+        for (uint32_t p = 0; p < np; ++p)
+            for (uint32_t q = S.first[p]; q < S.first[p + 1]; ++q) {
+                if (D->olen[q] > S.width[p]) { set_error("debug_post_msa: a corrected read is longer than its row"); return RATTLE_ERR_HIP; }
+                const uint64_t at = S.moff[p] + (uint64_t)(q - S.first[p]) * S.width[p];
+                memcpy(D->out_seq + D->out_off[q], rowc.data() + at, D->olen[q]);
+                memcpy(D->out_qual + D->out_off[q], rowq.data() + at, D->olen[q]);
+            }
+    }
+    return 0;
+}
 
 // a step of this rank's own work: not run after an earlier one failed
 #define LOCAL_TRY(call) do { if (J.local_rc == 0) RT_TRY(J.own_error(call)); } while (0)
@@ -718,9 +813,7 @@ int correct_driver(rattle_ctx *ctx, const uint8_t *seq, const uint8_t *qual, con
                    uint32_t n_clusters, const uint32_t *coff, const int32_t *mid, const uint8_t *mrev,
                    const rattle_correct_params *P, rattle_correction **out) {
     char order[8] = {0};
-    memcpy(order, P->vote_order[0] ? P->vote_order : "U-GTCA", 6);
-    for (int i = 0; i < 6; ++i)
-        if (!order[i] || !strchr("ACGTU-", order[i])) { set_error("vote_order must be a permutation of ACGTU-"); return RATTLE_ERR_ARG; }
+    RT_TRY(vote_order_of(P, order));
     rattle_correction *R = (rattle_correction *)calloc(1, sizeof(rattle_correction));
     *out = R;
     phase_timer T_all("correct: total");

@@ -195,3 +195,32 @@ def test_avx2_row_fill_gives_the_scalar_alignments(oracle):
         oracle.set_poa_simd(False)
     assert got == want
     assert got_c[:3] == want_c[:3]
+
+
+def test_post_msa_wrapper_reproduces_the_whole_path_oracle(oracle):
+    """oracle.post_msa (the post-MSA half on an explicit MSA, what tests/test_gpu_post_msa.py compares kernel D with) against the
+    pinned whole path: for one synthetic cluster of 12 reads that forms a single pack, poa_msa -> post_msa (mode 1) gives the records
+    oracle.correct writes, and the mode 2 consensus of the POA of those corrected reads (longest first, stable) is its consensus."""
+    from rattle_amd import hps, synth
+    seqs, quals, tid, _ = synth.reads(60, 2, 1, False, seed=5)
+    ids = [i for i in range(len(seqs)) if tid[i] == tid[0]][:12]
+    assert len(ids) == 12
+    seqs, quals = [seqs[i] for i in ids], [quals[i] for i in ids]
+    headers = [b"@r%d" % i for i in range(12)]
+    clusters = [((0, 0, -1), [(i, 0, -1) for i in range(12)])]
+    corrected, uncorrected, consensi, counters = oracle.correct(headers, seqs, quals, hps.encode(clusters))
+    assert counters[1] == 1                                                   # one pack
+    lines = corrected.split(b"\n")
+    want = {l.split(b",")[0]: (s, q) for l, s, q in zip(lines[0::4], lines[1::4], lines[3::4])}
+    rows, _ = oracle.poa_msa(seqs)
+    one = oracle.post_msa(rows, quals, 0.3, 0.3, 30.0, mode=1)
+    got = {headers[i]: one["reads"][i] for i in range(12) if not one["empty"][i]}
+    assert got == want and len(want) >= 10
+    assert all(r == (b"", b"") for r, e in zip(one["reads"], one["empty"]) if e)
+    assert any(s != seqs[i] for i, (s, _) in enumerate(one["reads"])), "nothing was corrected"
+    cor = sorted((r for r, e in zip(one["reads"], one["empty"]) if not e), key=lambda r: -len(r[0]))      # sort_read_set: stable
+    rows2, _ = oracle.poa_msa([s for s, _ in cor])
+    two = oracle.post_msa(rows2, None, 0.3, 0.3, 30.0, mode=2)
+    assert two["consensus"] == consensi.split(b"\n")[1] and len(two["consensus"]) > 500
+    # quality bytes do not enter the mode 2 vote
+    assert oracle.post_msa(rows2, [q for _, q in cor], 0.3, 0.3, 30.0, mode=2)["consensus"] == two["consensus"]
