@@ -260,6 +260,32 @@ int rattle_hip_correct_reads(rattle_ctx *ctx, const uint8_t *seq_concat, const u
                              const uint32_t *cluster_offsets, const int32_t *member_id, const uint8_t *member_rev,
                              const rattle_correct_params *params, rattle_correction **out);
 void rattle_hip_correction_free(rattle_correction *c);
+/* The per-read correction report: what the per-read correction (correct.cpp:196-309) did to every corrected read.  Off by default;
+ * rattle_hip_set_correction_report(ctx, 1) makes the following rattle_hip_correct_reads calls on this context launch the report form
+ * of the post-MSA kernel in stage 1, which counts, for every row of a pack over the columns of its voting window after
+ * fix_msa_ends, the branch that handled each column (nt: the row's symbol, c: the column winner):
+ *   match          nt is a base and nt == c
+ *   substituted    nt and c are different bases, the winner's share reaches min_occ and the error test passes: c is emitted
+ *   mismatch_kept  nt and c are different bases and nt is emitted
+ *   inserted       nt == '-', c is a base and its share reaches gap_occ: c is emitted
+ *   deleted        nt is a base, c == '-' and its share reaches gap_occ: nothing is emitted
+ *   gap_kept       nt is a base, c == '-' below gap_occ: nt is emitted
+ * (a gap that stays a gap is not counted).  With trim_front / trim_back, the bases fix_msa_ends erased at either end:
+ *   out_len = match + substituted + mismatch_kept + inserted + gap_kept
+ *   in_len  = trim_front + trim_back + match + substituted + mismatch_kept + deleted + gap_kept
+ * No output of correct_reads changes with the switch.  The counters travel inside the result object, behind the public struct;
+ * rattle_hip_correction_report copies them out (n == corrected.n, every array parallel to corrected.read_id; release with
+ * rattle_hip_correction_report_free).  RATTLE_ERR_STATE if the correction was made with the switch off -- or, for a result of
+ * rattle_hip_correction_gather, if ANY rank made its share with the switch off -- or is not an object of this library. */
+typedef struct {
+    uint32_t n;
+    uint32_t *in_len, *out_len, *trim_front, *trim_back;
+    uint32_t *match, *substituted, *mismatch_kept, *inserted, *deleted, *gap_kept;
+} rattle_correction_report;
+int rattle_hip_set_correction_report(rattle_ctx *ctx, int on);
+int rattle_hip_correction_report(const rattle_correction *c, rattle_correction_report **out);
+void rattle_hip_correction_report_free(rattle_correction_report *r);
+
 /* Optional: allocate the POA arena of correct_reads ahead of time (a caller can overlap the seconds a > 100 GB allocation takes
  * with reading its input).  bytes is a hint, clamped to what the device has free; correct_reads grows the arena if it must. */
 int rattle_hip_reserve_arena(rattle_ctx *ctx, uint64_t bytes);
@@ -297,7 +323,8 @@ int rattle_hip_comm_stats(rattle_ctx *ctx, uint64_t *calls, uint64_t *bytes);
  * once after rattle_hip_comm_init / rattle_hip_set_exchange, before it trusts the transport with a job. */
 int rattle_hip_comm_probe(rattle_ctx *ctx);
 /* Collective: merges the per-rank results of rattle_hip_correct_reads on `root` (*merged is NULL on the
- * other ranks).  With nranks == 1 it returns a copy. */
+ * other ranks).  With nranks == 1 it returns a copy.  The correction report travels with the records: the merged
+ * result has one (equal to the single-GPU one) if every rank's share has. */
 int rattle_hip_correction_gather(rattle_ctx *ctx, const rattle_correction *local, int root, rattle_correction **merged);
 
 /* The work list of correct_reads without a device (pack building correct.cpp:328-370 and the static
@@ -396,6 +423,8 @@ typedef struct {
     double *err;                  /* [n_cols]  the winner's mean error (mode 1; meaningful where the winner is a base) */
     uint32_t *cons_len;           /* [n_packs] length of the pack consensus (mode 2, else NULL) */
     uint8_t *consensus;           /* [n_cols]  the winners without gaps, cons_len[p] bytes at coff[p] (mode 2, else NULL) */
+    /* [n_rows] each: the counters of the correction report (mode 1 on a context with rattle_hip_set_correction_report on, else NULL) */
+    uint32_t *match, *substituted, *mismatch_kept, *inserted, *deleted, *gap_kept;
 } rattle_debug_post;
 
 int rattle_hip_debug_post_msa(rattle_ctx *ctx, const rattle_correct_params *params, int mode /* 1 | 2 */, const rattle_debug_msa *in,

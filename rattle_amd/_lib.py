@@ -80,6 +80,11 @@ class DebugMsa(C.Structure):
                 ("col", C.POINTER(C.c_uint32))]
 
 
+# the correction report (rattle_correction_report): lengths and trim counts, then kernel D's six counters
+REPORT_COUNTERS = ("match", "substituted", "mismatch_kept", "inserted", "deleted", "gap_kept")
+REPORT_FIELDS = ("in_len", "out_len", "trim_front", "trim_back") + REPORT_COUNTERS
+
+
 class DebugPost(C.Structure):
     _fields_ = [("n_packs", C.c_uint32), ("n_rows", C.c_uint32), ("mode", C.c_int), ("n_cols", C.c_uint64),
                 ("moff", C.POINTER(C.c_uint64)), ("coff", C.POINTER(C.c_uint64)), ("rfirst", C.POINTER(C.c_int32)),
@@ -87,7 +92,11 @@ class DebugPost(C.Structure):
                 ("olen", C.POINTER(C.c_uint32)), ("out_off", C.POINTER(C.c_uint64)), ("out_seq", C.POINTER(C.c_uint8)),
                 ("out_qual", C.POINTER(C.c_uint8)), ("cons", C.POINTER(C.c_uint8)), ("flag", C.POINTER(C.c_uint8)),
                 ("sym", C.POINTER(C.c_uint8)), ("err", C.POINTER(C.c_double)), ("cons_len", C.POINTER(C.c_uint32)),
-                ("consensus", C.POINTER(C.c_uint8))]
+                ("consensus", C.POINTER(C.c_uint8))] + [(f, C.POINTER(C.c_uint32)) for f in REPORT_COUNTERS]
+
+
+class CorrectionReport(C.Structure):
+    _fields_ = [("n", C.c_uint32)] + [(f, C.POINTER(C.c_uint32)) for f in REPORT_FIELDS]
 
 
 # int fn(void *user, const void *send, uint64 send_bytes, void *recv, const uint64 *recv_bytes)
@@ -134,6 +143,9 @@ SIGNATURES = {
     "rattle_hip_correct_reads": (C.c_int, [C.c_void_p, _u8p, _u8p, _u64p, C.c_uint32, C.c_uint32, _u32p, _i32p, _u8p,
                                            _P(CorrectParams), _P(_P(Correction))]),
     "rattle_hip_correction_free": (None, [_P(Correction)]),
+    "rattle_hip_set_correction_report": (C.c_int, [C.c_void_p, C.c_int]),
+    "rattle_hip_correction_report": (C.c_int, [_P(Correction), _P(_P(CorrectionReport))]),
+    "rattle_hip_correction_report_free": (None, [_P(CorrectionReport)]),
     "rattle_hip_reserve_arena": (C.c_int, [C.c_void_p, C.c_uint64]),
     "rattle_hip_set_exchange": (C.c_int, [C.c_void_p, C.c_int, C.c_int, ALLGATHERV_FN, C.c_void_p]),
     "rattle_hip_comm_unique_id": (C.c_int, [_u8p]),
@@ -169,6 +181,10 @@ def load():
         fn.argtypes = args
     _lib = lib
     return lib
+
+
+# return codes of include/rattle_hip.h
+RATTLE_OK, RATTLE_ERR_HIP, RATTLE_ERR_ARG, RATTLE_ERR_STATE = 0, -1, -2, -3
 
 
 class RattleError(RuntimeError):

@@ -82,8 +82,27 @@ def correct_params(min_occ=0.3, gap_occ=0.3, err_ratio=30.0, split=200, min_read
     return P, keep
 
 
+def correction_report(lib, ptr) -> Optional[dict]:
+    """The correction report of a library-owned rattle_correction (pointer) as a dict of uint32 arrays, one entry per record of
+    `corrected` (_lib.REPORT_FIELDS); None if the correction was made with the report off (Context.set_correction_report)."""
+    out = C.POINTER(_lib.CorrectionReport)()
+    rc = lib.rattle_hip_correction_report(ptr, C.byref(out))
+    if rc == _lib.RATTLE_ERR_STATE:
+        return None
+    check(rc)
+    n = out.contents.n
+    res = {f: np.ctypeslib.as_array(getattr(out.contents, f), (max(n, 1),))[:n].copy() for f in _lib.REPORT_FIELDS}
+    lib.rattle_hip_correction_report_free(out)
+    return res
+
+
 def unpack_correction(R) -> dict:
-    """rattle_correction -> dict of record lists (read_id, cluster_id, n_reads, seq, qual), counters, skip list."""
+    """rattle_correction (the struct or a pointer to it) -> dict of record lists (read_id, cluster_id, n_reads, seq, qual), counters,
+    skip list and, when the correction carries one, the correction report under "report" (a dict of uint32 arrays parallel to
+    "corrected").  The report lives behind the library's own object, so it is found for `ptr.contents` of a result the library
+    returned, not for a copy of the struct."""
+    if hasattr(R, "contents"):
+        R = R.contents
     def unpack(S):
         n = S.n
         o = np.ctypeslib.as_array(S.off, (n + 1,)).copy()
@@ -103,8 +122,12 @@ def unpack_correction(R) -> dict:
         for i in range(K.n):
             skipped.append({"cluster": int(K.cluster_id[i]), "pack": int(K.pack[i]), "stage": int(K.stage[i]),
                             "reads": [int(x) for x in rid[int(ro[i]):int(ro[i + 1])]]})
-    return {"corrected": unpack(R.corrected), "uncorrected": unpack(R.uncorrected), "consensi": unpack(R.consensi),
-            "counters": np.array(list(R.counters), dtype=np.uint64), "skipped": skipped}
+    res = {"corrected": unpack(R.corrected), "uncorrected": unpack(R.uncorrected), "consensi": unpack(R.consensi),
+           "counters": np.array(list(R.counters), dtype=np.uint64), "skipped": skipped}
+    report = correction_report(_lib.load(), C.pointer(R))
+    if report is not None:
+        res["report"] = report
+    return res
 
 
 def correction_digest(R) -> int:
@@ -137,6 +160,18 @@ class CorrectionHandle:
 
     def digest(self):
         return None if self.ptr is None else correction_digest(self.ptr.contents)
+
+    def report(self):
+        """The per-read correction report: a dict of uint32 arrays parallel to the corrected records (in_len, out_len, trim_front,
+        trim_back, match, substituted, mismatch_kept, inserted, deleted, gap_kept).  Raises if the correction was made with the
+        report off (Context.set_correction_report)."""
+        if self.ptr is None:
+            raise _lib.RattleError("no correction on this rank")
+        lib = self.lib or _lib.load()
+        res = correction_report(lib, self.ptr)
+        if res is None:
+            raise _lib.RattleError(f"librattle_hip error {_lib.RATTLE_ERR_STATE}: {lib.rattle_hip_last_error().decode()}")
+        return res
 
     def host_bytes(self):
         """bases + qualities held by the three read sets (what free() gives back to the OS)"""
@@ -181,6 +216,10 @@ class Context:
             self.close()
         except Exception:
             pass
+
+    def set_correction_report(self, on: bool):
+        """Switch the per-read correction report of the following correct_* / debug_post_msa calls on or off (off by default)."""
+        check(self.lib.rattle_hip_set_correction_report(self.h, int(bool(on))))
 
     # a3
     def load_reads(self, seqs: Sequence[bytes], k: int, both_strands: bool):
@@ -499,7 +538,8 @@ class Context:
         """Kernel D alone on given MSAs (rattle_hip_debug_post_msa, a test hook), all packs in one launch.  packs: a list of
         (width, sequences, columns per sequence, qualities per sequence or None), see msa_pack.  Returns a list with one dict per
         pack: moff, coff, rfirst, rlast, cons (bytes, one per column); mode 1: tfront, tback, olen, reads [(seq, qual)], flag, sym,
-        err (float64; .view(uint64) for the bits); mode 2: consensus (bytes)."""
+        err (float64; .view(uint64) for the bits) and, with set_correction_report on, the six per-row counters match, substituted,
+        mismatch_kept, inserted, deleted, gap_kept; mode 2: consensus (bytes)."""
         first = np.zeros(len(packs) + 1, np.uint32)
         first[1:] = np.cumsum([len(p[1]) for p in packs])
         width = np.array([p[0] for p in packs] + [0], np.uint32)
@@ -531,6 +571,7 @@ class Context:
             tfront, tback, olen, ooff = arr(D.tfront, n), arr(D.tback, n), arr(D.olen, n), arr(D.out_off, n + 1)
             oseq, oqual = arr(D.out_seq, ooff[n]).tobytes(), arr(D.out_qual, ooff[n]).tobytes()
             flag, sym, err = arr(D.flag, ncol), arr(D.sym, ncol), arr(D.err, ncol)
+            counters = {f: arr(getattr(D, f), n) for f in _lib.REPORT_COUNTERS if getattr(D, f)}
         else:
             clen, consensus = arr(D.cons_len, npk), arr(D.consensus, ncol)
         self.lib.rattle_hip_debug_post_msa_free(out)
@@ -542,6 +583,7 @@ class Context:
             if mode == 1:
                 d.update(tfront=tfront[a:b], tback=tback[a:b], olen=olen[a:b], flag=flag[c0:c1], sym=sym[c0:c1], err=err[c0:c1],
                          reads=[(oseq[int(ooff[q]):int(ooff[q + 1])], oqual[int(ooff[q]):int(ooff[q + 1])]) for q in range(a, b)])
+                d.update({f: v[a:b] for f, v in counters.items()})
             else:
                 d["consensus"] = consensus[c0:c0 + int(clen[p])].tobytes()
             res.append(d)

@@ -8,6 +8,7 @@
 #include <unistd.h>
 
 #include <memory>
+#include <unordered_set>
 
 #include "common.h"
 
@@ -51,6 +52,43 @@ __attribute__((constructor)) static void settle_hw_queues() {
 int hw_queues() { return g_hw_queues; }
 
 void dev_free(void *p) { if (p) (void)hipFree(p); }
+
+// ---- result objects of `correct`: the public struct at the head of a box that also holds the correction report (common.h)
+const char *const rep_names[REP_FIELDS] = {"in_len", "out_len", "trim_front", "trim_back", "match", "substituted", "mismatch_kept", "inserted", "deleted", "gap_kept"};
+namespace {
+std::mutex g_box_mu;
+std::unordered_set<const rattle_correction *> &boxes() { static std::unordered_set<const rattle_correction *> s; return s; }
+}  // namespace
+
+rattle_correction *new_correction() {
+    correction_box *B = (correction_box *)calloc(1, sizeof(correction_box));
+    std::lock_guard<std::mutex> g(g_box_mu);
+    boxes().insert(&B->pub);
+    return &B->pub;
+}
+
+correction_box *box_of(const rattle_correction *c) {
+    std::lock_guard<std::mutex> g(g_box_mu);
+    return c && boxes().count(c) ? (correction_box *)c : nullptr;
+}
+
+void alloc_report(correction_box *B, size_t n) {
+    for (int f = 0; f < REP_FIELDS; ++f) { free(B->rep[f]); B->rep[f] = (uint32_t *)calloc(std::max<size_t>(1, n), 4); }
+    B->has_report = true;
+}
+
+void print_report_totals(const rattle_correction *c, const char *what) {
+    static const bool enabled = getenv("RATTLE_TIMING") != nullptr;
+    const correction_box *B = enabled ? box_of(c) : nullptr;
+    if (!B || !B->has_report) return;
+    std::string line = std::string("[rattle] ") + what + ":";
+    for (int f = REP_MATCH; f < REP_FIELDS; ++f) {
+        uint64_t tot = 0;
+        for (uint32_t i = 0; i < c->corrected.n; ++i) tot += B->rep[f][i];
+        line += std::string(" ") + rep_names[f] + " " + std::to_string(tot);
+    }
+    fprintf(stderr, "%s (%u reads)\n", line.c_str(), c->corrected.n);
+}
 
 }  // namespace rattle
 
@@ -518,9 +556,48 @@ static void free_set(rattle_read_set &s) {
 
 void rattle_hip_correction_free(rattle_correction *r) {
     if (!r) return;
+    if (correction_box *B = box_of(r)) {
+        for (int f = 0; f < REP_FIELDS; ++f) free(B->rep[f]);
+        std::lock_guard<std::mutex> g(g_box_mu);
+        boxes().erase(r);
+    }
     free_set(r->corrected); free_set(r->uncorrected); free_set(r->consensi);
     free(r->skipped.cluster_id); free(r->skipped.pack); free(r->skipped.stage); free(r->skipped.read_off); free(r->skipped.read_id);
     free(r->corrected_pack); free(r->uncorrected_pack);
+    free(r);
+}
+
+int rattle_hip_set_correction_report(rattle_ctx *c, int on) {
+    if (!c) { set_error("null ctx"); return RATTLE_ERR_ARG; }
+    c->correction_report = on != 0;
+    return 0;
+}
+
+int rattle_hip_correction_report(const rattle_correction *c, rattle_correction_report **out) {
+    if (out) *out = nullptr;
+    if (!c || !out) { set_error("null argument"); return RATTLE_ERR_ARG; }
+    const correction_box *B = box_of(c);
+    if (!B || !B->has_report) {
+        set_error("this correction carries no report: rattle_hip_set_correction_report(ctx, 1) comes before rattle_hip_correct_reads, on every rank of a sharded job");
+        return RATTLE_ERR_STATE;
+    }
+    rattle_correction_report *R = (rattle_correction_report *)calloc(1, sizeof(rattle_correction_report));
+    const size_t n = c->corrected.n;
+    R->n = (uint32_t)n;
+    uint32_t **dst[REP_FIELDS] = {&R->in_len, &R->out_len, &R->trim_front, &R->trim_back, &R->match, &R->substituted, &R->mismatch_kept,
+                                  &R->inserted, &R->deleted, &R->gap_kept};
+    for (int f = 0; f < REP_FIELDS; ++f) {
+        *dst[f] = (uint32_t *)malloc(std::max<size_t>(1, n) * 4);
+        if (n) memcpy(*dst[f], B->rep[f], n * 4);
+    }
+    *out = R;
+    return 0;
+}
+
+void rattle_hip_correction_report_free(rattle_correction_report *r) {
+    if (!r) return;
+    free(r->in_len); free(r->out_len); free(r->trim_front); free(r->trim_back); free(r->match); free(r->substituted);
+    free(r->mismatch_kept); free(r->inserted); free(r->deleted); free(r->gap_kept);
     free(r);
 }
 
@@ -598,6 +675,7 @@ void rattle_hip_debug_post_msa_free(rattle_debug_post *d) {
     if (!d) return;
     free(d->moff); free(d->coff); free(d->rfirst); free(d->rlast); free(d->tfront); free(d->tback); free(d->olen); free(d->out_off);
     free(d->out_seq); free(d->out_qual); free(d->cons); free(d->flag); free(d->sym); free(d->err); free(d->cons_len); free(d->consensus);
+    free(d->match); free(d->substituted); free(d->mismatch_kept); free(d->inserted); free(d->deleted); free(d->gap_kept);
     free(d);
 }
 

@@ -262,7 +262,26 @@ struct post_args {
     uint32_t n_exc;
     uint8_t order[8];                   // vote slot order
     double min_occ, gap_occ, err_ratio;
+    uint32_t *rep;                      // report form of MODE 1 (else null): REP_KERNEL counters per sequence, counter f of sequence q at rep[f * rep_stride + q]
+    uint32_t rep_stride;
 };
+
+// The per-read correction report.  Kernel D's report form counts, per row, the columns of its window by the branch of step d that
+// handled them (REP_MATCH ..., REP_KERNEL counters in that order); the driver puts the lengths and the trim counts in front.
+enum { REP_IN = 0, REP_OUT, REP_TFRONT, REP_TBACK, REP_MATCH, REP_SUBST, REP_MISKEPT, REP_INS, REP_DEL, REP_GAPKEPT, REP_FIELDS, REP_KERNEL = 6 };
+extern const char *const rep_names[REP_FIELDS];
+// A rattle_correction the library hands out is the head of this box: the report lies behind the public struct, where no caller's
+// layout sees it.  The library keeps a list of the boxes it made, so a rattle_correction a caller built itself is told apart (box_of
+// returns null for it) and nothing behind it is read.
+struct correction_box {
+    rattle_correction pub;
+    bool has_report;
+    uint32_t *rep[REP_FIELDS];          // [pub.corrected.n] each, parallel to pub.corrected.read_id
+};
+rattle_correction *new_correction();
+correction_box *box_of(const rattle_correction *c);
+void alloc_report(correction_box *B, size_t n);                      // the arrays (never null pointers), has_report = true
+void print_report_totals(const rattle_correction *c, const char *what);      // RATTLE_TIMING=1: the six totals on stderr
 
 int hw_queues();      // hardware queues the HIP runtime of this process hands out (settled when the library is loaded, abi.hip)
 
@@ -317,6 +336,7 @@ struct rattle_ctx {
     rattle::dbuf<unsigned long long> d_exc_bits;
     rattle::dbuf<int32_t> d_exc_val;
     bool phred_ready = false;
+    bool correction_report = false;         // rattle_hip_set_correction_report: stage 1 of `correct` launches kernel D's report form
     rattle::exchange xchg;
     rattle_ctx() = default;
     rattle_ctx(const rattle_ctx &) = delete;

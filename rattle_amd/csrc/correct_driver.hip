@@ -190,6 +190,7 @@ struct stage {
     dbuf<uint8_t> seq, qual, rowc, rowq, ccons, cflag, csym, cons_out;
     dbuf<uint64_t> d_off, d_moff, d_coff;
     dbuf<uint32_t> col, d_width, d_first, tfront, tback, olen, cons_len;
+    dbuf<uint32_t> rep;                 // mode 1 with the correction report on: kernel D's REP_KERNEL counters, counter f of sequence q at rep[f * n() + q]
     dbuf<int32_t> rfirst, rlast;
     dbuf<double> cerr;
     uint32_t n() const { return (uint32_t)off.size() - 1; }
@@ -198,7 +199,7 @@ struct stage {
         seq.release(); qual.release(); rowc.release(); rowq.release(); ccons.release(); cflag.release(); csym.release();
         cons_out.release(); d_off.release(); d_moff.release(); d_coff.release(); col.release(); d_width.release();
         d_first.release(); tfront.release(); tback.release(); olen.release(); cons_len.release(); rfirst.release();
-        rlast.release(); cerr.release();
+        rlast.release(); cerr.release(); rep.release();
     }
 };
 
@@ -243,6 +244,7 @@ int run_post_msa(rattle_ctx *ctx, stage &S, int mode, const rattle_correct_param
     if (mode == 1) {
         RT_TRY(S.rowq.reserve(cells + 64)); RT_TRY(S.tfront.reserve(n + 1)); RT_TRY(S.tback.reserve(n + 1)); RT_TRY(S.olen.reserve(n + 1));
         RT_TRY(S.cflag.reserve(cols + 64)); RT_TRY(S.csym.reserve(cols + 64)); RT_TRY(S.cerr.reserve(cols + 8));
+        if (ctx->correction_report) RT_TRY(S.rep.reserve((size_t)REP_KERNEL * n + REP_KERNEL));
     } else {
         RT_TRY(S.cons_out.reserve(cols + 64)); RT_TRY(S.cons_len.reserve(np));
     }
@@ -259,6 +261,7 @@ int run_post_msa(rattle_ctx *ctx, stage &S, int mode, const rattle_correct_param
     A.n_exc = (uint32_t)ctx->phred.exc_bits.size();
     memcpy(A.order, order, 6);
     A.min_occ = P->min_occ; A.gap_occ = P->gap_occ; A.err_ratio = P->err_ratio;
+    A.rep = mode == 1 && ctx->correction_report ? S.rep.p : nullptr; A.rep_stride = n;      // with A.rep the launch takes the report form
     RT_TRY(launch_post_msa(ctx, A, np, mode));
     return 0;
 }
@@ -353,6 +356,8 @@ struct correct_job {
     stage S1;
     std::vector<sref> r;                             // my packs' members, pack after pack
     std::vector<uint32_t> olen, tfront, tback;       // per member
+    const bool report = ctx->correction_report;      // the correction report is on for this call
+    std::vector<uint32_t> rep;                       // ... kernel D's counters, counter f of member q at rep[f * r.size() + q]
     dbuf<uint8_t> d_rseq, d_rqual;                   // the reads in HBM, unless they are staged there already
     const uint8_t *dev_seq = nullptr, *dev_qual = nullptr;
     dbuf<uint8_t> d_os, d_oq;                        // corrected reads, compacted on the device
@@ -488,6 +493,10 @@ struct correct_job {
         RT_HIP(hipMemcpyAsync(olen.data(), S1.olen.p, (size_t)n1 * 4, hipMemcpyDeviceToHost, st));
         RT_HIP(hipMemcpyAsync(tfront.data(), S1.tfront.p, (size_t)n1 * 4, hipMemcpyDeviceToHost, st));
         RT_HIP(hipMemcpyAsync(tback.data(), S1.tback.p, (size_t)n1 * 4, hipMemcpyDeviceToHost, st));
+        if (report) {
+            rep.assign((size_t)REP_KERNEL * n1 + 1, 0);
+            if (n1) RT_HIP(hipMemcpyAsync(rep.data(), S1.rep.p, (size_t)REP_KERNEL * n1 * 4, hipMemcpyDeviceToHost, st));
+        }
         RT_HIP(hipStreamSynchronize(st));
         S1.seq.release(); S1.qual.release(); S1.col.release();
         for (uint32_t k = 0; k < nm; ++k)
@@ -513,12 +522,14 @@ struct correct_job {
             phase_timer T("correct: corrected reads D2H");
             std::vector<gather_desc> od;
             std::vector<int32_t> o_rid, o_cid;
+            std::vector<uint32_t> o_q;
             uint64_t tot = 0;
             for (uint32_t k = 0; k < nm; ++k)
                 for (uint32_t q = S1.first[k]; q < S1.first[k + 1]; ++q) {
                     if (olen[q] == 0) continue;
                     od.push_back(gather_desc{row_of(k, q), tot, olen[q], 0u});
                     o_rid.push_back(r[q].rid); o_cid.push_back(PL.pk_cid[mine[k]]);
+                    o_q.push_back(q);
                     cor_pack.push_back(mine[k]);
                     tot += olen[q];
                 }
@@ -527,6 +538,17 @@ struct correct_job {
             alloc_read_set(C, (uint32_t)nc, tot);
             for (size_t i = 0; i < nc; ++i) { C.off[i] = od[i].dst; C.read_id[i] = o_rid[i]; C.cluster_id[i] = o_cid[i]; C.n_reads[i] = 0; }
             C.off[nc] = tot;
+            if (report) {                            // the report of record i: the lengths, the trim counts and kernel D's counters of its member
+                correction_box *B = box_of(R);
+                alloc_report(B, nc);
+                const size_t n1 = r.size();
+                for (size_t i = 0; i < nc; ++i) {
+                    const uint32_t q = o_q[i];
+                    B->rep[REP_IN][i] = (uint32_t)(off[r[q].rid + 1] - off[r[q].rid]); B->rep[REP_OUT][i] = olen[q];
+                    B->rep[REP_TFRONT][i] = tfront[q]; B->rep[REP_TBACK][i] = tback[q];
+                    for (int f = 0; f < REP_KERNEL; ++f) B->rep[REP_MATCH + f][i] = rep[f * n1 + q];
+                }
+            }
             if (nc) {
                 make_room(ctx, 2 * (tot + 64) + nc * sizeof(gather_desc));
                 RT_TRY(d_os.reserve(tot + 64)); RT_TRY(d_oq.reserve(tot + 64));
@@ -686,6 +708,7 @@ struct correct_job {
     // ---- the three read sets, the pack of every read, the skip list, the counters
     void assemble() {
         if (!nm) fill_set(R->corrected, {}, {}, {});      // (else: stage1_finish)
+        if (report && !box_of(R)->has_report) alloc_report(box_of(R), 0);
         std::vector<hread> consensi;
         std::vector<int32_t> con_cid, con_n;
         for (uint32_t c = 0; c < n_clusters; ++c) {
@@ -780,6 +803,13 @@ int debug_post_msa(rattle_ctx *ctx, const rattle_correct_params *P, int mode, co
             RT_HIP(fetch(D->flag, S.cflag.p, S.cols)); RT_HIP(fetch(D->sym, S.csym.p, S.cols)); RT_HIP(fetch(D->err, S.cerr.p, S.cols * 8));
             RT_HIP(fetch(rowc.data(), S.rowc.p, S.cells)); RT_HIP(fetch(rowq.data(), S.rowq.p, S.cells));
         }
+        if (ctx->correction_report) {
+            uint32_t **dst[REP_KERNEL] = {&D->match, &D->substituted, &D->mismatch_kept, &D->inserted, &D->deleted, &D->gap_kept};
+            for (int f = 0; f < REP_KERNEL; ++f) {
+                *dst[f] = result_array<uint32_t>(n);
+                if (np) RT_HIP(fetch(*dst[f], S.rep.p + (size_t)f * n, (size_t)n * 4));
+            }
+        }
     } else {
         D->cons_len = result_array<uint32_t>(np); D->consensus = result_array<uint8_t>(S.cols);
         if (np) { RT_HIP(fetch(D->cons_len, S.cons_len.p, (size_t)np * 4)); RT_HIP(fetch(D->consensus, S.cons_out.p, S.cols)); }
@@ -814,7 +844,7 @@ int correct_driver(rattle_ctx *ctx, const uint8_t *seq, const uint8_t *qual, con
                    const rattle_correct_params *P, rattle_correction **out) {
     char order[8] = {0};
     RT_TRY(vote_order_of(P, order));
-    rattle_correction *R = (rattle_correction *)calloc(1, sizeof(rattle_correction));
+    rattle_correction *R = new_correction();
     *out = R;
     phase_timer T_all("correct: total");
     correct_job J{ctx, seq, qual, off, n_reads, n_clusters, P, order, R, ctx->xchg.rank, ctx->xchg.nranks, ctx->stream};
@@ -853,6 +883,7 @@ int correct_driver(rattle_ctx *ctx, const uint8_t *seq, const uint8_t *qual, con
     if (n3b || J.nranks > 1 || xchg_recording(ctx)) RT_TRY(J.exchange_stage(bytes_3b));
     J.d_os.release(); J.d_oq.release();
     J.assemble();
+    print_report_totals(R, J.nranks > 1 ? "correction report (this rank's packs)" : "correction report");
     return 0;
 }
 #undef LOCAL_TRY

@@ -286,6 +286,8 @@ struct piece_view {                      // one rank's serialised set
     const uint32_t *pack = nullptr;
     const uint64_t *off = nullptr;
     const char *seq = nullptr, *qual = nullptr;
+    const uint32_t *rep[REP_FIELDS] = {};      // the correction report of the records (corrected set), if the rank made one
+    bool has_rep = false;
 };
 
 void put_set(std::vector<uint8_t> &b, const rattle_read_set &S, const uint32_t *pack) {
@@ -318,7 +320,8 @@ piece_view take_set(const uint8_t *b, size_t &at) {
 }
 
 // merge the pieces' records in key order (stable: equal keys keep piece order, then record order)
-void merge_sets(const std::vector<piece_view> &V, rattle_read_set &S, uint32_t **pack_out) {
+// rep_out: where the records' correction report goes, field by field ([REP_FIELDS] arrays of S.n entries), or null
+void merge_sets(const std::vector<piece_view> &V, rattle_read_set &S, uint32_t **pack_out, uint32_t *const *rep_out = nullptr) {
     std::vector<rec_ref> refs;
     uint64_t tot = 0;
     for (uint32_t p = 0; p < V.size(); ++p) {
@@ -360,6 +363,7 @@ void merge_sets(const std::vector<piece_view> &V, rattle_read_set &S, uint32_t *
             const uint64_t len = P.off[j + 1] - P.off[j];
             S.read_id[i] = P.read_id[j]; S.cluster_id[i] = P.cluster_id[j]; S.n_reads[i] = P.n_reads[j];
             pk[i] = P.pack[j];
+            if (rep_out) for (int f = 0; f < REP_FIELDS; ++f) rep_out[f][i] = P.rep[f][j];
             memcpy(S.seq + S.off[i], P.seq + P.off[j], len); memcpy(S.qual + S.off[i], P.qual + P.off[j], len);
         }
     });
@@ -397,6 +401,13 @@ int correction_gather(rattle_ctx *ctx, const rattle_correction *L, int root, rat
         if ((3 * n + tot) & 1) { const uint32_t z = 0; put(mine, &z, 1); }
         put(mine, L->counters, 8);
     }
+    {
+        // the correction report of the corrected records, if this rank made one (ten arrays of 4-byte entries: 8-byte aligned as a whole)
+        const correction_box *B = box_of(L);
+        const uint64_t has = B && B->has_report ? 1 : 0;
+        put(mine, &has, 1);
+        if (has) for (int f = 0; f < REP_FIELDS; ++f) put(mine, B->rep[f], L->corrected.n);
+    }
     }
     T_ser.stop();
     gathered G;
@@ -406,7 +417,7 @@ int correction_gather(rattle_ctx *ctx, const rattle_correction *L, int root, rat
     }
     if (X.rank != root) return 0;
     phase_timer T_merge("gather: merge on the root");
-    rattle_correction *R = (rattle_correction *)calloc(1, sizeof(rattle_correction));
+    rattle_correction *R = new_correction();
     std::vector<piece_view> cor, unc;
     struct skip_ref { int32_t cid; uint32_t pack, stage; const int32_t *rid; uint64_t n; };
     std::vector<skip_ref> sk;
@@ -423,6 +434,10 @@ int correction_gather(rattle_ctx *ctx, const rattle_correction *L, int root, rat
         if (r == root) {                         // this rank's own share, in place
             cor.push_back(view_of(L->corrected, L->corrected_pack, no_pack_c));
             unc.push_back(view_of(L->uncorrected, L->uncorrected_pack, no_pack_u));
+            if (const correction_box *B = box_of(L)) {
+                cor.back().has_rep = B->has_report;
+                if (B->has_report) for (int f = 0; f < REP_FIELDS; ++f) cor.back().rep[f] = B->rep[f];
+            }
             const rattle_skip_list &K = L->skipped;
             for (uint64_t i = 0; i < K.n; ++i) sk.push_back(skip_ref{K.cluster_id[i], K.pack[i], K.stage[i], K.read_id + K.read_off[i], K.read_off[i + 1] - K.read_off[i]});
             cnt[0] += L->counters[0]; cnt[1] += L->counters[1]; cnt[2] = L->counters[2]; cnt[3] += L->counters[3]; cnt[4] += L->counters[4];
@@ -446,8 +461,20 @@ int correction_gather(rattle_ctx *ctx, const rattle_correction *L, int root, rat
         cnt[2] = c8[2];
         cnt[3] += c8[3]; cnt[4] += c8[4];
         cnt[5] += c8[5]; cnt[6] += c8[6]; cnt[7] += c8[7];      // cells computed, certified bands, failed certificates add up as well
+        piece_view &C = cor[cor.size() - 1];
+        C.has_rep = *take<uint64_t>(b, at, 1) != 0;
+        if (C.has_rep) for (int f = 0; f < REP_FIELDS; ++f) C.rep[f] = take<uint32_t>(b, at, C.n);
     }
-    merge_sets(cor, R->corrected, &R->corrected_pack);
+    // the merged result has a correction report if every rank made one
+    bool all_rep = true;
+    for (const piece_view &C : cor) all_rep = all_rep && C.has_rep;
+    correction_box *RB = box_of(R);
+    if (all_rep) {
+        size_t n_cor = 0;
+        for (const piece_view &C : cor) n_cor += C.n;
+        alloc_report(RB, n_cor);
+    }
+    merge_sets(cor, R->corrected, &R->corrected_pack, all_rep ? RB->rep : nullptr);
     merge_sets(unc, R->uncorrected, &R->uncorrected_pack);
     // consensi are complete on every rank
     {
@@ -474,6 +501,7 @@ int correction_gather(rattle_ctx *ctx, const rattle_correction *L, int root, rat
         for (size_t i = 0; i < n; ++i) if (sk[i].n) memcpy(K.read_id + K.read_off[i], sk[i].rid, sk[i].n * 4);
     }
     memcpy(R->counters, cnt, sizeof(cnt));
+    if (X.nranks > 1) print_report_totals(R, "correction report (all ranks)");
     *merged = R;
     return 0;
 }

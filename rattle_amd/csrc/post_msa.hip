@@ -15,6 +15,9 @@
 //   d. MODE 1 (after POA #1): one thread per row rewrites the read against the column winners
 //      (in place: the output index never passes the column index);
 //      MODE 2 (after POA #2 / #3): the gap-stripped column winners are the pack consensus.
+// The REPORT form of MODE 1 (rattle_hip_set_correction_report) also counts, per row, the columns of its window by the branch of step d
+// that handled them: six counters the row's thread keeps in registers and stores once, next to olen.  It is an instance of its own:
+// without the report the kernel is the code it was.
 //
 // phred_symbol (utils.cpp:6-8) is `(char)(-10*log10(p)+33)`: the host libm's log10 decides the
 // truncation, so the device does not evaluate log10 at all.  The host tabulates, for every integer n
@@ -108,8 +111,9 @@ __device__ void fix_phase(uint8_t *r, uint32_t n, uint32_t &trimmed, uint32_t &s
 #undef AT
 }
 
-template <int MODE>
+template <int MODE, bool REPORT = false>
 __global__ __launch_bounds__(256) void post_msa_kernel(post_args A) {
+    static_assert(MODE == 1 || !REPORT, "the report is about the per-read correction");
     __shared__ double s_perr[256];
     const uint32_t p = blockIdx.x, tid = threadIdx.x;
     const uint32_t q0 = A.pack_first[p], q1 = A.pack_first[p + 1], R = q1 - q0;
@@ -121,6 +125,7 @@ __global__ __launch_bounds__(256) void post_msa_kernel(post_args A) {
     if (R == 0 || W == 0) {
         if (tid == 0 && MODE == 2) A.cons_len[p] = 0;
         if (MODE == 1) for (uint32_t i = tid; i < R; i += 256) { A.olen[q0 + i] = 0; A.tfront[q0 + i] = 0; A.tback[q0 + i] = 0; }
+        if (REPORT) for (uint32_t i = tid; i < R; i += 256) for (uint32_t f = 0; f < REP_KERNEL; ++f) A.rep[(uint64_t)f * A.rep_stride + q0 + i] = 0;
         return;
     }
     // ---- a. expand
@@ -197,24 +202,35 @@ __global__ __launch_bounds__(256) void post_msa_kernel(post_args A) {
             uint8_t *qrow = rq + (uint64_t)i * W;
             const int32_t first = A.rfirst[q0 + i], last = A.rlast[q0 + i];
             uint32_t o = 0;
+            uint32_t n_match = 0, n_subst = 0, n_miskept = 0, n_ins = 0, n_del = 0, n_gapkept = 0;      // REPORT: the branch taken, column by column
             for (int32_t k = first; k <= last; ++k) {
                 const uint8_t nt = row[k], qq = qrow[k], cnt = ccons[k], fl = cflag[k];
                 uint8_t es = 0, eq = 0;
                 bool emit = true;
                 if (cnt == '-') {
-                    if (nt != '-' && !(fl & 1)) { es = nt; eq = qq; } else emit = false;
+                    if (nt != '-' && !(fl & 1)) { es = nt; eq = qq; if (REPORT) ++n_gapkept; }
+                    else { emit = false; if (REPORT && nt != '-') ++n_del; }
                 } else if (nt == '-') {
-                    if (fl & 1) { es = cnt; eq = csym[k]; } else emit = false;
+                    if (fl & 1) { es = cnt; eq = csym[k]; if (REPORT) ++n_ins; } else emit = false;
                 } else if (nt == cnt) {
                     es = nt; eq = qq;
+                    if (REPORT) ++n_match;
                 } else if ((fl & 2) && A.err_ratio * s_perr[qq] > cerr[k]) {
                     es = cnt; eq = csym[k];
+                    if (REPORT) ++n_subst;
                 } else {
                     es = nt; eq = qq;
+                    if (REPORT) ++n_miskept;
                 }
                 if (emit) { row[o] = es; qrow[o] = eq; ++o; }
             }
             A.olen[q0 + i] = o;
+            if (REPORT) {
+                uint32_t *rep = A.rep + q0 + i;
+                const uint64_t s = A.rep_stride;
+                rep[(REP_MATCH - REP_MATCH) * s] = n_match; rep[(REP_SUBST - REP_MATCH) * s] = n_subst; rep[(REP_MISKEPT - REP_MATCH) * s] = n_miskept;
+                rep[(REP_INS - REP_MATCH) * s] = n_ins; rep[(REP_DEL - REP_MATCH) * s] = n_del; rep[(REP_GAPKEPT - REP_MATCH) * s] = n_gapkept;
+            }
         }
     } else {
         // ---- d'. consensus = column winners without gaps
@@ -237,7 +253,8 @@ __global__ __launch_bounds__(256) void post_msa_kernel(post_args A) {
 int launch_post_msa(rattle_ctx *ctx, const post_args &A, uint32_t n_packs, int mode) {
     if (n_packs == 0) return 0;
     ktimer T(ctx, K_POST, 0);
-    if (mode == 1) hipLaunchKernelGGL(post_msa_kernel<1>, dim3(n_packs), dim3(256), 0, ctx->stream, A);
+    if (mode == 1 && A.rep) hipLaunchKernelGGL((post_msa_kernel<1, true>), dim3(n_packs), dim3(256), 0, ctx->stream, A);      // the report form: same timer slot
+    else if (mode == 1) hipLaunchKernelGGL(post_msa_kernel<1>, dim3(n_packs), dim3(256), 0, ctx->stream, A);
     else hipLaunchKernelGGL(post_msa_kernel<2>, dim3(n_packs), dim3(256), 0, ctx->stream, A);
     RT_HIP(hipGetLastError());
     return 0;

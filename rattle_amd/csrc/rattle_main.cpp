@@ -747,10 +747,13 @@ int mode_correct(int argc, char **argv) {
         {"min-occ", {"-m", "--min-occ"}, true}, {"split", {"-s", "--split"}, true}, {"min-reads", {"-r", "--min-reads"}, true},
         {"threads", {"-t", "--threads"}, true}, {"verbose", {"--verbose"}, false}, {"device", {"--device"}, true},
         {"vote-order", {"--vote-order"}, true}, {"max-pack-cells", {"--max-pack-cells"}, true}, {"devices", {"--devices"}, true},
-        {"host-exchange", {"--host-exchange"}, false}, {"write-unzipped", {"--write-unzipped"}, false}};
+        {"host-exchange", {"--host-exchange"}, false}, {"write-unzipped", {"--write-unzipped"}, false}, {"report", {"--report"}, false}};
     args_t a = parse(argc, argv, defs);
     if (a.has("help")) {
         std::cerr << "rattle correct -i reads.fq -c clusters.out [-o dir] ... (flags of RATTLE's correct mode)\n"
+                     "  --report             also write correction_report.tsv: per record of corrected.fq its lengths before and after, the bases\n"
+                     "                       trimmed at either end, and how many columns matched, were substituted, kept against the\n"
+                     "                       winner, inserted, deleted or kept against a gap winner\n"
                      "  --max-pack-cells N   leave packs whose largest alignment needs more than N DP cells uncorrected (default: only\n"
                      "                       packs that do not fit the device are skipped); skipped packs are listed in skipped_packs.tsv\n"
                      "  --devices 0,1,..     one job over several GPUs (RCCL; --host-exchange: in-process exchange on host buffers)\n";
@@ -853,8 +856,10 @@ int mode_correct(int argc, char **argv) {
         };
         P.corrected_ready_user = &early;
     }
+    const bool want_report = a.has("report");
     team.run([&](int r, rattle_ctx *ctx) {                                      // packs sharded over the ranks, result reassembled on rank 0
         rattle_correction *mine = nullptr, *merged = nullptr;
+        if (want_report) chk(rattle_hip_set_correction_report(ctx, 1));
         const int rc = rattle_hip_correct_reads(ctx, cat.data(), qcat.data(), off.data(), n_reads, (uint32_t)clusters.size(), coff.data(), mid.data(),
                                                 mrev.data(), &P, &mine);
         if (rc != 0 && team.n() == 1) unlink(corrected_tmp.c_str());           // no half of a result stays behind
@@ -916,6 +921,28 @@ int mode_correct(int argc, char **argv) {
     if (!early.done && !write_set(R->corrected, true, corrected_path)) die("Error: cannot write " + corrected_path);
     if (!write_set(R->uncorrected, false, outdir + "/uncorrected.fq")) die("Error: cannot write " + outdir + "/uncorrected.fq");
     write_fastq_file(consensi, outdir + "/consensi.fq");
+    if (want_report) {
+        // correction_report.tsv: one line per record of corrected.fq, in that file's order
+        rattle_correction_report *rp = nullptr;
+        chk(rattle_hip_correction_report(R, &rp));
+        const std::string path = outdir + "/correction_report.tsv";
+        std::ofstream f(path);
+        f << "read\tcluster\tin_len\tout_len\ttrim_front\ttrim_back\tmatch\tsubstituted\tmismatch_kept\tinserted\tdeleted\tgap_kept\n";
+        for (uint32_t i = 0; i < rp->n; ++i) {
+            const span &h = T.header[(uint32_t)R->corrected.read_id[i]];             // the id: the header's first token, without its '@' / '>'
+            const char *b = h.p, *e = h.p + h.n;
+            if (b < e && (*b == '@' || *b == '>')) ++b;
+            const char *t = b;
+            while (t < e && *t != ' ' && *t != '\t') ++t;
+            f.write(b, t - b);
+            f << "\t" << R->corrected.cluster_id[i] << "\t" << rp->in_len[i] << "\t" << rp->out_len[i] << "\t" << rp->trim_front[i] << "\t" << rp->trim_back[i]
+              << "\t" << rp->match[i] << "\t" << rp->substituted[i] << "\t" << rp->mismatch_kept[i] << "\t" << rp->inserted[i] << "\t" << rp->deleted[i]
+              << "\t" << rp->gap_kept[i] << "\n";
+        }
+        rattle_hip_correction_report_free(rp);
+        f.close();
+        if (!f) die("Error: cannot write " + path);
+    }
     if (R->skipped.n) {
         // packs whose POA did not fit the device (or the --max-pack-cells budget): their reads are in uncorrected.fq
         std::ofstream f(outdir + "/skipped_packs.tsv");
