@@ -153,6 +153,37 @@ int rattle_hip_cluster_iso_unsorted(rattle_ctx *ctx, const uint8_t *seq_concat, 
                                     const rattle_cluster_params *iso_params, rattle_cluster_set **out, uint32_t *n_gene_clusters);
 void rattle_hip_cluster_set_free(rattle_cluster_set *cs);
 
+/* The cluster report: why every read is where it is.  Every absorption the greedy clustering performs is one JOIN: in the initial
+ * pass (pass 0) a read joins a founder, in merge pass 1, 2, ... a cluster, through its representative main.id, joins another
+ * cluster's representative.  A clustering of n reads into c clusters has exactly n - c joins.  A join names the comparison that
+ * decided it -- the first accepting founder, forward before reverse, exactly as the driver resolved it -- with what the full
+ * comparison computed for that pair (cluster.cpp:20-34 / :44-58): bases, hc_bases and the variance, min_len = the shorter read's
+ * length and score = the double the verdict compared with t_s (use_hc ? hc_bases / min_len : bases / min_len); score >= t_s and
+ * variance < t_v hold for every join.  Joins are ordered by pass, then by the absorbed item's position in the pass; neither the
+ * order nor the content depends on the seed batch.
+ * Off by default; rattle_hip_set_cluster_report(ctx, 1) makes the following clustering calls on this context launch the report form of
+ * the verdict kernel, which writes the three numbers of every accepted pair beside the pair.  No cluster set changes with the switch.
+ * The joins travel inside the result object, behind the public struct; rattle_hip_cluster_report copies them out (release with
+ * rattle_hip_cluster_report_free).  into / absorbed are ids in the id space of that set's member_id: loaded reads (cluster_reads),
+ * positions in the subset (cluster_subset, cluster_subsets: every outs[i] carries its own joins), the caller's order
+ * (cluster_unsorted).  cluster_iso_unsorted: the level-0 joins of the gene clustering (n - n_genes of them), then the level-1 joins of
+ * every gene in gene order (n - n_clusters in all), ids in the caller's order.
+ * RATTLE_ERR_STATE if the set was made with the switch off or is not an object of this library.  Sharded jobs carry no report yet: with
+ * the switch on, on a context that is one rank of several (rattle_hip_set_exchange / rattle_hip_comm_init, nranks > 1), every
+ * clustering entry point returns RATTLE_ERR_STATE before it exchanges anything (on every rank alike, so none is left waiting). */
+typedef struct {
+    uint64_t n;                 /* joins */
+    uint8_t  *level;            /* 0: gene level / plain clustering, 1: --iso second level */
+    uint32_t *pass; double *bv_threshold;
+    int32_t  *into, *absorbed;
+    uint8_t  *rev;
+    int32_t  *bases, *hc_bases; uint32_t *min_len;
+    double   *score, *variance;
+} rattle_cluster_report;
+int rattle_hip_set_cluster_report(rattle_ctx *ctx, int on);
+int rattle_hip_cluster_report(const rattle_cluster_set *cs, rattle_cluster_report **out);
+void rattle_hip_cluster_report_free(rattle_cluster_report *r);
+
 /* ------------------------------------------------------------------------------------
  * a15  spoa engine + graph as called from /root/reference/correct.cpp:395-405,428-436,520-532
  * (createAlignmentEngine(kSW,5,-4,-8,-6); align + add_alignment per sequence;
@@ -383,6 +414,10 @@ typedef struct {
     int count_pass;                 /* bit 0: the seed-major count pass ran, bit 1: the per-pair search ran, bit 2: the index pass ran */
     uint64_t filter_launches;       /* kernel A launches (one more per survivor-capacity retry) */
     uint64_t oversize_pairs;        /* pairs that went through the oversize full pass */
+    /* [hits.n] each, parallel to hits: what the report form of the verdict kernel wrote for the accepted pair (on a context with
+       rattle_hip_set_cluster_report on, else NULL) */
+    int32_t *hit_bases, *hit_hc_bases;
+    double *hit_variance;
 } rattle_debug_eval;
 
 int rattle_hip_debug_evaluate(rattle_ctx *ctx, const rattle_cluster_params *params, int count_pass, const rattle_debug_rect *rects,

@@ -71,7 +71,8 @@ class DebugPairs(C.Structure):
 
 class DebugEval(C.Structure):
     _fields_ = [("survivors", DebugPairs), ("kept", DebugPairs), ("hits", DebugPairs), ("counters", C.POINTER(C.c_uint64)),
-                ("count_pass", C.c_int), ("filter_launches", C.c_uint64), ("oversize_pairs", C.c_uint64)]
+                ("count_pass", C.c_int), ("filter_launches", C.c_uint64), ("oversize_pairs", C.c_uint64),
+                ("hit_bases", C.POINTER(C.c_int32)), ("hit_hc_bases", C.POINTER(C.c_int32)), ("hit_variance", C.POINTER(C.c_double))]
 
 
 class DebugMsa(C.Structure):
@@ -97,6 +98,16 @@ class DebugPost(C.Structure):
 
 class CorrectionReport(C.Structure):
     _fields_ = [("n", C.c_uint32)] + [(f, C.POINTER(C.c_uint32)) for f in REPORT_FIELDS]
+
+
+# the cluster report (rattle_cluster_report): one entry per join
+CLUSTER_REPORT_FIELDS = (("level", C.c_uint8), ("pass", C.c_uint32), ("bv_threshold", C.c_double), ("into", C.c_int32),
+                         ("absorbed", C.c_int32), ("rev", C.c_uint8), ("bases", C.c_int32), ("hc_bases", C.c_int32),
+                         ("min_len", C.c_uint32), ("score", C.c_double), ("variance", C.c_double))
+
+
+class ClusterReport(C.Structure):
+    _fields_ = [("n", C.c_uint64)] + [(f, C.POINTER(t)) for f, t in CLUSTER_REPORT_FIELDS]
 
 
 # int fn(void *user, const void *send, uint64 send_bytes, void *recv, const uint64 *recv_bytes)
@@ -138,6 +149,9 @@ SIGNATURES = {
     "rattle_hip_cluster_iso_unsorted": (C.c_int, [C.c_void_p, _u8p, _u64p, C.c_uint32, C.c_int, C.c_int, _P(ClusterParams),
                                                   _P(ClusterParams), _P(_P(ClusterSet)), _u32p]),
     "rattle_hip_cluster_set_free": (None, [_P(ClusterSet)]),
+    "rattle_hip_set_cluster_report": (C.c_int, [C.c_void_p, C.c_int]),
+    "rattle_hip_cluster_report": (C.c_int, [_P(ClusterSet), _P(_P(ClusterReport))]),
+    "rattle_hip_cluster_report_free": (None, [_P(ClusterReport)]),
     "rattle_hip_poa_msa": (C.c_int, [C.c_void_p, _u8p, _u64p, C.c_uint32, _u32p, C.c_uint32, _P(_P(MsaSet))]),
     "rattle_hip_msa_set_free": (None, [_P(MsaSet)]),
     "rattle_hip_correct_reads": (C.c_int, [C.c_void_p, _u8p, _u8p, _u64p, C.c_uint32, C.c_uint32, _u32p, _i32p, _u8p,

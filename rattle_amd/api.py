@@ -41,6 +41,13 @@ class Clusters:
     member_id: np.ndarray
     member_rev: np.ndarray
     counters: np.ndarray
+    joins: Optional[dict] = None
+
+    def report(self) -> Optional[dict]:
+        """The cluster report: a dict of arrays with one entry per join (level, pass, bv_threshold, into, absorbed, rev, bases,
+        hc_bases, min_len, score, variance; include/rattle_hip.h), or None if the set was made with the report off
+        (Context.set_cluster_report)."""
+        return self.joins
 
     def as_list(self):
         """[( (main_id, main_rev, -1), [(id, rev, -1), ...] ), ...] like rattle_amd.hps."""
@@ -80,6 +87,25 @@ def correct_params(min_occ=0.3, gap_occ=0.3, err_ratio=30.0, split=200, min_read
         keep = [cl, offs, perm]
     P.max_pack_cells = int(max_pack_cells)
     return P, keep
+
+
+def cluster_report(lib, ptr) -> Optional[dict]:
+    """The cluster report of a library-owned rattle_cluster_set (pointer) as a dict of arrays, one entry per join
+    (_lib.CLUSTER_REPORT_FIELDS); None if the set was made with the report off (Context.set_cluster_report)."""
+    out = C.POINTER(_lib.ClusterReport)()
+    rc = lib.rattle_hip_cluster_report(ptr, C.byref(out))
+    if rc == _lib.RATTLE_ERR_STATE:
+        return None
+    check(rc)
+    n = int(out.contents.n)
+    res = {f: np.ctypeslib.as_array(getattr(out.contents, f), (max(n, 1),))[:n].copy() for f, _ in _lib.CLUSTER_REPORT_FIELDS}
+    lib.rattle_hip_cluster_report_free(out)
+    return res
+
+
+def concat_reports(parts: Sequence[dict]) -> dict:
+    """cluster reports one after the other"""
+    return {f: np.concatenate([p[f] for p in parts]) if parts else np.zeros(0, np.dtype(t)) for f, t in _lib.CLUSTER_REPORT_FIELDS}
 
 
 def correction_report(lib, ptr) -> Optional[dict]:
@@ -205,6 +231,7 @@ class Context:
         self.n = 0
         self.both = False
         self.k = 0
+        self.cluster_report = False
 
     def close(self):
         if self.h:
@@ -216,6 +243,12 @@ class Context:
             self.close()
         except Exception:
             pass
+
+    def set_cluster_report(self, on: bool):
+        """Switch the cluster report of the following cluster_* calls (and the evidence debug_evaluate returns) on or off (off by
+        default): Clusters.report() of their results."""
+        check(self.lib.rattle_hip_set_cluster_report(self.h, int(bool(on))))
+        self.cluster_report = bool(on)
 
     def set_correction_report(self, on: bool):
         """Switch the per-read correction report of the following correct_* / debug_post_msa calls on or off (off by default)."""
@@ -287,17 +320,7 @@ class Context:
         else:
             sub = np.ascontiguousarray(subset, np.uint32)
             check(self.lib.rattle_hip_cluster_subset(self.h, C.byref(P), _ptr(sub, C.c_uint32), len(sub), C.byref(out)))
-        cs = out.contents
-        nc = cs.n_clusters
-        offsets = np.ctypeslib.as_array(cs.offsets, (nc + 1,)).copy()
-        nm = int(offsets[nc])
-        res = Clusters(np.ctypeslib.as_array(cs.main_id, (max(nc, 1),))[:nc].copy(),
-                       np.ctypeslib.as_array(cs.main_rev, (max(nc, 1),))[:nc].copy(), offsets,
-                       np.ctypeslib.as_array(cs.member_id, (max(nm, 1),))[:nm].copy(),
-                       np.ctypeslib.as_array(cs.member_rev, (max(nm, 1),))[:nm].copy(),
-                       np.array(list(cs.counters), dtype=np.uint64))
-        self.lib.rattle_hip_cluster_set_free(out)
-        return res
+        return self._take_clusters(out)
 
     def cluster_subsets(self, subsets: Sequence[np.ndarray], t_s=0.2, t_v=1000000.0, bv_threshold=0.4, min_bv_threshold=0.2,
                         bv_falloff=0.05, repr_percentile=0.15, is_rna=False, n_workers=0) -> List[Clusters]:
@@ -320,7 +343,7 @@ class Context:
                        np.ctypeslib.as_array(cs.main_rev, (max(nc, 1),))[:nc].copy(), offsets,
                        np.ctypeslib.as_array(cs.member_id, (max(nm, 1),))[:nm].copy(),
                        np.ctypeslib.as_array(cs.member_rev, (max(nm, 1),))[:nm].copy(),
-                       np.array(list(cs.counters), dtype=np.uint64))
+                       np.array(list(cs.counters), dtype=np.uint64), cluster_report(self.lib, out))
         self.lib.rattle_hip_cluster_set_free(out)
         return res
 
@@ -501,7 +524,8 @@ class Context:
         rects: list of (seed_ids, cand_ids, thr); cand_ids None = triangular (the seeds against each other, pairs s < c).
         count_pass: "auto" (the driver's rule), "seed", "search" or "index".  Returns a dict: "survivors" (with "count"), "kept" and
         "hits", each a dict of arrays rect / seed / cand / strand (indices within the rectangle); "counters" [n_rects, 8];
-        "count_pass" (the set of passes that ran); "filter_launches"; "oversize_pairs"."""
+        "count_pass" (the set of passes that ran); "filter_launches"; "oversize_pairs"; with set_cluster_report on also "evidence":
+        arrays bases / hc_bases / variance parallel to "hits", what the verdict kernel's report form wrote for each of them."""
         mode = {"auto": 0, "seed": 1, "search": 2, "index": 3}[count_pass]
         P = ClusterParams(t_s, t_v, 0.0, 0.0, 0.0, 0, int(use_hc), 0.0, int(is_rna))
         keep = []
@@ -531,6 +555,9 @@ class Context:
                "counters": np.ctypeslib.as_array(D.counters, (len(rects) * 8 + 1,))[:len(rects) * 8].reshape(len(rects), 8).copy(),
                "count_pass": {p for b, p in ((1, "seed"), (2, "search"), (4, "index")) if D.count_pass & b},
                "filter_launches": int(D.filter_launches), "oversize_pairs": int(D.oversize_pairs)}
+        if D.hit_bases:
+            nh = D.hits.n
+            res["evidence"] = {f: np.ctypeslib.as_array(getattr(D, "hit_" + f), (max(nh, 1),))[:nh].copy() for f in ("bases", "hc_bases", "variance")}
         self.lib.rattle_hip_debug_evaluate_free(out)
         return res
 
@@ -617,17 +644,44 @@ def min_common_lut(thr: float) -> np.ndarray:
 
 def cluster_command(ctx: Context, seqs: Sequence[bytes], ann: Sequence[int], *, k=10, t_s=0.2, t_v=1000000.0,
                     iso=False, iso_k=11, iso_t_s=0.3, iso_t_v=25.0, bv_threshold=0.4, bv_min_threshold=0.2,
-                    bv_falloff=0.05, repr_percentile=0.15, is_rna=False):
+                    bv_falloff=0.05, repr_percentile=0.15, is_rna=False, report=False):
     """`rattle cluster` after input parsing (main.cpp:254-323).  `seqs`/`ann` are the filtered reads
-    and their original record indices.  Returns clusters in rattle_amd.hps list form."""
+    and their original record indices.  Returns clusters in rattle_amd.hps list form and the counters; report=True: also the
+    cluster report (Clusters.report(): gene-level joins, then with iso the level-1 joins of every gene in gene order; into / absorbed
+    are record indices), made with the context's switch on for the length of the call."""
+    if report:
+        was = ctx.cluster_report
+        ctx.set_cluster_report(True)
+        try:
+            return _cluster_command(ctx, seqs, ann, k, t_s, t_v, iso, iso_k, iso_t_s, iso_t_v, bv_threshold, bv_min_threshold, bv_falloff,
+                                    repr_percentile, is_rna, True)
+        finally:
+            ctx.set_cluster_report(was)
+    return _cluster_command(ctx, seqs, ann, k, t_s, t_v, iso, iso_k, iso_t_s, iso_t_v, bv_threshold, bv_min_threshold, bv_falloff,
+                            repr_percentile, is_rna, False)
+
+
+def _cluster_command(ctx, seqs, ann, k, t_s, t_v, iso, iso_k, iso_t_s, iso_t_v, bv_threshold, bv_min_threshold, bv_falloff,
+                     repr_percentile, is_rna, report):
     order = sorted(range(len(seqs)), key=lambda i: -len(seqs[i]))       # stable, length desc (fasta.cpp:462)
     sseqs = [seqs[i] for i in order]
     sann = [ann[i] for i in order]
+    ann_of = np.asarray(sann, np.int64)
+
+    def joins_of(cl, ids, level):
+        """a set's joins with its ids (positions in `ids`) as record indices"""
+        j = dict(cl.report())
+        j["into"] = ann_of[ids[j["into"]]].astype(np.int32); j["absorbed"] = ann_of[ids[j["absorbed"]]].astype(np.int32)
+        j["level"] = np.full(len(j["into"]), level, np.uint8)
+        return j
+
     ctx.load_reads(sseqs, k, not is_rna)
     gene = ctx.cluster_reads(t_s, t_v, bv_threshold, bv_min_threshold, bv_falloff, 0, False, repr_percentile, is_rna)
     gl = gene.as_list()
+    parts = [joins_of(gene, np.arange(len(sseqs)), 0)] if report else []
     if not iso:
-        return [((sann[m[0]], m[1], -1), [(sann[s[0]], s[1], -1) for s in mem]) for m, mem in gl], gene.counters
+        res = [((sann[m[0]], m[1], -1), [(sann[s[0]], s[1], -1) for s in mem]) for m, mem in gl], gene.counters
+        return res + (concat_reports(parts),) if report else res
     ctx.load_reads(sseqs, iso_k, not is_rna)
     out = []
     counters = gene.counters.copy()
@@ -642,7 +696,9 @@ def cluster_command(ctx: Context, seqs: Sequence[bytes], ann: Sequence[int], *, 
         counters += sub.counters
         for im, imem in sub.as_list():
             out.append(((sann[int(ids[im[0]])], im[1], gi), [(sann[int(ids[s[0]])], s[1], gi) for s in imem]))
-    return out, counters
+        if report:
+            parts.append(joins_of(sub, ids.astype(np.int64), 1))
+    return (out, counters, concat_reports(parts)) if report else (out, counters)
 
 
 def correct_command(ctx: Context, headers: Sequence[bytes], seqs: Sequence[bytes], quals: Sequence[bytes], clusters, *,

@@ -72,6 +72,23 @@ correction_box *box_of(const rattle_correction *c) {
     return c && boxes().count(c) ? (correction_box *)c : nullptr;
 }
 
+// ---- result objects of `cluster`: the public struct at the head of a box that also holds the joins of the cluster report (common.h)
+namespace {
+std::unordered_set<const rattle_cluster_set *> &cluster_boxes() { static std::unordered_set<const rattle_cluster_set *> s; return s; }
+}  // namespace
+
+rattle_cluster_set *new_cluster_set() {
+    cluster_box *B = (cluster_box *)calloc(1, sizeof(cluster_box));
+    std::lock_guard<std::mutex> g(g_box_mu);
+    cluster_boxes().insert(&B->pub);
+    return &B->pub;
+}
+
+cluster_box *cluster_box_of(const rattle_cluster_set *cs) {
+    std::lock_guard<std::mutex> g(g_box_mu);
+    return cs && cluster_boxes().count(cs) ? (cluster_box *)cs : nullptr;
+}
+
 void alloc_report(correction_box *B, size_t n) {
     for (int f = 0; f < REP_FIELDS; ++f) { free(B->rep[f]); B->rep[f] = (uint32_t *)calloc(std::max<size_t>(1, n), 4); }
     B->has_report = true;
@@ -99,6 +116,23 @@ static int use_device(rattle_ctx *c) {
     if (c->device < 0) { set_error("this context has no device (rattle_hip_ctx_create_host): only the exchange entry points work"); return RATTLE_ERR_STATE; }
     RT_HIP(hipSetDevice(c->device));
     return 0;
+}
+
+// The cluster report does not travel through the exchange of a sharded job yet: refused on every rank alike, before any collective
+static int report_needs_one_rank(rattle_ctx *c) {
+    if (c->cluster_report && c->xchg.nranks > 1) {
+        set_error("the cluster report (rattle_hip_set_cluster_report) is not available on a context that is one rank of several: "
+                  "switch it off on every rank, or cluster on one device");
+        return RATTLE_ERR_STATE;
+    }
+    return 0;
+}
+
+// joins of a set whose ids were positions in `map` -> the ids map holds
+static void translate_joins(rattle_cluster_set *cs, const uint32_t *map) {
+    cluster_box *B = cluster_box_of(cs);
+    if (!B || !B->has_report) return;
+    for (cluster_join &j : *B->joins) { j.into = (int32_t)map[j.into]; j.absorbed = (int32_t)map[j.absorbed]; }
 }
 
 extern "C" {
@@ -235,6 +269,7 @@ int rattle_hip_pair_score(rattle_ctx *c, const uint32_t *i_ids, const uint32_t *
 int rattle_hip_cluster_reads(rattle_ctx *c, const rattle_cluster_params *P, rattle_cluster_set **out) {
     if (!c || !P || !out) { set_error("null argument"); return RATTLE_ERR_ARG; }
     *out = nullptr;
+    RT_TRY(report_needs_one_rank(c));
     RT_TRY(use_device(c));
     if (c->idx.k == 0) { set_error("no reads loaded"); return RATTLE_ERR_STATE; }      // (never loaded, or the index made room for a big `correct`)
     if (!P->is_rna && !c->idx.both) { set_error("cDNA mode needs the reads loaded with both_strands=1"); return RATTLE_ERR_STATE; }
@@ -247,6 +282,7 @@ int rattle_hip_cluster_subset(rattle_ctx *c, const rattle_cluster_params *P, con
                               rattle_cluster_set **out) {
     if (!c || !P || !out || (n_subset && !subset)) { set_error("null argument"); return RATTLE_ERR_ARG; }
     *out = nullptr;
+    RT_TRY(report_needs_one_rank(c));
     for (uint32_t i = 0; i < n_subset; ++i) if (subset[i] >= c->idx.n) { set_error("subset id out of range"); return RATTLE_ERR_ARG; }
     RT_TRY(use_device(c));
     if (!P->is_rna && !c->idx.both) { set_error("cDNA mode needs the reads loaded with both_strands=1"); return RATTLE_ERR_STATE; }
@@ -263,6 +299,7 @@ int rattle_hip_cluster_subsets(rattle_ctx *c, const rattle_cluster_params *P, co
                                uint32_t n_subsets, rattle_cluster_set **outs, int n_workers) {
     if (!c || !P || !outs || !sub_off || (n_subsets && sub_off[n_subsets] && !ids)) { set_error("null argument"); return RATTLE_ERR_ARG; }
     for (uint32_t i = 0; i < n_subsets; ++i) outs[i] = nullptr;
+    RT_TRY(report_needs_one_rank(c));
     for (uint64_t i = 0; i < sub_off[n_subsets]; ++i) if (ids[i] >= c->idx.n) { set_error("subset id out of range"); return RATTLE_ERR_ARG; }
     RT_TRY(use_device(c));
     if (!P->is_rna && !c->idx.both) { set_error("cDNA mode needs the reads loaded with both_strands=1"); return RATTLE_ERR_STATE; }
@@ -315,7 +352,7 @@ int rattle_hip_cluster_subsets(rattle_ctx *c, const rattle_cluster_params *P, co
                 uint32_t hdr[3];
                 memcpy(hdr, b.data() + at, 12); at += 12;
                 if (hdr[0] >= n_subsets || outs[hdr[0]]) { set_error("cluster_subsets exchange: malformed record"); rc = RATTLE_ERR_HIP; break; }
-                rattle_cluster_set *cs = (rattle_cluster_set *)calloc(1, sizeof(rattle_cluster_set));
+                rattle_cluster_set *cs = new_cluster_set();
                 cs->n_clusters = hdr[1];
                 memcpy(cs->counters, b.data() + at, 64); at += 64;
                 cs->main_id = (int32_t *)malloc(std::max<size_t>(1, hdr[1]) * 4); cs->offsets = (uint32_t *)malloc(((size_t)hdr[1] + 1) * 4);
@@ -416,6 +453,7 @@ int rattle_hip_cluster_unsorted(rattle_ctx *c, const uint8_t *seq, const uint64_
                                 const rattle_cluster_params *P, rattle_cluster_set **out) {
     if (!c || !off || !P || !out || (n && !seq)) { set_error("null argument"); return RATTLE_ERR_ARG; }
     *out = nullptr;
+    RT_TRY(report_needs_one_rank(c));
     RT_TRY(use_device(c));
     phase_timer T_all("cluster_unsorted: total");
     std::vector<uint32_t> order;
@@ -425,6 +463,7 @@ int rattle_hip_cluster_unsorted(rattle_ctx *c, const uint8_t *seq, const uint64_
     const uint32_t nm = cs->offsets[cs->n_clusters];
     for (uint32_t i = 0; i < cs->n_clusters; ++i) cs->main_id[i] = (int32_t)order[cs->main_id[i]];
     for (uint32_t i = 0; i < nm; ++i) cs->member_id[i] = (int32_t)order[cs->member_id[i]];
+    translate_joins(cs, order.data());
     return 0;
 }
 
@@ -437,6 +476,7 @@ int rattle_hip_cluster_iso_unsorted(rattle_ctx *c, const uint8_t *seq, const uin
                                     uint32_t *n_gene_clusters) {
     if (!c || !off || !P || !iso_P || !out || (n && !seq)) { set_error("null argument"); return RATTLE_ERR_ARG; }
     *out = nullptr;
+    RT_TRY(report_needs_one_rank(c));
     RT_TRY(use_device(c));
     phase_timer T_all("cluster_iso_unsorted: total");
     std::vector<uint32_t> order;
@@ -460,7 +500,15 @@ int rattle_hip_cluster_iso_unsorted(rattle_ctx *c, const uint8_t *seq, const uin
     { phase_timer T("cluster: iso level"); RT_TRY(rattle_hip_cluster_subsets(c, iso_P, ids.data(), sub_off.data(), G, subs.data(), 0)); }
     size_t nc = 0, nm = 0;
     for (uint32_t g = 0; g < G; ++g) { nc += subs[g]->n_clusters; nm += subs[g]->offsets[subs[g]->n_clusters]; }
-    rattle_cluster_set *R = (rattle_cluster_set *)calloc(1, sizeof(rattle_cluster_set));
+    rattle_cluster_set *R = new_cluster_set();
+    // the cluster report: the gene level's joins, then every gene's, all in the caller's order
+    std::vector<cluster_join> *joins = nullptr;
+    if (const cluster_box *GB = cluster_box_of(gene); GB && GB->has_report) {
+        joins = new std::vector<cluster_join>(*GB->joins);
+        for (cluster_join &j : *joins) { j.into = (int32_t)order[j.into]; j.absorbed = (int32_t)order[j.absorbed]; }
+        cluster_box *RB = cluster_box_of(R);
+        RB->joins = joins; RB->has_report = true;
+    }
     R->n_clusters = (uint32_t)nc;
     R->main_id = (int32_t *)malloc(std::max<size_t>(1, nc) * 4); R->main_rev = (uint8_t *)malloc(std::max<size_t>(1, nc));
     R->gene_id = (int32_t *)malloc(std::max<size_t>(1, nc) * 4);
@@ -478,6 +526,11 @@ int rattle_hip_cluster_iso_unsorted(rattle_ctx *c, const uint8_t *seq, const uin
             ++ci;
         }
         for (int i = 0; i < 8; ++i) R->counters[i] += S->counters[i];
+        if (const cluster_box *SB = joins ? cluster_box_of(S) : nullptr; SB && SB->has_report)
+            for (cluster_join j : *SB->joins) {
+                j.level = 1; j.into = (int32_t)order[gids[j.into]]; j.absorbed = (int32_t)order[gids[j.absorbed]];
+                joins->push_back(j);
+            }
         rattle_hip_cluster_set_free(subs[g]);
     }
     R->offsets[nc] = mi;
@@ -487,8 +540,53 @@ int rattle_hip_cluster_iso_unsorted(rattle_ctx *c, const uint8_t *seq, const uin
 
 void rattle_hip_cluster_set_free(rattle_cluster_set *cs) {
     if (!cs) return;
+    if (cluster_box *B = cluster_box_of(cs)) {
+        delete B->joins;
+        std::lock_guard<std::mutex> g(g_box_mu);
+        cluster_boxes().erase(cs);
+    }
     free(cs->main_id); free(cs->main_rev); free(cs->offsets); free(cs->member_id); free(cs->member_rev); free(cs->gene_id);
     free(cs);
+}
+
+int rattle_hip_set_cluster_report(rattle_ctx *c, int on) {
+    if (!c) { set_error("null ctx"); return RATTLE_ERR_ARG; }
+    c->cluster_report = on != 0;
+    if (!c->cluster_report) { c->d_hit_ev.release(); c->h_hit_ev.release(); }
+    return 0;
+}
+
+int rattle_hip_cluster_report(const rattle_cluster_set *cs, rattle_cluster_report **out) {
+    if (out) *out = nullptr;
+    if (!cs || !out) { set_error("null argument"); return RATTLE_ERR_ARG; }
+    const cluster_box *B = cluster_box_of(cs);
+    if (!B || !B->has_report) {
+        set_error("this cluster set carries no report: rattle_hip_set_cluster_report(ctx, 1) comes before the clustering call, and the set must be one this library returned");
+        return RATTLE_ERR_STATE;
+    }
+    const std::vector<cluster_join> &J = *B->joins;
+    const size_t n = J.size(), m = std::max<size_t>(1, n);
+    rattle_cluster_report *R = (rattle_cluster_report *)calloc(1, sizeof(rattle_cluster_report));
+    R->n = n;
+    R->level = (uint8_t *)malloc(m); R->pass = (uint32_t *)malloc(4 * m); R->bv_threshold = (double *)malloc(8 * m);
+    R->into = (int32_t *)malloc(4 * m); R->absorbed = (int32_t *)malloc(4 * m); R->rev = (uint8_t *)malloc(m);
+    R->bases = (int32_t *)malloc(4 * m); R->hc_bases = (int32_t *)malloc(4 * m); R->min_len = (uint32_t *)malloc(4 * m);
+    R->score = (double *)malloc(8 * m); R->variance = (double *)malloc(8 * m);
+    for (size_t i = 0; i < n; ++i) {
+        const cluster_join &j = J[i];
+        R->level[i] = j.level; R->pass[i] = j.pass; R->bv_threshold[i] = j.thr; R->into[i] = j.into; R->absorbed[i] = j.absorbed;
+        R->rev[i] = j.rev; R->bases[i] = j.bases; R->hc_bases[i] = j.hc; R->min_len[i] = j.min_len; R->score[i] = j.score;
+        R->variance[i] = j.variance;
+    }
+    *out = R;
+    return 0;
+}
+
+void rattle_hip_cluster_report_free(rattle_cluster_report *r) {
+    if (!r) return;
+    free(r->level); free(r->pass); free(r->bv_threshold); free(r->into); free(r->absorbed); free(r->rev); free(r->bases);
+    free(r->hc_bases); free(r->min_len); free(r->score); free(r->variance);
+    free(r);
 }
 
 int rattle_hip_poa_msa(rattle_ctx *c, const uint8_t *seq, const uint64_t *off, uint32_t n_seqs, const uint32_t *pack_first,
@@ -639,6 +737,7 @@ static void free_pairs(rattle_debug_pairs &d) { free(d.rect); free(d.seed); free
 void rattle_hip_debug_evaluate_free(rattle_debug_eval *e) {
     if (!e) return;
     free_pairs(e->survivors); free_pairs(e->kept); free_pairs(e->hits);
+    free(e->hit_bases); free(e->hit_hc_bases); free(e->hit_variance);
     free(e->counters);
     free(e);
 }

@@ -100,12 +100,17 @@ __global__ __launch_bounds__(256) void count_bound_kernel(const uint32_t *__rest
 // the host sees the few accepted pairs instead of four integers and a double for every full comparison (10 M of them in the
 // --iso level at 1e6 reads).  Pairs whose match list did not fit LDS are listed for the oversize pass (out[0] = count, out[1] =
 // oversize pairs, out[2] = their largest match count) and judged by a second launch over that list.
-__global__ __launch_bounds__(256) void verdict_kernel(const int32_t *__restrict__ res, const double *__restrict__ var, uint32_t n,
-                                                      const uint32_t *__restrict__ remap, const uint32_t *__restrict__ pi,
-                                                      const uint32_t *__restrict__ pj, const uint32_t *__restrict__ slot2,
-                                                      const uint32_t *__restrict__ len, int use_hc, double t_s, double t_v,
-                                                      unsigned long long *__restrict__ out, uint32_t *__restrict__ hits,
-                                                      uint32_t *__restrict__ big) {
+//
+// The report form (REPORT, the cluster report: rattle_hip_set_cluster_report) also writes what the full comparison computed for every
+// accepted pair -- bases, hc_bases, the variance's 64 bits: one 16-byte vector store -- at the pair's compacted position, so evid[at]
+// belongs to hits[2 * at ..] whichever of the two launches accepted it.
+template <bool REPORT>
+__device__ __forceinline__ void verdict_body(const int32_t *__restrict__ res, const double *__restrict__ var, uint32_t n,
+                                             const uint32_t *__restrict__ remap, const uint32_t *__restrict__ pi,
+                                             const uint32_t *__restrict__ pj, const uint32_t *__restrict__ slot2,
+                                             const uint32_t *__restrict__ len, int use_hc, double t_s, double t_v,
+                                             unsigned long long *__restrict__ out, uint32_t *__restrict__ hits,
+                                             uint32_t *__restrict__ big, uint4 *__restrict__ evid) {
     const uint32_t t = blockIdx.x * blockDim.x + threadIdx.x;
     const int lane = threadIdx.x & 63;
     bool ok = false, over = false;
@@ -136,8 +141,31 @@ __global__ __launch_bounds__(256) void verdict_kernel(const int32_t *__restrict_
         if (ok) {
             const uint64_t at = base + (uint64_t)__popcll(mk & ((1ull << lane) - 1ull));
             hits[2 * at] = slot2[2 * (size_t)q]; hits[2 * at + 1] = slot2[2 * (size_t)q + 1];
+            if (REPORT) {
+                const int32_t *r = res + 4 * (size_t)q;
+                const unsigned long long vb = (unsigned long long)__double_as_longlong(var[q]);
+                evid[at] = make_uint4((uint32_t)r[0], (uint32_t)r[1], (uint32_t)vb, (uint32_t)(vb >> 32));
+            }
         }
     }
+}
+
+__global__ __launch_bounds__(256) void verdict_kernel(const int32_t *__restrict__ res, const double *__restrict__ var, uint32_t n,
+                                                      const uint32_t *__restrict__ remap, const uint32_t *__restrict__ pi,
+                                                      const uint32_t *__restrict__ pj, const uint32_t *__restrict__ slot2,
+                                                      const uint32_t *__restrict__ len, int use_hc, double t_s, double t_v,
+                                                      unsigned long long *__restrict__ out, uint32_t *__restrict__ hits,
+                                                      uint32_t *__restrict__ big) {
+    verdict_body<false>(res, var, n, remap, pi, pj, slot2, len, use_hc, t_s, t_v, out, hits, big, nullptr);
+}
+
+__global__ __launch_bounds__(256) void verdict_report_kernel(const int32_t *__restrict__ res, const double *__restrict__ var, uint32_t n,
+                                                             const uint32_t *__restrict__ remap, const uint32_t *__restrict__ pi,
+                                                             const uint32_t *__restrict__ pj, const uint32_t *__restrict__ slot2,
+                                                             const uint32_t *__restrict__ len, int use_hc, double t_s, double t_v,
+                                                             unsigned long long *__restrict__ out, uint32_t *__restrict__ hits,
+                                                             uint32_t *__restrict__ big, uint4 *__restrict__ evid) {
+    verdict_body<true>(res, var, n, remap, pi, pj, slot2, len, use_hc, t_s, t_v, out, hits, big, evid);
 }
 
 namespace {
@@ -154,6 +182,7 @@ struct request {
     uint64_t *counters = nullptr;             // the job's work counters
     uint32_t tag = 0;                         // the test hook's rectangle number (eval_sink)
     std::vector<hit_t> hits;                  // out: accepted (seed index, candidate index, strand); sorted if triangular
+    std::vector<hit_evidence> ev;             // out, only when the context reports (else empty): the evidence of hits[i]
     uint32_t n_cands() const { return (uint32_t)(triangular ? seeds.size() : cands.size()); }
     uint64_t n_pairs() const {
         const uint64_t s = seeds.size();
@@ -270,10 +299,20 @@ struct evaluator {
         return run_chunks(reqs);
     }
 
-    static void sort_hits(std::vector<hit_t> &hits) {
-        std::sort(hits.begin(), hits.end(), [](const hit_t &a, const hit_t &b) {
+    static void sort_hits(request &Q) {
+        std::vector<hit_t> &hits = Q.hits;
+        auto before = [](const hit_t &a, const hit_t &b) {
             return a.seed != b.seed ? a.seed < b.seed : (a.cand != b.cand ? a.cand < b.cand : a.rev < b.rev);
-        });
+        };
+        if (Q.ev.empty()) { std::sort(hits.begin(), hits.end(), before); return; }
+        // reporting: the evidence moves with its hit
+        std::vector<uint32_t> at(hits.size());
+        for (uint32_t i = 0; i < at.size(); ++i) at[i] = i;
+        std::sort(at.begin(), at.end(), [&](uint32_t a, uint32_t b) { return before(hits[a], hits[b]); });
+        std::vector<hit_t> h2(hits.size());
+        std::vector<hit_evidence> e2(hits.size());
+        for (size_t i = 0; i < at.size(); ++i) { h2[i] = hits[at[i]]; e2[i] = Q.ev[at[i]]; }
+        hits.swap(h2); Q.ev.swap(e2);
     }
 
     // Every pair can survive the filter, and in the thr == 0 pass every pair does (cluster.cpp:19,43): one launch
@@ -304,7 +343,7 @@ struct evaluator {
         // ---- the rectangles side by side in one seed array and one candidate array
         uint64_t ns = 0, nc = 0, npairs = 0;
         for (size_t q = 0; q < nreq; ++q) {
-            reqs[q]->hits.clear();
+            reqs[q]->hits.clear(); reqs[q]->ev.clear();
             if (reqs[q]->seeds.empty() || reqs[q]->n_cands() == 0) continue;
             ns += reqs[q]->seeds.size(); nc += reqs[q]->n_cands();
         }
@@ -430,8 +469,16 @@ struct evaluator {
         unsigned long long *vout = ctx->d_bound_stats.p + 2 + 3 * (size_t)nrect;
         uint32_t *d_hits = ctx->d_surv.p, *d_big = ctx->d_pi2.p;
         const int use_hc = P->use_hc ? 1 : 0;
-        hipLaunchKernelGGL(verdict_kernel, dim3((n2 + 255) / 256), dim3(256), 0, st, ctx->d_res.p, ctx->d_var.p, n2, (const uint32_t *)nullptr,
-                           ctx->d_pi.p, ctx->d_pj.p, ctx->d_slot2.p, X.len.p, use_hc, t_s, t_v, vout, d_hits, d_big);
+        // the cluster report: the evidence of the accepted pairs (at most n2 of them over both verdict launches) beside them
+        const bool report = ctx->cluster_report;
+        uint4 *d_ev = nullptr;
+        if (report) { RT_TRY(ctx->d_hit_ev.reserve(n2)); d_ev = (uint4 *)ctx->d_hit_ev.p; }
+        if (report)
+            hipLaunchKernelGGL(verdict_report_kernel, dim3((n2 + 255) / 256), dim3(256), 0, st, ctx->d_res.p, ctx->d_var.p, n2, (const uint32_t *)nullptr,
+                               ctx->d_pi.p, ctx->d_pj.p, ctx->d_slot2.p, X.len.p, use_hc, t_s, t_v, vout, d_hits, d_big, d_ev);
+        else
+            hipLaunchKernelGGL(verdict_kernel, dim3((n2 + 255) / 256), dim3(256), 0, st, ctx->d_res.p, ctx->d_var.p, n2, (const uint32_t *)nullptr,
+                               ctx->d_pi.p, ctx->d_pj.p, ctx->d_slot2.p, X.len.p, use_hc, t_s, t_v, vout, d_hits, d_big);
         ++launches;
         unsigned long long *hv = ctx->h_bound_stats.p + 2 + 3 * (size_t)nrect;
         // the first accepted pairs travel with the counters (one synchronisation per evaluation instead of two: the --iso level
@@ -440,6 +487,10 @@ struct evaluator {
         RT_TRY(ctx->h_surv.reserve((size_t)spec * 2 + 2));
         RT_HIP(hipMemcpyAsync(hv, vout, 24, hipMemcpyDeviceToHost, st));
         RT_HIP(hipMemcpyAsync(ctx->h_surv.p, d_hits, (size_t)spec * 8, hipMemcpyDeviceToHost, st));
+        if (report) {
+            RT_TRY(ctx->h_hit_ev.reserve(spec));
+            RT_HIP(hipMemcpyAsync(ctx->h_hit_ev.p, d_ev, (size_t)spec * sizeof(hit_evidence), hipMemcpyDeviceToHost, st));
+        }
         RT_HIP(hipStreamSynchronize(st));
         const bool nbig_seen = hv[1] != 0;
         if (hv[1]) {
@@ -452,17 +503,26 @@ struct evaluator {
             ++launches;
             if (sink) sink->oversize += nbig;
             RT_HIP(hipMemsetAsync(vout + 1, 0, 16, st));
-            hipLaunchKernelGGL(verdict_kernel, dim3((nbig + 255) / 256), dim3(256), 0, st, ctx->d_res.p, ctx->d_var.p, nbig, (const uint32_t *)d_big,
-                               ctx->d_pi.p, ctx->d_pj.p, ctx->d_slot2.p, X.len.p, use_hc, t_s, t_v, vout, d_hits, d_big);
+            if (report)
+                hipLaunchKernelGGL(verdict_report_kernel, dim3((nbig + 255) / 256), dim3(256), 0, st, ctx->d_res.p, ctx->d_var.p, nbig, (const uint32_t *)d_big,
+                                   ctx->d_pi.p, ctx->d_pj.p, ctx->d_slot2.p, X.len.p, use_hc, t_s, t_v, vout, d_hits, d_big, d_ev);
+            else
+                hipLaunchKernelGGL(verdict_kernel, dim3((nbig + 255) / 256), dim3(256), 0, st, ctx->d_res.p, ctx->d_var.p, nbig, (const uint32_t *)d_big,
+                                   ctx->d_pi.p, ctx->d_pj.p, ctx->d_slot2.p, X.len.p, use_hc, t_s, t_v, vout, d_hits, d_big);
             ++launches;
             RT_HIP(hipMemcpyAsync(hv, vout, 24, hipMemcpyDeviceToHost, st));
             RT_HIP(hipStreamSynchronize(st));
             if (hv[1]) { set_error("pair_score: a pair is still oversize after the oversize pass"); return RATTLE_ERR_HIP; }
         }
         const uint32_t nhit = (uint32_t)hv[0];
+        if (hv[0] > n2) { set_error("verdicts: more accepted pairs than full comparisons"); return RATTLE_ERR_HIP; }
         if (nhit > spec || nbig_seen) {                  // more than came along (or the oversize pass appended some): fetch them all
             RT_TRY(ctx->h_surv.reserve((size_t)nhit * 2 + 2));
             if (nhit) RT_HIP(hipMemcpyAsync(ctx->h_surv.p, d_hits, (size_t)nhit * 8, hipMemcpyDeviceToHost, st));
+            if (report && nhit) {
+                RT_TRY(ctx->h_hit_ev.reserve(nhit));
+                RT_HIP(hipMemcpyAsync(ctx->h_hit_ev.p, d_ev, (size_t)nhit * sizeof(hit_evidence), hipMemcpyDeviceToHost, st));
+            }
             RT_HIP(hipStreamSynchronize(st));
         }
         // accepted pairs back to their rectangle
@@ -471,8 +531,9 @@ struct evaluator {
             const uint32_t rj = many ? seed_req[a >> 1] : 0;
             const bvf_rect &J = rects[rj];
             reqs[rect_req[rj]]->hits.push_back(hit_t{(a >> 1) - J.s_base, c - J.c_base, (uint8_t)(a & 1u)});
+            if (report) reqs[rect_req[rj]]->ev.push_back(ctx->h_hit_ev.p[q]);
         }
-        for (uint32_t j = 0; j < nrect; ++j) if (reqs[rect_req[j]]->triangular) sort_hits(reqs[rect_req[j]]->hits);      // level 2 takes them in any order
+        for (uint32_t j = 0; j < nrect; ++j) if (reqs[rect_req[j]]->triangular) sort_hits(*reqs[rect_req[j]]);      // level 2 takes them in any order
         lap(4);
         return 0;
     }
@@ -518,6 +579,12 @@ struct job {
     enum { ROUND, WAIT_L1, FOUNDERS, WAIT_L2 } phase = ROUND;
     std::vector<uint32_t> items, owner, remaining, next, seeds_local, founders, best;
     std::vector<uint8_t> rev, taken;
+    // the cluster report: the evidence of the hit that decided owner[i] / rev[i], the winning hit per level-2 candidate, the joins so far
+    bool report = false;
+    uint32_t pass_no = 0;
+    std::vector<hit_evidence> why;
+    std::vector<uint32_t> best_at;
+    std::vector<cluster_join> joins;
     uint32_t B = 0, batch_now = 0;
     request rq;
     double t_phase[5] = {0, 0, 0, 0, 0};                   // RATTLE_TIMING: round set-up, level-1 resolve, founders + request, level-2 resolve, end of pass
@@ -551,6 +618,7 @@ struct job {
         const uint32_t m = (uint32_t)items.size();
         owner.resize(m);
         rev.assign(m, 0);
+        if (report) why.assign(m, hit_evidence{0, 0, 0.0});
         remaining.resize(m);
         for (uint32_t i = 0; i < m; ++i) { owner[i] = i; remaining[i] = i; }
         phase = ROUND;
@@ -605,7 +673,23 @@ struct job {
         begin_pass(t);
     }
 
+    // one join per absorbed item of the pass that ends, in item order (items: local read ids -- the reads themselves in the initial
+    // pass, the clusters' representatives in a merge pass)
+    void emit_joins() {
+        for (uint32_t i = 0; i < items.size(); ++i) {
+            if (owner[i] == i) continue;
+            const uint32_t into = items[owner[i]], absorbed = items[i];
+            const hit_evidence &e = why[i];
+            const uint32_t li = rlen(into), lj = rlen(absorbed);
+            const double mn = (double)(li < lj ? li : lj);
+            const double score = P->use_hc ? (double)e.hc / mn : (double)e.bases / mn;      // the verdict's expression
+            joins.push_back(cluster_join{pass_no, thr, (int32_t)into, (int32_t)absorbed, rev[i], 0, e.bases, e.hc, li < lj ? li : lj, score, e.var});
+        }
+        ++pass_no;
+    }
+
     void end_pass() {
+        if (report) emit_joins();
         if (stage == INITIAL) {                                   // cluster.cpp:124-166
             std::vector<int32_t> slot(n, -1);
             std::vector<uint32_t> size(n, 0);
@@ -690,6 +774,7 @@ struct job {
                         taken[c] = 1;
                         owner[remaining[c]] = remaining[s];
                         rev[remaining[c]] = hits[q].rev;
+                        if (report) why[remaining[c]] = rq.ev[q];
                     }
                 }
                 phase = FOUNDERS;
@@ -724,11 +809,20 @@ struct job {
                 // founders in order, the first accepting founder wins, forward before reverse: the smallest (founder, strand)
                 // key per candidate, whatever order the hits arrive in
                 best.assign(nrest, 0xFFFFFFFFu);
-                for (const hit_t &q : rq.hits) best[q.cand] = std::min(best[q.cand], (q.seed << 1) | q.rev);
+                if (!report) for (const hit_t &q : rq.hits) best[q.cand] = std::min(best[q.cand], (q.seed << 1) | q.rev);
+                else {                                            // ... and which hit that was (a key occurs once per candidate)
+                    best_at.resize(nrest);
+                    for (uint32_t h = 0; h < rq.hits.size(); ++h) {
+                        const hit_t &q = rq.hits[h];
+                        const uint32_t key = (q.seed << 1) | q.rev;
+                        if (key < best[q.cand]) { best[q.cand] = key; best_at[q.cand] = h; }
+                    }
+                }
                 for (uint32_t c = 0; c < nrest; ++c) {
                     if (best[c] == 0xFFFFFFFFu) { next.push_back(remaining[B + c]); continue; }
                     owner[remaining[B + c]] = remaining[founders[best[c] >> 1]];
                     rev[remaining[B + c]] = (uint8_t)(best[c] & 1u);
+                    if (report) why[remaining[B + c]] = rq.ev[best_at[c]];
                 }
                 remaining.swap(next);
                 phase = ROUND;
@@ -740,7 +834,12 @@ struct job {
     }
 
     rattle_cluster_set *flatten() const {
-        rattle_cluster_set *R = (rattle_cluster_set *)calloc(1, sizeof(rattle_cluster_set));
+        rattle_cluster_set *R = new_cluster_set();
+        if (report) {
+            cluster_box *B = cluster_box_of(R);
+            B->joins = new std::vector<cluster_join>(joins);
+            B->has_report = true;
+        }
         size_t nm = 0;
         for (auto &c : clusters) nm += c.seqs.size();
         R->n_clusters = (uint32_t)clusters.size();
@@ -766,7 +865,7 @@ struct job {
 int run_jobs(rattle_ctx *ctx, const rattle_cluster_params *P, std::vector<job> &jobs, bool shard_level2) {
     evaluator E{ctx, P};
     std::vector<uint32_t> active(jobs.size());
-    for (uint32_t i = 0; i < jobs.size(); ++i) { active[i] = i; jobs[i].inner_parallel = jobs.size() == 1; jobs[i].start(); }
+    for (uint32_t i = 0; i < jobs.size(); ++i) { active[i] = i; jobs[i].inner_parallel = jobs.size() == 1; jobs[i].report = ctx->cluster_report; jobs[i].start(); }
     std::vector<request *> want, reqs;
     static const bool timing = getenv("RATTLE_TIMING") != nullptr;
     double t_steps = 0;
@@ -865,6 +964,13 @@ int debug_evaluate(rattle_ctx *ctx, const rattle_cluster_params *P, int count_mo
     size_t h = 0;
     for (uint32_t r = 0; r < n_rects; ++r)
         for (const hit_t &x : q[r].hits) put(D->hits, h++, eval_sink::pair{r, x.seed, x.cand, x.rev, 0});
+    if (ctx->cluster_report) {
+        D->hit_bases = (int32_t *)malloc(4 * std::max<size_t>(nh, 1)); D->hit_hc_bases = (int32_t *)malloc(4 * std::max<size_t>(nh, 1));
+        D->hit_variance = (double *)malloc(8 * std::max<size_t>(nh, 1));
+        h = 0;
+        for (uint32_t r = 0; r < n_rects; ++r)
+            for (const hit_evidence &e : q[r].ev) { D->hit_bases[h] = e.bases; D->hit_hc_bases[h] = e.hc; D->hit_variance[h] = e.var; ++h; }
+    }
     D->counters = (uint64_t *)malloc(counters.size() * 8);
     memcpy(D->counters, counters.data(), counters.size() * 8);
     D->count_pass = sink.count_pass;

@@ -283,6 +283,28 @@ correction_box *box_of(const rattle_correction *c);
 void alloc_report(correction_box *B, size_t n);                      // the arrays (never null pointers), has_report = true
 void print_report_totals(const rattle_correction *c, const char *what);      // RATTLE_TIMING=1: the six totals on stderr
 
+// The cluster report.  The verdict kernel's report form writes an evidence record (hit_evidence) beside every accepted pair; the greedy
+// driver keeps the record of the hit that decided each absorption and emits one join per absorbed item at the end of a pass.
+struct hit_evidence { int32_t bases, hc; double var; };      // 16 bytes, the layout the kernel writes
+struct cluster_join {
+    uint32_t pass;                      // 0: the initial pass, 1 ..: the merge passes
+    double thr;                         // bit-vector threshold of the pass
+    int32_t into, absorbed;             // ids in the id space of the set's member_id
+    uint8_t rev, level;
+    int32_t bases, hc;
+    uint32_t min_len;
+    double score, variance;
+};
+// A rattle_cluster_set the library hands out is the head of this box, as a rattle_correction is the head of a correction_box: the joins
+// lie behind the public struct, and the library's list of its boxes tells a set a caller built itself apart (cluster_box_of: null).
+struct cluster_box {
+    rattle_cluster_set pub;
+    bool has_report;
+    std::vector<cluster_join> *joins;   // owned; null without a report
+};
+rattle_cluster_set *new_cluster_set();
+cluster_box *cluster_box_of(const rattle_cluster_set *cs);
+
 int hw_queues();      // hardware queues the HIP runtime of this process hands out (settled when the library is loaded, abi.hip)
 
 }  // namespace rattle
@@ -316,6 +338,11 @@ struct rattle_ctx {
     rattle::dbuf<uint32_t> d_scratch;       // global scratch for oversize pairs
     rattle::hbuf<uint32_t> h_surv;
     rattle::hbuf<uint32_t> h_counter;
+    // the cluster report (rattle_hip_set_cluster_report; never allocated while it is off): the evidence record of every accepted pair,
+    // parallel to the accepted pairs in d_surv / h_surv
+    bool cluster_report = false;
+    rattle::dbuf<rattle::hit_evidence> d_hit_ev;
+    rattle::hbuf<rattle::hit_evidence> h_hit_ev;
     // POA arena: kept across stages and calls (allocating ~100 GB costs seconds)
     uint8_t *poa_arena = nullptr;
     size_t poa_arena_bytes = 0;

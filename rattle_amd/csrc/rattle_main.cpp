@@ -605,9 +605,12 @@ int mode_cluster(int argc, char **argv) {
         {"rna", {"--rna"}, false}, {"verbose", {"--verbose"}, false}, {"raw", {"--raw"}, false},
         {"lower_len", {"--lower-length"}, true}, {"upper_len", {"--upper-length"}, true}, {"device", {"--device"}, true},
         {"devices", {"--devices"}, true}, {"host-exchange", {"--host-exchange"}, false}, {"write-unzipped", {"--write-unzipped"}, false},
-        {"count-pass", {"--count-pass"}, true}};
+        {"count-pass", {"--count-pass"}, true}, {"report", {"--report"}, false}};
     args_t a = parse(argc, argv, defs);
     const char *usage = "rattle cluster -i reads.fq [-o dir] [--rna] [--iso] ... (flags of RATTLE's cluster mode)\n"
+                        "  --report           also write cluster_report.tsv: one line per join (a read joining a cluster's founder, or a cluster\n"
+                        "                     joining another through their representatives) with the comparison that decided it: pass,\n"
+                        "                     bit-vector threshold, strand, bases, hc_bases, min_len, score, variance (one device only)\n"
                         "  --devices 0,1,..   one job over several GPUs (RCCL; --host-exchange: in-process exchange on host buffers)\n"
                         "  --count-pass auto|seed|search|index   form of the count pass (what RATTLE_PAIR_COUNT sets; default auto)\n";
     if (a.has("count-pass")) {
@@ -631,6 +634,9 @@ int mode_cluster(int argc, char **argv) {
     std::string outdir = a.str("output", ".");
     if (a.has("output") && access(outdir.c_str(), F_OK)) die("\nOutput folder doesn't exit. Please create it first. \n");
     bool is_rna = a.has("rna");
+    const bool want_report = a.has("report");
+    if (want_report && a.has("devices") && split_string(a.str("devices", ""), ',').size() > 1)
+        die("\nError: --report cannot be combined with --devices naming more than one device: the cluster report is made on one device\n");
     std::cerr << "RNA mode: " << std::boolalpha << is_rna << std::endl;
     std::cerr << "Reading fasta file... " << std::endl;
     device_team team;
@@ -682,7 +688,39 @@ int mode_cluster(int argc, char **argv) {
     P.min_reads_cluster = a.i("min_reads_cluster", 0); P.use_hc = 0; P.repr_percentile = a.d("repr_percentile", 0.15);
     P.is_rna = is_rna ? 1 : 0;
     rattle_cluster_set *raw = nullptr;
+    // cluster_report.tsv: one line per join, in the library's order; ids_of: the set's ids -> processing positions (null: identity)
+    std::string report_text = "level\tpass\tbv_threshold\tabsorbed\tinto\tstrand\tbases\thc_bases\tmin_len\tscore\tvariance\n";
+    auto report_rows = [&](const rattle_cluster_set *cs, int level, const cseq_t *ids_of) {
+        rattle_cluster_report *rp = nullptr;
+        chk(rattle_hip_cluster_report(cs, &rp));
+        auto name = [&](int32_t id) {                                           // the id: the header's first token, without its '@' / '>'
+            const span &h = T.header[order[ids_of ? (uint32_t)ids_of[id].seq_id : (uint32_t)id]];
+            const char *b = h.p, *e = h.p + h.n;
+            if (b < e && (*b == '@' || *b == '>')) ++b;
+            const char *t = b;
+            while (t < e && *t != ' ' && *t != '\t') ++t;
+            return std::string(b, t - b);
+        };
+        char num[3][40];
+        for (uint64_t i = 0; i < rp->n; ++i) {
+            snprintf(num[0], sizeof num[0], "%.17g", rp->bv_threshold[i]);
+            snprintf(num[1], sizeof num[1], "%.17g", rp->score[i]);
+            snprintf(num[2], sizeof num[2], "%.17g", rp->variance[i]);
+            report_text += std::to_string(level) + "\t" + std::to_string(rp->pass[i]) + "\t" + num[0] + "\t" + name(rp->absorbed[i]) + "\t" +
+                           name(rp->into[i]) + "\t" + (rp->rev[i] ? "-" : "+") + "\t" + std::to_string(rp->bases[i]) + "\t" +
+                           std::to_string(rp->hc_bases[i]) + "\t" + std::to_string(rp->min_len[i]) + "\t" + num[1] + "\t" + num[2] + "\n";
+        }
+        rattle_hip_cluster_report_free(rp);
+    };
+    auto write_report = [&]() {
+        const std::string path = outdir + "/cluster_report.tsv";
+        std::ofstream f(path);
+        f << report_text;
+        f.close();
+        if (!f) die("Error: cannot write " + path);
+    };
     team.run([&](int r, rattle_ctx *ctx) {                                      // every rank ends up with the same clusters
+        if (want_report) chk(rattle_hip_set_cluster_report(ctx, 1));
         chk(rattle_hip_load_reads(ctx, cat.data(), off.data(), n_reads, k, is_rna ? 0 : 1));
         rattle_cluster_set *mine = nullptr;
         chk(rattle_hip_cluster_reads(ctx, &P, &mine));
@@ -690,6 +728,7 @@ int mode_cluster(int argc, char **argv) {
     });
     t_lib.reset();
     cli_timer t_out("to clusters.out");
+    if (want_report) report_rows(raw, 0, nullptr);
     cluster_set_t gene = to_set(raw);
     std::cerr << "Gene clustering done" << std::endl;
     std::cerr << gene.size() << " gene clusters found" << std::endl;
@@ -700,6 +739,7 @@ int mode_cluster(int argc, char **argv) {
             for (auto &s : c.seqs) s.seq_id = (int)order[s.seq_id];
         }
         write_clusters(gene, out_path);
+        if (want_report) write_report();
         team.close();
         return EXIT_SUCCESS;
     }
@@ -725,6 +765,7 @@ int mode_cluster(int argc, char **argv) {
     });
     int gi = 0;
     for (auto &c : gene) {
+        if (want_report) report_rows(subs[gi], 1, c.seqs.data());
         for (auto &ic : to_set(subs[gi])) {
             cluster_t o;
             o.main_seq = cseq_t{(int)order[c.seqs[ic.main_seq.seq_id].seq_id], ic.main_seq.rev, gi};
@@ -736,6 +777,7 @@ int mode_cluster(int argc, char **argv) {
     std::cerr << "Isoform clustering done" << std::endl;
     std::cerr << iso.size() << " isoform clusters found" << std::endl;
     write_clusters(iso, out_path);
+    if (want_report) write_report();
     team.close();
     return EXIT_SUCCESS;
 }
