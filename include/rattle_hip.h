@@ -317,6 +317,38 @@ int rattle_hip_set_correction_report(rattle_ctx *ctx, int on);
 int rattle_hip_correction_report(const rattle_correction *c, rattle_correction_report **out);
 void rattle_hip_correction_report_free(rattle_correction_report *r);
 
+/* The consensus support: how many reads stand behind every base of every consensus.  Off by default;
+ * rattle_hip_set_consensus_support(ctx, 1) makes the consensus stages of the following rattle_hip_correct_reads calls on this context
+ * launch the report form of the post-MSA kernel's mode 2.  For every record of `consensi` and every base j of it, two values counted
+ * in READS, support[j] <= depth[j] and depth[j] >= 1:
+ *   level 2, the consensus of one pack (POA #2 over its corrected reads + the column vote).  Base j is the winner of a column k;
+ *     depth = the rows whose voting window after fix_msa_ends covers k, gaps included (the vote's total), support = the winner's
+ *     count.  The rows are corrected reads.  A cluster with a single queued pack takes that pack's consensus as its own
+ *     (correct.cpp:547-549) and its support with it; a pack consensus that is a copy of a single sequence (min_reads = 0, what
+ *     `polish` uses) has 1 / 1 for every base.
+ *   level 3, the consensus of a cluster of several packs (POA #3 over its pack consensi + the column vote).  Row i is pack consensus
+ *     i with its level-2 values sup_i[], dep_i[] per base.  Base j is the winner w of a column K; of the rows whose window
+ *     [rfirst_i, rlast_i] covers K, support[j] is the sum of sup_i[b] over the rows that hold w at K (b: that base's index in row
+ *     i), and depth[j] the sum of dep_i[b'] over all of them, b' being the row's base at K or, where the row has '-' at K, the row's
+ *     last base at a column below K (it exists: a window starts on a base).
+ * pack_support / pack_depth are the vote's own winner count / total of the column, in rows of the last MSA: equal to support / depth
+ * at level 2, counts of pack consensi at level 3.  A cluster whose POA #3 was skipped has no consensus and so no record.
+ * No output of correct_reads changes with the switch.  The values travel inside the result object, behind the public struct;
+ * rattle_hip_consensus_support copies them out (release with rattle_hip_consensus_support_free).  RATTLE_ERR_STATE if the correction
+ * was made with the switch off or is not an object of this library.  Sharded jobs carry no support yet: with the switch on, a context
+ * that is one rank of several gets RATTLE_ERR_STATE from rattle_hip_correct_reads before anything is exchanged, on every rank alike,
+ * and the result of rattle_hip_correction_gather has none. */
+typedef struct {
+    uint32_t n;                 /* == consensi.n, parallel to consensi.read_id */
+    uint8_t  *level;            /* 2: the votes of POA #2 (one pack), 3: composed through POA #3 */
+    uint64_t *off;              /* [n+1], == consensi.off */
+    uint32_t *support, *depth;  /* per base, reads */
+    uint32_t *pack_support, *pack_depth;   /* per base, rows of the last MSA */
+} rattle_consensus_support;
+int  rattle_hip_set_consensus_support(rattle_ctx *ctx, int on);
+int  rattle_hip_consensus_support(const rattle_correction *c, rattle_consensus_support **out);
+void rattle_hip_consensus_support_free(rattle_consensus_support *s);
+
 /* Optional: allocate the POA arena of correct_reads ahead of time (a caller can overlap the seconds a > 100 GB allocation takes
  * with reading its input).  bytes is a hint, clamped to what the device has free; correct_reads grows the arena if it must. */
 int rattle_hip_reserve_arena(rattle_ctx *ctx, uint64_t bytes);
@@ -465,6 +497,36 @@ typedef struct {
 int rattle_hip_debug_post_msa(rattle_ctx *ctx, const rattle_correct_params *params, int mode /* 1 | 2 */, const rattle_debug_msa *in,
                               rattle_debug_post **out);
 void rattle_hip_debug_post_msa_free(rattle_debug_post *p);
+
+/* Test hook: the report form of the post-MSA kernel's mode 2 (the consensus support) ALONE on given MSAs, through the driver's own
+ * stage layout and launch.  The MSAs are given and checked as for rattle_hip_debug_post_msa.  sup / dep: a support and a depth for
+ * every base, which makes every pack a level-3 pack (rows that are pack consensi); both NULL: level 2 (rows that are reads).
+ * Returns per pack the consensus (cons_len[p] bytes at coff[p]) and, at the same index, support and depth of every base -- at level 3
+ * also pack_support and pack_depth, at level 2 they are NULL.  On a context with rattle_hip_set_consensus_support off all four are
+ * NULL.  Only vote_order of params is read. */
+typedef struct {
+    uint32_t n_packs;
+    const uint32_t *pack_first;   /* [n_packs+1] row range of each pack, pack_first[0] == 0 */
+    const uint32_t *width;        /* [n_packs]   MSA columns */
+    const uint64_t *off;          /* [n_rows+1]  base range of each row, off[0] == 0 */
+    const uint8_t *seq;           /* bases of all rows back to back */
+    const uint32_t *col;          /* [n_bases]   MSA column of every base */
+    const uint32_t *sup, *dep;    /* [n_bases]   support / depth of every base, or both NULL */
+} rattle_debug_support_msa;
+
+typedef struct {
+    uint32_t n_packs;
+    int level;                    /* 2 | 3 */
+    uint64_t n_cols;              /* sum of the widths */
+    uint64_t *coff;               /* [n_packs] where the pack's consensus and its values start */
+    uint32_t *cons_len;           /* [n_packs] */
+    uint8_t *consensus;           /* [n_cols] */
+    uint32_t *support, *depth, *pack_support, *pack_depth;   /* [n_cols] */
+} rattle_debug_support;
+
+int rattle_hip_debug_consensus_support(rattle_ctx *ctx, const rattle_correct_params *params, const rattle_debug_support_msa *in,
+                                       rattle_debug_support **out);
+void rattle_hip_debug_consensus_support_free(rattle_debug_support *d);
 
 /* ------------------------------------------------------------------------------------
  * Per-kernel timing measured with HIP events on the stream the kernels run on.

@@ -100,6 +100,27 @@ class CorrectionReport(C.Structure):
     _fields_ = [("n", C.c_uint32)] + [(f, C.POINTER(C.c_uint32)) for f in REPORT_FIELDS]
 
 
+# the consensus support (rattle_consensus_support): four values per base of the consensi
+SUPPORT_FIELDS = ("support", "depth", "pack_support", "pack_depth")
+
+
+class ConsensusSupport(C.Structure):
+    _fields_ = [("n", C.c_uint32), ("level", C.POINTER(C.c_uint8)), ("off", C.POINTER(C.c_uint64))] + \
+               [(f, C.POINTER(C.c_uint32)) for f in SUPPORT_FIELDS]
+
+
+class DebugSupportMsa(C.Structure):
+    _fields_ = [("n_packs", C.c_uint32), ("pack_first", C.POINTER(C.c_uint32)), ("width", C.POINTER(C.c_uint32)),
+                ("off", C.POINTER(C.c_uint64)), ("seq", C.POINTER(C.c_uint8)), ("col", C.POINTER(C.c_uint32)),
+                ("sup", C.POINTER(C.c_uint32)), ("dep", C.POINTER(C.c_uint32))]
+
+
+class DebugSupport(C.Structure):
+    _fields_ = [("n_packs", C.c_uint32), ("level", C.c_int), ("n_cols", C.c_uint64), ("coff", C.POINTER(C.c_uint64)),
+                ("cons_len", C.POINTER(C.c_uint32)), ("consensus", C.POINTER(C.c_uint8))] + \
+               [(f, C.POINTER(C.c_uint32)) for f in SUPPORT_FIELDS]
+
+
 # the cluster report (rattle_cluster_report): one entry per join
 CLUSTER_REPORT_FIELDS = (("level", C.c_uint8), ("pass", C.c_uint32), ("bv_threshold", C.c_double), ("into", C.c_int32),
                          ("absorbed", C.c_int32), ("rev", C.c_uint8), ("bases", C.c_int32), ("hc_bases", C.c_int32),
@@ -160,6 +181,11 @@ SIGNATURES = {
     "rattle_hip_set_correction_report": (C.c_int, [C.c_void_p, C.c_int]),
     "rattle_hip_correction_report": (C.c_int, [_P(Correction), _P(_P(CorrectionReport))]),
     "rattle_hip_correction_report_free": (None, [_P(CorrectionReport)]),
+    "rattle_hip_set_consensus_support": (C.c_int, [C.c_void_p, C.c_int]),
+    "rattle_hip_consensus_support": (C.c_int, [_P(Correction), _P(_P(ConsensusSupport))]),
+    "rattle_hip_consensus_support_free": (None, [_P(ConsensusSupport)]),
+    "rattle_hip_debug_consensus_support": (C.c_int, [C.c_void_p, _P(CorrectParams), _P(DebugSupportMsa), _P(_P(DebugSupport))]),
+    "rattle_hip_debug_consensus_support_free": (None, [_P(DebugSupport)]),
     "rattle_hip_reserve_arena": (C.c_int, [C.c_void_p, C.c_uint64]),
     "rattle_hip_set_exchange": (C.c_int, [C.c_void_p, C.c_int, C.c_int, ALLGATHERV_FN, C.c_void_p]),
     "rattle_hip_comm_unique_id": (C.c_int, [_u8p]),

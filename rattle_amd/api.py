@@ -122,11 +122,44 @@ def correction_report(lib, ptr) -> Optional[dict]:
     return res
 
 
+def consensus_support(lib, ptr) -> Optional[dict]:
+    """The consensus support of a library-owned rattle_correction (pointer) as a dict of arrays: level (uint8, per record of
+    `consensi`), off (uint64, [n + 1], == consensi.off) and support, depth, pack_support, pack_depth (uint32, per base); None if the
+    correction was made with the support off (Context.set_consensus_support)."""
+    out = C.POINTER(_lib.ConsensusSupport)()
+    rc = lib.rattle_hip_consensus_support(ptr, C.byref(out))
+    if rc == _lib.RATTLE_ERR_STATE:
+        return None
+    check(rc)
+    S = out.contents
+    n = int(S.n)
+    res = {"level": np.ctypeslib.as_array(S.level, (max(n, 1),))[:n].copy(), "off": np.ctypeslib.as_array(S.off, (n + 1,)).copy()}
+    tot = int(res["off"][n])
+    res.update({f: np.ctypeslib.as_array(getattr(S, f), (max(tot, 1),))[:tot].copy() for f in _lib.SUPPORT_FIELDS})
+    lib.rattle_hip_consensus_support_free(out)
+    return res
+
+
+def support_tsv(names: Sequence[bytes], n_reads: Sequence[int], sup: dict) -> bytes:
+    """consensus_support.tsv as `rattle correct --support` writes it: one line per consensus (names: the first token of its header,
+    n_reads: its `reads=`): consensus, length, level, reads, min_ratio (the smallest support / depth, %.17g), weak (bases with
+    2 * support <= depth), support and depth as comma-separated per-base lists."""
+    lines = [b"consensus\tlength\tlevel\treads\tmin_ratio\tweak\tsupport\tdepth\n"]
+    for i, name in enumerate(names):
+        a, b = int(sup["off"][i]), int(sup["off"][i + 1])
+        s, d = sup["support"][a:b], sup["depth"][a:b]
+        ratio = float(np.min(s.astype(np.float64) / d.astype(np.float64))) if b > a else 0.0
+        lines.append(b"%s\t%d\t%d\t%d\t%s\t%d\t%s\t%s\n" % (name, b - a, int(sup["level"][i]), int(n_reads[i]), ("%.17g" % ratio).encode(),
+                                                             int(np.sum(2 * s.astype(np.uint64) <= d)), ",".join(map(str, s)).encode(),
+                                                             ",".join(map(str, d)).encode()))
+    return b"".join(lines)
+
+
 def unpack_correction(R) -> dict:
     """rattle_correction (the struct or a pointer to it) -> dict of record lists (read_id, cluster_id, n_reads, seq, qual), counters,
     skip list and, when the correction carries one, the correction report under "report" (a dict of uint32 arrays parallel to
-    "corrected").  The report lives behind the library's own object, so it is found for `ptr.contents` of a result the library
-    returned, not for a copy of the struct."""
+    "corrected") and the consensus support under "support" (consensus_support).  Both live behind the library's own object, so they
+    are found for `ptr.contents` of a result the library returned, not for a copy of the struct."""
     if hasattr(R, "contents"):
         R = R.contents
     def unpack(S):
@@ -150,6 +183,9 @@ def unpack_correction(R) -> dict:
                             "reads": [int(x) for x in rid[int(ro[i]):int(ro[i + 1])]]})
     res = {"corrected": unpack(R.corrected), "uncorrected": unpack(R.uncorrected), "consensi": unpack(R.consensi),
            "counters": np.array(list(R.counters), dtype=np.uint64), "skipped": skipped}
+    support = consensus_support(_lib.load(), C.pointer(R))
+    if support is not None:
+        res["support"] = support
     report = correction_report(_lib.load(), C.pointer(R))
     if report is not None:
         res["report"] = report
@@ -199,6 +235,13 @@ class CorrectionHandle:
             raise _lib.RattleError(f"librattle_hip error {_lib.RATTLE_ERR_STATE}: {lib.rattle_hip_last_error().decode()}")
         return res
 
+    def support(self):
+        """The consensus support (consensus_support): a dict of arrays, or None if the correction was made with the support off
+        (Context.set_consensus_support)."""
+        if self.ptr is None:
+            return None
+        return consensus_support(self.lib or _lib.load(), self.ptr)
+
     def host_bytes(self):
         """bases + qualities held by the three read sets (what free() gives back to the OS)"""
         if self.ptr is None:
@@ -232,6 +275,7 @@ class Context:
         self.both = False
         self.k = 0
         self.cluster_report = False
+        self.consensus_support = False
 
     def close(self):
         if self.h:
@@ -253,6 +297,12 @@ class Context:
     def set_correction_report(self, on: bool):
         """Switch the per-read correction report of the following correct_* / debug_post_msa calls on or off (off by default)."""
         check(self.lib.rattle_hip_set_correction_report(self.h, int(bool(on))))
+
+    def set_consensus_support(self, on: bool):
+        """Switch the per-base support of the consensi of the following correct_* calls (and what debug_consensus_support returns) on
+        or off (off by default): CorrectionHandle.support(), the "support" key of correct_reads."""
+        check(self.lib.rattle_hip_set_consensus_support(self.h, int(bool(on))))
+        self.consensus_support = bool(on)
 
     # a3
     def load_reads(self, seqs: Sequence[bytes], k: int, both_strands: bool):
@@ -616,6 +666,49 @@ class Context:
             res.append(d)
         return res
 
+    def debug_consensus_support(self, packs, sup=None, dep=None, vote_order: bytes = b""):
+        """The mode-2 report form of kernel D alone on given MSAs (rattle_hip_debug_consensus_support, a test hook), all packs in one
+        launch.  packs as for debug_post_msa (qualities ignored); sup / dep: per pack, per row, a uint32 array with one value per base
+        (both None: rows that are reads, level 2).  Returns one dict per pack: consensus (bytes) and support, depth, pack_support,
+        pack_depth (uint32 per base of the consensus; None where the hook returns NULL: all four with set_consensus_support off,
+        the pack_* pair at level 2)."""
+        first = np.zeros(len(packs) + 1, np.uint32)
+        first[1:] = np.cumsum([len(p[1]) for p in packs])
+        width = np.array([p[0] for p in packs] + [0], np.uint32)
+        cat, off = pack_reads([s for p in packs for s in p[1]])
+        col = np.concatenate([np.asarray(c, np.uint32) for p in packs for c in p[2]] + [np.zeros(1, np.uint32)])
+        assert len(col) == len(cat) + 1, "one column per base"
+        assert (sup is None) == (dep is None)
+        vals = []
+        for v in (sup, dep):
+            if v is not None:
+                v = np.concatenate([np.asarray(r, np.uint32) for p in v for r in p] + [np.zeros(1, np.uint32)])
+                assert len(v) == len(cat) + 1, "one support and one depth per base"
+            vals.append(v)
+        M = _lib.DebugSupportMsa(len(packs), _ptr(first, C.c_uint32), _ptr(width, C.c_uint32), _ptr(off, C.c_uint64),
+                                 _ptr(cat, C.c_uint8) if len(cat) else None, _ptr(col, C.c_uint32),
+                                 None if vals[0] is None else _ptr(vals[0], C.c_uint32), None if vals[1] is None else _ptr(vals[1], C.c_uint32))
+        P, _ = correct_params(vote_order=vote_order)
+        out = C.POINTER(_lib.DebugSupport)()
+        check(self.lib.rattle_hip_debug_consensus_support(self.h, C.byref(P), C.byref(M), C.byref(out)))
+        D = out.contents
+        npk, ncol = D.n_packs, int(D.n_cols)
+
+        def arr(ptr, n):
+            return np.ctypeslib.as_array(ptr, (max(int(n), 1),))[:int(n)].copy() if ptr else None
+
+        coff, clen, cons = arr(D.coff, npk), arr(D.cons_len, npk), arr(D.consensus, ncol)
+        fields = {f: arr(getattr(D, f), ncol) for f in _lib.SUPPORT_FIELDS}
+        level = D.level
+        self.lib.rattle_hip_debug_consensus_support_free(out)
+        res = []
+        for p in range(npk):
+            a, b = int(coff[p]), int(coff[p]) + int(clen[p])
+            d = {"level": level, "consensus": cons[a:b].tobytes()}
+            d.update({f: None if v is None else v[a:b] for f, v in fields.items()})
+            res.append(d)
+        return res
+
     def kernel_stats(self, kernel: int):
         ms = C.c_double(); n = C.c_uint64(); b = C.c_uint64()
         check(self.lib.rattle_hip_kernel_stats(self.h, kernel, C.byref(ms), C.byref(n), C.byref(b)))
@@ -704,14 +797,22 @@ def _cluster_command(ctx, seqs, ann, k, t_s, t_v, iso, iso_k, iso_t_s, iso_t_v, 
 def correct_command(ctx: Context, headers: Sequence[bytes], seqs: Sequence[bytes], quals: Sequence[bytes], clusters, *,
                     min_occ=0.3, gap_occ=0.3, split=200, min_reads=5, n_threads=0, vote_order=b"", pack_order=None,
                     ann: Optional[Sequence[bytes]] = None, max_pack_cells=0, gather_root: Optional[int] = None,
-                    with_skipped=False):
+                    with_skipped=False, support=False):
     """`rattle correct` after input parsing (main.cpp:396-408): returns the three FASTQ texts
     (corrected, uncorrected, consensi) with the headers correct.cpp:348-353,540-549 builds
     (no -l labels: `labels=` is empty).  `ann` = the third line of each input record: uncorrected reads
     keep theirs (the reference pushes the original read_t, correct.cpp:362-366,289-293); corrected reads
-    and consensi get "+" (:286, :469)."""
-    res = ctx.correct_reads(seqs, quals, clusters, min_occ, gap_occ, 30.0, split, min_reads, n_threads, vote_order, pack_order,
-                            max_pack_cells, gather_root)
+    and consensi get "+" (:286, :469).  support=True: the call runs with the context's consensus support on (one device) and the
+    text of consensus_support.tsv (support_tsv) is appended to the result."""
+    was = ctx.consensus_support
+    if support:
+        ctx.set_consensus_support(True)
+    try:
+        res = ctx.correct_reads(seqs, quals, clusters, min_occ, gap_occ, 30.0, split, min_reads, n_threads, vote_order, pack_order,
+                                max_pack_cells, gather_root)
+    finally:
+        if support:
+            ctx.set_consensus_support(was)
     if res is None:
         return None
     gene_mode = len(clusters) == 0 or clusters[0][0][2] == -1
@@ -734,4 +835,9 @@ def correct_command(ctx: Context, headers: Sequence[bytes], seqs: Sequence[bytes
             h = b"@transcript_cluster_%d gene_cluster_%d reads=%d labels=" % (cid, clusters[cid][0][2], nr)
         cons.append(b"%s\n%s\n+\n%s\n" % (h, s, q))
     out = (fq(res["corrected"], False), fq(res["uncorrected"], True), b"".join(cons), res["counters"])
-    return out + (res["skipped"],) if with_skipped else out
+    if with_skipped:
+        out = out + (res["skipped"],)
+    if support:
+        names = [(b"gene_cluster_%d" if gene_mode else b"transcript_cluster_%d") % r[1] for r in res["consensi"]]
+        out = out + (support_tsv(names, [r[2] for r in res["consensi"]], res["support"]),)
+    return out

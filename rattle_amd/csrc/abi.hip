@@ -94,6 +94,24 @@ void alloc_report(correction_box *B, size_t n) {
     B->has_report = true;
 }
 
+void alloc_support(correction_box *B, size_t n, size_t bases) {
+    free(B->sup_level); B->sup_level = (uint8_t *)calloc(std::max<size_t>(1, n), 1);
+    for (int f = 0; f < SUP_FIELDS; ++f) { free(B->sup[f]); B->sup[f] = (uint32_t *)calloc(std::max<size_t>(1, bases), 4); }
+    B->has_support = true;
+}
+
+void print_support_totals(const rattle_correction *c) {
+    static const bool enabled = getenv("RATTLE_TIMING") != nullptr;
+    const correction_box *B = enabled ? box_of(c) : nullptr;
+    if (!B || !B->has_support) return;
+    const rattle_read_set &S = c->consensi;
+    uint64_t sup = 0, dep = 0, weak = 0, composed = 0;
+    for (uint64_t b = 0; b < S.off[S.n]; ++b) { sup += B->sup[SUP_SUPPORT][b]; dep += B->sup[SUP_DEPTH][b]; weak += 2ull * B->sup[SUP_SUPPORT][b] <= B->sup[SUP_DEPTH][b]; }
+    for (uint32_t i = 0; i < S.n; ++i) composed += B->sup_level[i] == 3;
+    fprintf(stderr, "[rattle] consensus support: %u consensi (%llu composed through POA #3), %llu bases, support %llu of depth %llu, %llu weak bases\n", S.n,
+            (unsigned long long)composed, (unsigned long long)S.off[S.n], (unsigned long long)sup, (unsigned long long)dep, (unsigned long long)weak);
+}
+
 void print_report_totals(const rattle_correction *c, const char *what) {
     static const bool enabled = getenv("RATTLE_TIMING") != nullptr;
     const correction_box *B = enabled ? box_of(c) : nullptr;
@@ -612,6 +630,12 @@ int rattle_hip_correct_reads(rattle_ctx *c, const uint8_t *seq, const uint8_t *q
     }
     *out = nullptr;
     RT_TRY(use_device(c));
+    // The consensus support does not travel through the exchange of a sharded job yet: refused on every rank alike, before any collective
+    if (c->consensus_support && c->xchg.nranks > 1) {
+        set_error("the consensus support (rattle_hip_set_consensus_support) is not available on a context that is one rank of several: "
+                  "switch it off on every rank, or correct on one device");
+        return RATTLE_ERR_STATE;
+    }
     {
         // A context that clustered its reads still holds their k-mer index (12-20 bytes per base) and kernel B's work lists; `correct`
         // uses none of it and sizes its arena by what is free.  Beyond 24 GB the index goes first (3e6 mixed reads: 72 GB of it beside the
@@ -656,6 +680,8 @@ void rattle_hip_correction_free(rattle_correction *r) {
     if (!r) return;
     if (correction_box *B = box_of(r)) {
         for (int f = 0; f < REP_FIELDS; ++f) free(B->rep[f]);
+        for (int f = 0; f < SUP_FIELDS; ++f) free(B->sup[f]);
+        free(B->sup_level);
         std::lock_guard<std::mutex> g(g_box_mu);
         boxes().erase(r);
     }
@@ -697,6 +723,44 @@ void rattle_hip_correction_report_free(rattle_correction_report *r) {
     free(r->in_len); free(r->out_len); free(r->trim_front); free(r->trim_back); free(r->match); free(r->substituted);
     free(r->mismatch_kept); free(r->inserted); free(r->deleted); free(r->gap_kept);
     free(r);
+}
+
+int rattle_hip_set_consensus_support(rattle_ctx *c, int on) {
+    if (!c) { set_error("null ctx"); return RATTLE_ERR_ARG; }
+    c->consensus_support = on != 0;
+    return 0;
+}
+
+int rattle_hip_consensus_support(const rattle_correction *c, rattle_consensus_support **out) {
+    if (out) *out = nullptr;
+    if (!c || !out) { set_error("null argument"); return RATTLE_ERR_ARG; }
+    const correction_box *B = box_of(c);
+    if (!B || !B->has_support) {
+        set_error("this correction carries no consensus support: rattle_hip_set_consensus_support(ctx, 1) comes before rattle_hip_correct_reads, on one device, "
+                  "and the correction must be one this library returned");
+        return RATTLE_ERR_STATE;
+    }
+    rattle_consensus_support *R = (rattle_consensus_support *)calloc(1, sizeof(rattle_consensus_support));
+    const rattle_read_set &S = c->consensi;
+    const size_t n = S.n, bases = S.off[n];
+    R->n = (uint32_t)n;
+    R->level = (uint8_t *)malloc(std::max<size_t>(1, n));
+    R->off = (uint64_t *)malloc((n + 1) * 8);
+    if (n) memcpy(R->level, B->sup_level, n);
+    memcpy(R->off, S.off, (n + 1) * 8);
+    uint32_t **dst[SUP_FIELDS] = {&R->support, &R->depth, &R->pack_support, &R->pack_depth};
+    for (int f = 0; f < SUP_FIELDS; ++f) {
+        *dst[f] = (uint32_t *)malloc(std::max<size_t>(1, bases) * 4);
+        if (bases) memcpy(*dst[f], B->sup[f], bases * 4);
+    }
+    *out = R;
+    return 0;
+}
+
+void rattle_hip_consensus_support_free(rattle_consensus_support *s) {
+    if (!s) return;
+    free(s->level); free(s->off); free(s->support); free(s->depth); free(s->pack_support); free(s->pack_depth);
+    free(s);
 }
 
 // Test hook (no device needed): the value of `-10*log10(p)+33` before the narrowing to char, once through the
@@ -742,9 +806,9 @@ void rattle_hip_debug_evaluate_free(rattle_debug_eval *e) {
     free(e);
 }
 
-int rattle_hip_debug_post_msa(rattle_ctx *c, const rattle_correct_params *P, int mode, const rattle_debug_msa *in, rattle_debug_post **out) {
-    if (!c || !P || !in || !out || !in->pack_first || !in->off || (in->n_packs && !in->width)) { set_error("null argument"); return RATTLE_ERR_ARG; }
-    *out = nullptr;
+// what the kernel D test hooks require of an MSA before anything of it reaches the device
+static int check_debug_msa(const rattle_debug_msa *in, int mode) {
+    if (!in->pack_first || !in->off || (in->n_packs && !in->width)) { set_error("null argument"); return RATTLE_ERR_ARG; }
     if (mode != 1 && mode != 2) { set_error("mode must be 1 (after POA #1: correction) or 2 (after POA #2 / #3: consensus)"); return RATTLE_ERR_ARG; }
     const uint32_t np = in->n_packs;
     if (in->pack_first[0] != 0 || in->off[0] != 0) { set_error("pack_first and off must start at 0"); return RATTLE_ERR_ARG; }
@@ -764,6 +828,13 @@ int rattle_hip_debug_post_msa(rattle_ctx *c, const rattle_correct_params *P, int
                 if (b > in->off[q] && in->col[b] <= in->col[b - 1]) { set_error("row " + std::to_string(q) + ": columns are not strictly increasing"); return RATTLE_ERR_ARG; }
             }
     }
+    return 0;
+}
+
+int rattle_hip_debug_post_msa(rattle_ctx *c, const rattle_correct_params *P, int mode, const rattle_debug_msa *in, rattle_debug_post **out) {
+    if (!c || !P || !in || !out) { set_error("null argument"); return RATTLE_ERR_ARG; }
+    *out = nullptr;
+    RT_TRY(check_debug_msa(in, mode));
     RT_TRY(use_device(c));
     int rc = debug_post_msa(c, P, mode, in, out);
     if (rc != 0 && *out) { rattle_hip_debug_post_msa_free(*out); *out = nullptr; }
@@ -775,6 +846,24 @@ void rattle_hip_debug_post_msa_free(rattle_debug_post *d) {
     free(d->moff); free(d->coff); free(d->rfirst); free(d->rlast); free(d->tfront); free(d->tback); free(d->olen); free(d->out_off);
     free(d->out_seq); free(d->out_qual); free(d->cons); free(d->flag); free(d->sym); free(d->err); free(d->cons_len); free(d->consensus);
     free(d->match); free(d->substituted); free(d->mismatch_kept); free(d->inserted); free(d->deleted); free(d->gap_kept);
+    free(d);
+}
+
+int rattle_hip_debug_consensus_support(rattle_ctx *c, const rattle_correct_params *P, const rattle_debug_support_msa *in, rattle_debug_support **out) {
+    if (!c || !P || !in || !out) { set_error("null argument"); return RATTLE_ERR_ARG; }
+    *out = nullptr;
+    const rattle_debug_msa M = {in->n_packs, in->pack_first, in->width, in->off, in->seq, nullptr, in->col};
+    RT_TRY(check_debug_msa(&M, 2));
+    if ((in->sup == nullptr) != (in->dep == nullptr)) { set_error("sup and dep come together (both NULL: rows that are reads)"); return RATTLE_ERR_ARG; }
+    RT_TRY(use_device(c));
+    int rc = debug_consensus_support(c, P, in, out);
+    if (rc != 0 && *out) { rattle_hip_debug_consensus_support_free(*out); *out = nullptr; }
+    return rc;
+}
+
+void rattle_hip_debug_consensus_support_free(rattle_debug_support *d) {
+    if (!d) return;
+    free(d->coff); free(d->cons_len); free(d->consensus); free(d->support); free(d->depth); free(d->pack_support); free(d->pack_depth);
     free(d);
 }
 

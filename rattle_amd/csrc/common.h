@@ -264,6 +264,16 @@ struct post_args {
     double min_occ, gap_occ, err_ratio;
     uint32_t *rep;                      // report form of MODE 1 (else null): REP_KERNEL counters per sequence, counter f of sequence q at rep[f * rep_stride + q]
     uint32_t rep_stride;
+    // report form of MODE 2, the consensus support (else ccnt is null).  Four uint32 per column, field f of column k of pack p at
+    // ccnt[f * cnt_stride + coff[p] + k]: support, depth (reads), the vote's winner count and total (rows); ocnt: the same for the bases
+    // of the consensus, at their index in cons_out.  Packs [0, n_composed) are POA #3 packs: in_sup / in_dep hold the support and the
+    // depth of every input base (parallel to seq; the composed packs' sequences come first), msup / mdep are rows x width matrices of
+    // them at moff (uint32 per cell, only for those packs)
+    uint32_t *ccnt, *ocnt;
+    uint64_t cnt_stride;
+    uint32_t n_composed;
+    const uint32_t *in_sup, *in_dep;
+    uint32_t *msup, *mdep;
 };
 
 // The per-read correction report.  Kernel D's report form counts, per row, the columns of its window by the branch of step d that
@@ -277,10 +287,18 @@ struct correction_box {
     rattle_correction pub;
     bool has_report;
     uint32_t *rep[REP_FIELDS];          // [pub.corrected.n] each, parallel to pub.corrected.read_id
+    // the consensus support (rattle_hip_set_consensus_support): per base of pub.consensi (at pub.consensi.off) support, depth, pack_support,
+    // pack_depth; per record the level (2: one pack's POA #2 vote, 3: composed through POA #3)
+    bool has_support;
+    uint8_t *sup_level;
+    uint32_t *sup[4];
 };
+enum { SUP_SUPPORT = 0, SUP_DEPTH, SUP_PACK_SUPPORT, SUP_PACK_DEPTH, SUP_FIELDS };
 rattle_correction *new_correction();
 correction_box *box_of(const rattle_correction *c);
 void alloc_report(correction_box *B, size_t n);                      // the arrays (never null pointers), has_report = true
+void alloc_support(correction_box *B, size_t n, size_t bases);       // level per record, four arrays per base (zeroed), has_support = true
+void print_support_totals(const rattle_correction *c);               // RATTLE_TIMING=1: the totals of the consensus support on stderr
 void print_report_totals(const rattle_correction *c, const char *what);      // RATTLE_TIMING=1: the six totals on stderr
 
 // The cluster report.  The verdict kernel's report form writes an evidence record (hit_evidence) beside every accepted pair; the greedy
@@ -364,6 +382,7 @@ struct rattle_ctx {
     rattle::dbuf<int32_t> d_exc_val;
     bool phred_ready = false;
     bool correction_report = false;         // rattle_hip_set_correction_report: stage 1 of `correct` launches kernel D's report form
+    bool consensus_support = false;         // rattle_hip_set_consensus_support: the consensus stages launch kernel D's mode-2 report form
     rattle::exchange xchg;
     rattle_ctx() = default;
     rattle_ctx(const rattle_ctx &) = delete;
@@ -461,5 +480,6 @@ int debug_evaluate(rattle_ctx *ctx, const rattle_cluster_params *P, int count_mo
 
 // correct_driver.hip
 int debug_post_msa(rattle_ctx *ctx, const rattle_correct_params *P, int mode, const rattle_debug_msa *in, rattle_debug_post **out);
+int debug_consensus_support(rattle_ctx *ctx, const rattle_correct_params *P, const rattle_debug_support_msa *in, rattle_debug_support **out);
 
 }  // namespace rattle

@@ -193,6 +193,13 @@ struct stage {
     dbuf<uint32_t> rep;                 // mode 1 with the correction report on: kernel D's REP_KERNEL counters, counter f of sequence q at rep[f * n() + q]
     dbuf<int32_t> rfirst, rlast;
     dbuf<double> cerr;
+    // mode 2 with the consensus support on.  The first n_composed packs are POA #3 packs: h_sup / h_dep are the support and the depth of
+    // every base of their sequences (the caller fills them; they lie first in seq), in_sup / in_dep their device copies, msup / mdep the
+    // cell matrices.  ccnt / ocnt: kernel D's four values per column / per consensus base, field f at f * cnt_stride
+    uint32_t n_composed = 0;
+    std::vector<uint32_t> h_sup, h_dep;
+    dbuf<uint32_t> in_sup, in_dep, msup, mdep, ccnt, ocnt;
+    uint64_t cnt_stride = 0;
     uint32_t n() const { return (uint32_t)off.size() - 1; }
     uint32_t n_packs() const { return (uint32_t)first.size() - 1; }
     void release() {
@@ -200,6 +207,7 @@ struct stage {
         cons_out.release(); d_off.release(); d_moff.release(); d_coff.release(); col.release(); d_width.release();
         d_first.release(); tfront.release(); tback.release(); olen.release(); cons_len.release(); rfirst.release();
         rlast.release(); cerr.release(); rep.release();
+        in_sup.release(); in_dep.release(); msup.release(); mdep.release(); ccnt.release(); ocnt.release();
     }
 };
 
@@ -238,7 +246,11 @@ int run_post_msa(rattle_ctx *ctx, stage &S, int mode, const rattle_correct_param
     }
     S.cells = cells; S.cols = cols;
     phase_timer T("  stage: post-MSA kernel");
-    make_room(ctx, (mode == 1 ? 2 : 1) * (cells + 64) + 4 * (cols + 64) + 20ull * (n + 1));
+    const bool support = mode == 2 && ctx->consensus_support;
+    const uint64_t ccells = !support ? 0 : S.n_composed < np ? S.moff[S.n_composed] : cells;      // cells of the composed packs
+    if (support && S.h_sup.size() != (S.n_composed ? S.off[S.first[S.n_composed]] : 0)) { set_error("consensus support: one support and depth per base of the composed packs"); return RATTLE_ERR_ARG; }
+    S.cnt_stride = cols + 64;
+    make_room(ctx, (mode == 1 ? 2 : 1) * (cells + 64) + 4 * (cols + 64) + 20ull * (n + 1) + (support ? 8 * (ccells + 64) + 32 * S.cnt_stride + 8 * (S.h_sup.size() + 64) : 0));
     RT_TRY(S.rowc.reserve(cells + 64)); RT_TRY(S.d_moff.reserve(np)); RT_TRY(S.d_coff.reserve(np));
     RT_TRY(S.rfirst.reserve(n + 1)); RT_TRY(S.rlast.reserve(n + 1)); RT_TRY(S.ccons.reserve(cols + 64));
     if (mode == 1) {
@@ -247,6 +259,15 @@ int run_post_msa(rattle_ctx *ctx, stage &S, int mode, const rattle_correct_param
         if (ctx->correction_report) RT_TRY(S.rep.reserve((size_t)REP_KERNEL * n + REP_KERNEL));
     } else {
         RT_TRY(S.cons_out.reserve(cols + 64)); RT_TRY(S.cons_len.reserve(np));
+        if (support) {
+            RT_TRY(S.ccnt.reserve(4 * S.cnt_stride)); RT_TRY(S.ocnt.reserve(4 * S.cnt_stride));
+            RT_TRY(S.msup.reserve(ccells + 64)); RT_TRY(S.mdep.reserve(ccells + 64));
+            RT_TRY(S.in_sup.reserve(S.h_sup.size() + 64)); RT_TRY(S.in_dep.reserve(S.h_dep.size() + 64));
+            if (!S.h_sup.empty()) {
+                RT_HIP(hipMemcpyAsync(S.in_sup.p, S.h_sup.data(), S.h_sup.size() * 4, hipMemcpyHostToDevice, st));
+                RT_HIP(hipMemcpyAsync(S.in_dep.p, S.h_dep.data(), S.h_dep.size() * 4, hipMemcpyHostToDevice, st));
+            }
+        }
     }
     RT_HIP(hipMemcpyAsync(S.d_moff.p, S.moff.data(), (size_t)np * 8, hipMemcpyHostToDevice, st));
     RT_HIP(hipMemcpyAsync(S.d_coff.p, S.coff.data(), (size_t)np * 8, hipMemcpyHostToDevice, st));
@@ -262,6 +283,10 @@ int run_post_msa(rattle_ctx *ctx, stage &S, int mode, const rattle_correct_param
     memcpy(A.order, order, 6);
     A.min_occ = P->min_occ; A.gap_occ = P->gap_occ; A.err_ratio = P->err_ratio;
     A.rep = mode == 1 && ctx->correction_report ? S.rep.p : nullptr; A.rep_stride = n;      // with A.rep the launch takes the report form
+    if (support) {                                                                          // with A.ccnt the launch takes the report form
+        A.ccnt = S.ccnt.p; A.ocnt = S.ocnt.p; A.cnt_stride = S.cnt_stride; A.n_composed = S.n_composed;
+        A.in_sup = S.in_sup.p; A.in_dep = S.in_dep.p; A.msup = S.msup.p; A.mdep = S.mdep.p;
+    }
     RT_TRY(launch_post_msa(ctx, A, np, mode));
     return 0;
 }
@@ -309,6 +334,7 @@ struct cons_stage {
     std::vector<uint8_t> h_in;                 // concatenated input sequences (host-sourced groups)
     std::vector<uint32_t> len;                 // [n_packs] consensus length
     std::vector<uint8_t> cons;                 // consensi at S.coff
+    std::vector<uint32_t> cnt;                 // the consensus support: field f of the base at cons[x] at cnt[f * S.cnt_stride + x]
 };
 
 int fetch_consensi(rattle_ctx *ctx, cons_stage &C) {
@@ -318,6 +344,10 @@ int fetch_consensi(rattle_ctx *ctx, cons_stage &C) {
     if (!np) return 0;
     RT_HIP(hipMemcpyAsync(C.len.data(), C.S.cons_len.p, (size_t)np * 4, hipMemcpyDeviceToHost, ctx->stream));
     if (C.S.cols) RT_HIP(hipMemcpyAsync(C.cons.data(), C.S.cons_out.p, C.S.cols, hipMemcpyDeviceToHost, ctx->stream));
+    if (C.S.ocnt.p && ctx->consensus_support) {
+        C.cnt.assign(4 * C.S.cnt_stride, 0);
+        RT_HIP(hipMemcpyAsync(C.cnt.data(), C.S.ocnt.p, C.cnt.size() * 4, hipMemcpyDeviceToHost, ctx->stream));
+    }
     RT_HIP(hipStreamSynchronize(ctx->stream));
     return 0;
 }
@@ -368,6 +398,10 @@ struct correct_job {
     std::vector<uint8_t> pk_dead;                    // stage at which a pack was given up (this rank's packs: exact; others: from the exchange)
     std::vector<std::string> pk_cons, cl_cons;       // pack consensus (POA #2) / cluster consensus, filled by the exchanges
     std::vector<uint8_t> pk_has, cl_has;
+    const bool support = ctx->consensus_support;     // the consensus support is on for this call (one rank: abi.hip refuses it on several)
+    std::vector<std::vector<uint32_t>> pk_sup, pk_dep;      // ... per base of pk_cons: winner's count / rows that voted in POA #2's MSA (reads)
+    std::vector<std::vector<uint32_t>> cl_sup[SUP_FIELDS];  // ... per base of cl_cons
+    std::vector<uint8_t> cl_level;
     std::vector<skip_t> skips;                       // skip list (this rank's share; unqueued entries on rank 0)
     std::vector<hread> uncorrected;
     std::vector<int32_t> unc_cid;
@@ -414,6 +448,10 @@ struct correct_job {
         RT_TRY(set_pack_orders());
         pk_dead.assign(n_packs, 0); pk_cons.resize(n_packs); pk_has.assign(n_packs, 0);
         cl_cons.resize(n_clusters); cl_has.assign(n_clusters, 0);
+        if (support) {
+            pk_sup.resize(n_packs); pk_dep.resize(n_packs); cl_level.assign(n_clusters, 0);
+            for (auto &v : cl_sup) v.resize(n_clusters);
+        }
         S1.first.assign(1, 0);
         for (uint32_t p = 0; p < n_packs; ++p) {
             if ((int)PL.pk_owner[p] != rank) continue;
@@ -609,7 +647,14 @@ struct correct_job {
             if ((big[c] != 0) != of_big || PL.cl_np[c] == 0) continue;
             group_of(c, g);
             if (g.size() > 1) { all.push_back(c); cost.push_back((uint64_t)g.size() * g.size() * pk_cons[g[0]].size()); }
-            else if (g.size() == 1) { cl_cons[c] = pk_cons[g[0]]; cl_has[c] = 1; }
+            else if (g.size() == 1) {
+                cl_cons[c] = pk_cons[g[0]]; cl_has[c] = 1;
+                if (support) {                       // ... and its support with it: rows of POA #2's MSA are reads
+                    cl_sup[SUP_SUPPORT][c] = cl_sup[SUP_PACK_SUPPORT][c] = pk_sup[g[0]];
+                    cl_sup[SUP_DEPTH][c] = cl_sup[SUP_PACK_DEPTH][c] = pk_dep[g[0]];
+                    cl_level[c] = 2;
+                }
+            }
         }
         lpt_assign(cost, nranks, own);
         for (size_t i = 0; i < all.size(); ++i) if ((int)own[i] == rank) my.push_back(all[i]);
@@ -663,11 +708,13 @@ struct correct_job {
             for (uint32_t p : g) {
                 d.push_back(gather_desc{(uint64_t)C.h_in.size(), S.off.back(), (uint32_t)pk_cons[p].size(), 0u});
                 C.h_in.insert(C.h_in.end(), pk_cons[p].begin(), pk_cons[p].end());
+                if (support) { S.h_sup.insert(S.h_sup.end(), pk_sup[p].begin(), pk_sup[p].end()); S.h_dep.insert(S.h_dep.end(), pk_dep[p].begin(), pk_dep[p].end()); }
                 S.off.push_back(S.off.back() + pk_cons[p].size());
             }
             S.first.push_back((uint32_t)S.off.size() - 1);
         }
         const uint32_t n3 = (uint32_t)d.size();
+        S.n_composed = (uint32_t)clusters3.size();
         for (uint32_t k : slots2) {                  // my pack k's corrected reads, length-sorted
             rows.clear();
             for (uint32_t q = S1.first[k]; q < S1.first[k + 1]; ++q) if (olen[q]) rows.push_back(q);
@@ -686,11 +733,18 @@ struct correct_job {
                          2, P, order, counters));
         RT_TRY(fetch_consensi(ctx, C));
         uint32_t slot = 0;
+        auto counts = [&](uint32_t sl, int f) {      // field f of the consensus of slot sl
+            const uint32_t *b = C.cnt.data() + (size_t)f * S.cnt_stride + S.coff[sl];
+            return std::vector<uint32_t>(b, b + C.len[sl]);
+        };
         for (uint32_t c : clusters3) {
             if (S.skipped[slot]) {
                 skips.push_back(skip_t{(int32_t)c, 0u, 3u, {}});
                 put_rec(bytes, c, 1u | (3u << 1), nullptr, 0);
-            } else put_rec(bytes, c, 1u, (const char *)C.cons.data() + S.coff[slot], C.len[slot]);
+            } else {
+                put_rec(bytes, c, 1u, (const char *)C.cons.data() + S.coff[slot], C.len[slot]);
+                if (support) { for (int f = 0; f < SUP_FIELDS; ++f) cl_sup[f][c] = counts(slot, f); cl_level[c] = 3; }
+            }
             ++slot;
         }
         for (uint32_t k : slots2) {
@@ -699,7 +753,10 @@ struct correct_job {
                 skips.push_back(skip_t{PL.pk_cid[p], PL.pk_local[p], 2u, {}});
                 for (uint32_t q = S1.first[k]; q < S1.first[k + 1]; ++q) skips.back().rids.push_back(r[q].rid);
                 put_rec(bytes, p, 2u << 1, nullptr, 0);
-            } else put_rec(bytes, p, 0u, (const char *)C.cons.data() + S.coff[slot], C.len[slot]);
+            } else {
+                put_rec(bytes, p, 0u, (const char *)C.cons.data() + S.coff[slot], C.len[slot]);
+                if (support) { pk_sup[p] = counts(slot, SUP_SUPPORT); pk_dep[p] = counts(slot, SUP_DEPTH); }
+            }
             ++slot;
         }
         return 0;
@@ -722,6 +779,17 @@ struct correct_job {
         }
         fill_set(R->uncorrected, uncorrected, unc_cid, {});
         fill_set(R->consensi, consensi, con_cid, con_n);
+        if (support) {                               // per base of the consensi, in their order
+            correction_box *B = box_of(R);
+            const rattle_read_set &S = R->consensi;
+            alloc_support(B, S.n, S.off[S.n]);
+            for (uint32_t i = 0; i < S.n; ++i) {
+                const uint32_t c = (uint32_t)con_cid[i];
+                B->sup_level[i] = cl_level[c];
+                for (int f = 0; f < SUP_FIELDS; ++f)
+                    if (S.off[i + 1] > S.off[i]) memcpy(B->sup[f] + S.off[i], cl_sup[f][c].data(), (S.off[i + 1] - S.off[i]) * 4);
+            }
+        }
         R->corrected_pack = result_array<uint32_t>(cor_pack.size());
         if (!cor_pack.empty()) memcpy(R->corrected_pack, cor_pack.data(), cor_pack.size() * 4);
         R->uncorrected_pack = result_array<uint32_t>(unc_pack.size());
@@ -756,12 +824,9 @@ int vote_order_of(const rattle_correct_params *P, char order[8]) {
 // Test hook: kernel D alone on a given MSA (sequences + the column of every base, as kernel C leaves them), through the
 // stage and the launch path of the driver (run_post_msa), and everything it wrote.  The input was validated by the caller
 // (abi.hip): columns strictly increasing and below the width in every pack of width > 0, bases in ACGTU.
-int debug_post_msa(rattle_ctx *ctx, const rattle_correct_params *P, int mode, const rattle_debug_msa *in, rattle_debug_post **out) {
-    char order[8];
-    RT_TRY(vote_order_of(P, order));
+static int debug_stage_upload(rattle_ctx *ctx, stage &S, int mode, const rattle_debug_msa *in) {
     hipStream_t st = ctx->stream;
     const uint32_t np = in->n_packs, n = in->pack_first[np];
-    stage S;
     S.first.assign(in->pack_first, in->pack_first + np + 1);
     S.off.assign(in->off, in->off + n + 1);
     S.width.assign(in->width, in->width + np);
@@ -778,6 +843,16 @@ int debug_post_msa(rattle_ctx *ctx, const rattle_correct_params *P, int mode, co
     RT_HIP(hipMemcpyAsync(S.d_off.p, S.off.data(), (size_t)(n + 1) * 8, hipMemcpyHostToDevice, st));
     RT_HIP(hipMemcpyAsync(S.d_first.p, S.first.data(), (size_t)(np + 1) * 4, hipMemcpyHostToDevice, st));
     if (np) RT_HIP(hipMemcpyAsync(S.d_width.p, S.width.data(), (size_t)np * 4, hipMemcpyHostToDevice, st));
+    return 0;
+}
+
+int debug_post_msa(rattle_ctx *ctx, const rattle_correct_params *P, int mode, const rattle_debug_msa *in, rattle_debug_post **out) {
+    char order[8];
+    RT_TRY(vote_order_of(P, order));
+    hipStream_t st = ctx->stream;
+    const uint32_t np = in->n_packs, n = in->pack_first[np];
+    stage S;
+    RT_TRY(debug_stage_upload(ctx, S, mode, in));
     RT_TRY(run_post_msa(ctx, S, mode, P, order));
 
     rattle_debug_post *D = (rattle_debug_post *)calloc(1, sizeof(rattle_debug_post));
@@ -836,6 +911,37 @@ int debug_post_msa(rattle_ctx *ctx, const rattle_correct_params *P, int mode, co
     return 0;
 }
 
+// Test hook: the mode-2 report form of kernel D alone on given MSAs (validated by the caller like debug_post_msa's), through
+// run_post_msa and fetch_consensi.  With in->sup / in->dep every pack is a composed (POA #3) pack.
+int debug_consensus_support(rattle_ctx *ctx, const rattle_correct_params *P, const rattle_debug_support_msa *in, rattle_debug_support **out) {
+    char order[8];
+    RT_TRY(vote_order_of(P, order));
+    const uint32_t np = in->n_packs, n = in->pack_first[np];
+    const rattle_debug_msa M = {np, in->pack_first, in->width, in->off, in->seq, nullptr, in->col};
+    cons_stage C;
+    stage &S = C.S;
+    RT_TRY(debug_stage_upload(ctx, S, 2, &M));
+    if (in->sup && ctx->consensus_support) {
+        S.n_composed = np;
+        S.h_sup.assign(in->sup, in->sup + S.off[n]); S.h_dep.assign(in->dep, in->dep + S.off[n]);
+    }
+    RT_TRY(run_post_msa(ctx, S, 2, P, order));
+    RT_TRY(fetch_consensi(ctx, C));
+    rattle_debug_support *D = (rattle_debug_support *)calloc(1, sizeof(rattle_debug_support));
+    *out = D;
+    D->n_packs = np; D->n_cols = S.cols; D->level = in->sup ? 3 : 2;
+    D->coff = result_array<uint64_t>(np); D->cons_len = result_array<uint32_t>(np); D->consensus = result_array<uint8_t>(S.cols);
+    if (np) { memcpy(D->coff, S.coff.data(), (size_t)np * 8); memcpy(D->cons_len, C.len.data(), (size_t)np * 4); }
+    if (S.cols) memcpy(D->consensus, C.cons.data(), S.cols);
+    if (!ctx->consensus_support) return 0;
+    uint32_t **dst[SUP_FIELDS] = {&D->support, &D->depth, &D->pack_support, &D->pack_depth};
+    for (int f = 0; f < (in->sup ? SUP_FIELDS : 2); ++f) {
+        *dst[f] = result_array<uint32_t>(S.cols);
+        if (S.cols) memcpy(*dst[f], C.cnt.data() + (size_t)f * S.cnt_stride, S.cols * 4);
+    }
+    return 0;
+}
+
 // a step of this rank's own work: not run after an earlier one failed
 #define LOCAL_TRY(call) do { if (J.local_rc == 0) RT_TRY(J.own_error(call)); } while (0)
 
@@ -883,6 +989,7 @@ int correct_driver(rattle_ctx *ctx, const uint8_t *seq, const uint8_t *qual, con
     if (n3b || J.nranks > 1 || xchg_recording(ctx)) RT_TRY(J.exchange_stage(bytes_3b));
     J.d_os.release(); J.d_oq.release();
     J.assemble();
+    print_support_totals(R);
     print_report_totals(R, J.nranks > 1 ? "correction report (this rank's packs)" : "correction report");
     return 0;
 }

@@ -18,6 +18,13 @@
 // The REPORT form of MODE 1 (rattle_hip_set_correction_report) also counts, per row, the columns of its window by the branch of step d
 // that handled them: six counters the row's thread keeps in registers and stores once, next to olen.  It is an instance of its own:
 // without the report the kernel is the code it was.
+// The REPORT form of MODE 2 (rattle_hip_set_consensus_support) keeps what the column vote knows about every base of the consensus: the
+// winner's count and the number of rows that voted (step c, vote_support: uint32 per column), written by step d' at the compacted
+// index of the base.  A pack below A.n_composed is a POA #3 pack: its rows are pack consensi that carry a support and a depth per
+// base, counted in reads.  They are expanded beside the bases (step a, two uint32 matrices), the row's thread carries the depth forward
+// into the gap cells of its window (step b), and the column's thread sums, in its row loop, the depth of every row whose window covers
+// the column and the support of the rows per slot; the winner's sum is the support in reads.  Again an instance of its own: every
+// line of it sits in an `if constexpr`, and the three other instances compile to the instructions they were.
 //
 // phred_symbol (utils.cpp:6-8) is `(char)(-10*log10(p)+33)`: the host libm's log10 decides the
 // truncation, so the device does not evaluate log10 at all.  The host tabulates, for every integer n
@@ -111,9 +118,37 @@ __device__ void fix_phase(uint8_t *r, uint32_t n, uint32_t &trimmed, uint32_t &s
 #undef AT
 }
 
+// Step c of the consensus support: the vote of MODE 2 (rows in order, the reference's slot order with strict '>') that also keeps, per
+// column, four uint32, field f at ccnt[f * cnt_stride]: support and depth in reads, then the winner's count and the total in rows of
+// this MSA.  Rows that are reads (msup == null) count 1 each: the first pair is the second.
+__device__ __forceinline__ void vote_support(const post_args &A, uint32_t p, uint32_t tid, uint32_t q0, uint32_t R, uint32_t W, const uint8_t *rc,
+                                             const uint32_t *msup, const uint32_t *mdep) {
+    uint8_t *ccons = A.ccons + A.coff[p];
+    uint32_t *ccnt = A.ccnt + A.coff[p];
+    uint8_t o[6];
+    for (int s = 0; s < 6; ++s) o[s] = A.order[s];
+    for (uint32_t k = tid; k < W; k += 256) {
+        uint32_t occ[6] = {0, 0, 0, 0, 0, 0}, sup[6] = {0, 0, 0, 0, 0, 0}, dep = 0;
+        for (uint32_t i = 0; i < R; ++i) {
+            if ((int32_t)k < A.rfirst[q0 + i] || (int32_t)k > A.rlast[q0 + i]) continue;
+            const uint8_t nt = rc[(uint64_t)i * W + k];
+            const uint32_t sv = !msup ? 1u : nt != '-' ? msup[(uint64_t)i * W + k] : 0u;
+            dep += msup ? mdep[(uint64_t)i * W + k] : 1u;
+#pragma unroll
+            for (int s = 0; s < 6; ++s) if (nt == o[s]) { ++occ[s]; sup[s] += sv; }
+        }
+        uint32_t best = 0, bsup = 0, total = 0;
+        uint8_t nt = 0;
+#pragma unroll
+        for (int s = 0; s < 6; ++s) { total += occ[s]; if (occ[s] > best) { best = occ[s]; nt = o[s]; bsup = sup[s]; } }
+        ccons[k] = nt ? nt : (uint8_t)'-';
+        ccnt[k] = bsup; ccnt[A.cnt_stride + k] = dep; ccnt[2 * A.cnt_stride + k] = best; ccnt[3 * A.cnt_stride + k] = total;
+    }
+}
+
 template <int MODE, bool REPORT = false>
 __global__ __launch_bounds__(256) void post_msa_kernel(post_args A) {
-    static_assert(MODE == 1 || !REPORT, "the report is about the per-read correction");
+    constexpr bool SUPPORT = MODE == 2 && REPORT;      // <1, true>: the correction report; <2, true>: the consensus support
     __shared__ double s_perr[256];
     const uint32_t p = blockIdx.x, tid = threadIdx.x;
     const uint32_t q0 = A.pack_first[p], q1 = A.pack_first[p + 1], R = q1 - q0;
@@ -125,7 +160,7 @@ __global__ __launch_bounds__(256) void post_msa_kernel(post_args A) {
     if (R == 0 || W == 0) {
         if (tid == 0 && MODE == 2) A.cons_len[p] = 0;
         if (MODE == 1) for (uint32_t i = tid; i < R; i += 256) { A.olen[q0 + i] = 0; A.tfront[q0 + i] = 0; A.tback[q0 + i] = 0; }
-        if (REPORT) for (uint32_t i = tid; i < R; i += 256) for (uint32_t f = 0; f < REP_KERNEL; ++f) A.rep[(uint64_t)f * A.rep_stride + q0 + i] = 0;
+        if (REPORT && MODE == 1) for (uint32_t i = tid; i < R; i += 256) for (uint32_t f = 0; f < REP_KERNEL; ++f) A.rep[(uint64_t)f * A.rep_stride + q0 + i] = 0;
         return;
     }
     // ---- a. expand
@@ -138,6 +173,7 @@ __global__ __launch_bounds__(256) void post_msa_kernel(post_args A) {
             const uint32_t c = A.col[b];
             row[c] = A.seq[b];
             if (MODE == 1) rq[(uint64_t)i * W + c] = A.qual[b];
+            if constexpr (SUPPORT) if (p < A.n_composed) { A.msup[A.moff[p] + (uint64_t)i * W + c] = A.in_sup[b]; A.mdep[A.moff[p] + (uint64_t)i * W + c] = A.in_dep[b]; }
         }
     }
     __syncthreads();
@@ -152,6 +188,12 @@ __global__ __launch_bounds__(256) void post_msa_kernel(post_args A) {
         if (s1 && s2 && p1 < W && p2 < W) { first = (int32_t)p1; last = (int32_t)(W - 1u - p2); }
         A.rfirst[q0 + i] = first; A.rlast[q0 + i] = last;
         if (MODE == 1) { A.tfront[q0 + i] = t1; A.tback[q0 + i] = t2; }
+        if constexpr (SUPPORT) if (p < A.n_composed) {
+            // a gap inside the window stands for the depth of the row's last base before it (a window starts on a base)
+            uint32_t *drow = A.mdep + A.moff[p] + (uint64_t)i * W;
+            uint32_t carry = 0;
+            for (int32_t k = first; k <= last; ++k) { if (row[k] != '-') carry = drow[k]; else drow[k] = carry; }
+        }
     }
     __syncthreads();
     // ---- c. vote (correct.cpp:94-193), one column per thread, rows in order
@@ -160,7 +202,8 @@ __global__ __launch_bounds__(256) void post_msa_kernel(post_args A) {
     uint8_t *csym = A.csym + A.coff[p];
     double *cerr = A.cerr + A.coff[p];
     const uint8_t o0 = A.order[0], o1 = A.order[1], o2 = A.order[2], o3 = A.order[3], o4 = A.order[4], o5 = A.order[5];
-    for (uint32_t k = tid; k < W; k += 256) {
+    if constexpr (SUPPORT) vote_support(A, p, tid, q0, R, W, rc, p < A.n_composed ? A.msup + A.moff[p] : nullptr, p < A.n_composed ? A.mdep + A.moff[p] : nullptr);
+    else for (uint32_t k = tid; k < W; k += 256) {
         int occ0 = 0, occ1 = 0, occ2 = 0, occ3 = 0, occ4 = 0, occ5 = 0;
         double e0 = 0.0, e1 = 0.0, e2 = 0.0, e3 = 0.0, e4 = 0.0, e5 = 0.0;
         for (uint32_t i = 0; i < R; ++i) {
@@ -243,6 +286,11 @@ __global__ __launch_bounds__(256) void post_msa_kernel(post_args A) {
                 const bool keep = c != '-';
                 const unsigned long long m = __ballot(keep);
                 if (keep) out[o + __popcll(m & ((1ull << tid) - 1ull))] = c;
+                if constexpr (SUPPORT) if (keep) {
+                    const uint32_t *cc = A.ccnt + A.coff[p] + k;
+                    uint32_t *oc = A.ocnt + A.coff[p] + o + __popcll(m & ((1ull << tid) - 1ull));
+                    for (uint32_t f = 0; f < 4; ++f) oc[f * A.cnt_stride] = cc[f * A.cnt_stride];
+                }
                 o += (uint32_t)__popcll(m);
             }
             if (tid == 0) A.cons_len[p] = o;
@@ -255,6 +303,7 @@ int launch_post_msa(rattle_ctx *ctx, const post_args &A, uint32_t n_packs, int m
     ktimer T(ctx, K_POST, 0);
     if (mode == 1 && A.rep) hipLaunchKernelGGL((post_msa_kernel<1, true>), dim3(n_packs), dim3(256), 0, ctx->stream, A);      // the report form: same timer slot
     else if (mode == 1) hipLaunchKernelGGL(post_msa_kernel<1>, dim3(n_packs), dim3(256), 0, ctx->stream, A);
+    else if (A.ccnt) hipLaunchKernelGGL((post_msa_kernel<2, true>), dim3(n_packs), dim3(256), 0, ctx->stream, A);      // the consensus support
     else hipLaunchKernelGGL(post_msa_kernel<2>, dim3(n_packs), dim3(256), 0, ctx->stream, A);
     RT_HIP(hipGetLastError());
     return 0;

@@ -789,13 +789,18 @@ int mode_correct(int argc, char **argv) {
         {"min-occ", {"-m", "--min-occ"}, true}, {"split", {"-s", "--split"}, true}, {"min-reads", {"-r", "--min-reads"}, true},
         {"threads", {"-t", "--threads"}, true}, {"verbose", {"--verbose"}, false}, {"device", {"--device"}, true},
         {"vote-order", {"--vote-order"}, true}, {"max-pack-cells", {"--max-pack-cells"}, true}, {"devices", {"--devices"}, true},
-        {"host-exchange", {"--host-exchange"}, false}, {"write-unzipped", {"--write-unzipped"}, false}, {"report", {"--report"}, false}};
+        {"host-exchange", {"--host-exchange"}, false}, {"write-unzipped", {"--write-unzipped"}, false}, {"report", {"--report"}, false},
+        {"support", {"--support"}, false}};
     args_t a = parse(argc, argv, defs);
     if (a.has("help")) {
         std::cerr << "rattle correct -i reads.fq -c clusters.out [-o dir] ... (flags of RATTLE's correct mode)\n"
                      "  --report             also write correction_report.tsv: per record of corrected.fq its lengths before and after, the bases\n"
                      "                       trimmed at either end, and how many columns matched, were substituted, kept against the\n"
                      "                       winner, inserted, deleted or kept against a gap winner\n"
+                     "  --support            also write consensus_support.tsv: per record of consensi.fq how many reads stand behind every\n"
+                     "                       base (support: reads that voted for it, depth: reads that voted in its column, composed through\n"
+                     "                       the pack consensi for a cluster of several packs), the smallest ratio and the number of bases\n"
+                     "                       with no majority; one device only.  consensi.fq itself keeps its qualities\n"
                      "  --max-pack-cells N   leave packs whose largest alignment needs more than N DP cells uncorrected (default: only\n"
                      "                       packs that do not fit the device are skipped); skipped packs are listed in skipped_packs.tsv\n"
                      "  --devices 0,1,..     one job over several GPUs (RCCL; --host-exchange: in-process exchange on host buffers)\n";
@@ -803,6 +808,9 @@ int mode_correct(int argc, char **argv) {
     }
     if (!a.has("input")) die("ERROR: No input file provided");
     if (!a.has("clusters")) die("ERROR: No clusters file provided");
+    const bool want_support = a.has("support");
+    if (want_support && a.has("devices") && split_string(a.str("devices", ""), ',').size() > 1)
+        die("\nError: --support cannot be combined with --devices naming more than one device: the consensus support is made on one device\n");
     std::cerr << "Reading fasta file... ";
     std::vector<std::string> labels = split_string(a.str("label", ""), ',');
     const std::vector<std::string> files = split_string(a.str("input", ""), ',');
@@ -902,6 +910,7 @@ int mode_correct(int argc, char **argv) {
     team.run([&](int r, rattle_ctx *ctx) {                                      // packs sharded over the ranks, result reassembled on rank 0
         rattle_correction *mine = nullptr, *merged = nullptr;
         if (want_report) chk(rattle_hip_set_correction_report(ctx, 1));
+        if (want_support) chk(rattle_hip_set_consensus_support(ctx, 1));
         const int rc = rattle_hip_correct_reads(ctx, cat.data(), qcat.data(), off.data(), n_reads, (uint32_t)clusters.size(), coff.data(), mid.data(),
                                                 mrev.data(), &P, &mine);
         if (rc != 0 && team.n() == 1) unlink(corrected_tmp.c_str());           // no half of a result stays behind
@@ -982,6 +991,38 @@ int mode_correct(int argc, char **argv) {
               << "\t" << rp->gap_kept[i] << "\n";
         }
         rattle_hip_correction_report_free(rp);
+        f.close();
+        if (!f) die("Error: cannot write " + path);
+    }
+    if (want_support) {
+        // consensus_support.tsv: one line per record of consensi.fq, in that file's order
+        rattle_consensus_support *sp = nullptr;
+        chk(rattle_hip_consensus_support(R, &sp));
+        const std::string path = outdir + "/consensus_support.tsv";
+        std::ofstream f(path);
+        f << "consensus\tlength\tlevel\treads\tmin_ratio\tweak\tsupport\tdepth\n";
+        for (uint32_t i = 0; i < sp->n; ++i) {
+            const std::string &h = consensi[i].header;                                  // the name: the header's first token, without its '@'
+            const size_t b = !h.empty() && h[0] == '@' ? 1 : 0;
+            const uint64_t p0 = sp->off[i], p1 = sp->off[i + 1];
+            double min_ratio = 0.0;
+            uint64_t weak = 0;
+            for (uint64_t p = p0; p < p1; ++p) {
+                const double ratio = double(sp->support[p]) / double(sp->depth[p]);
+                if (p == p0 || ratio < min_ratio) min_ratio = ratio;
+                weak += 2ull * sp->support[p] <= sp->depth[p];
+            }
+            char num[64];
+            snprintf(num, sizeof(num), "%.17g", min_ratio);
+            f << h.substr(b, h.find_first_of(" \t") - b) << "\t" << (p1 - p0) << "\t" << (int)sp->level[i] << "\t" << R->consensi.n_reads[i] << "\t" << num << "\t" << weak;
+            for (int which = 0; which < 2; ++which) {
+                const uint32_t *v = which ? sp->depth : sp->support;
+                f << "\t";
+                for (uint64_t p = p0; p < p1; ++p) { if (p > p0) f << ","; f << v[p]; }
+            }
+            f << "\n";
+        }
+        rattle_hip_consensus_support_free(sp);
         f.close();
         if (!f) die("Error: cannot write " + path);
     }
