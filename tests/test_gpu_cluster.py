@@ -51,6 +51,9 @@ def test_long_read_global_sort_path(gpu_ctx, oracle):
         fh, fp, rh, rp, bf, br = oracle.extract_kmers(q, 11, True)
         h, p, bv, _ = gpu_ctx.read_index(r, 1)
         assert np.array_equal(h, rh) and np.array_equal(p, rp) and np.array_equal(bv, br)
+        h, p, bv, pc = gpu_ctx.read_index(r, 0)
+        assert np.array_equal(h, fh) and np.array_equal(p, fp) and np.array_equal(bv, bf)
+        assert pc == int(np.bitwise_count(bf).sum())
 
 
 @pytest.mark.parametrize("thr", [0.4, 0.35000000000000003, 0.20000000000000007, 0.0])
@@ -76,6 +79,66 @@ def test_bv_filter_matches_oracle(gpu_ctx, oracle, small_reads, thr):
                 if cr / mmax >= thr:
                     want |= 2
             assert got[s, c] == want, (s, c)
+
+
+@pytest.fixture(scope="module")
+def tile_reads(oracle):
+    """the read set of the tile-edge test and the reference's side of it: vectors of both strands, forward popcounts"""
+    seqs = synth.reads(520, 4, 1, True, seed=71, exon=(20, 45))[0]                 # 150 - 400 nt, a few genes
+    rng = np.random.default_rng(72)
+    acgt = np.frombuffer(b"ACGT", np.uint8)
+    reads = seqs + [b"ACGTAC", b"GGT", acgt[rng.integers(0, 4, 60000)].tobytes()]  # two empty vectors (pcf = 0), one nearly full
+    idx = [oracle.extract_kmers(s, 10, True) for s in reads]
+    bf = np.array([x[4] for x in idx], np.uint64); br = np.array([x[5] for x in idx], np.uint64)
+    pcf = np.bitwise_count(bf).sum(1).astype(np.int64)
+    assert pcf[-3] == 0 and pcf[-2] == 0 and pcf[-1] > 4000 and 150 <= min(map(len, seqs)) and max(map(len, seqs)) <= 400
+    return reads, bf, br, pcf
+
+
+@pytest.mark.parametrize("both", [True, False])
+def test_bv_filter_tile_edges(gpu_ctx, tile_reads, both):
+    """Kernel A (bv_filter.hip) at the edges of its 32-seed x 256-candidate tile, against the numpy popcount expression of
+    test_bv_filter_matches_oracle.  Rectangles of 1, 31, 32, 33, 65 seeds x 1, 255, 256, 257, 513 candidates: `ns = min(BVF_TS,
+    ...)` and `live = c < n_cands` one short of, on and one past a tile, and the lone seed whose next-seed prefetch is itself.
+    first_cand all 0, seed + 1, and all seeds at 255 / 256 / 257 / 512 / n_cands: `if (c0 + BVF_TC <= s_minfirst)` returns early
+    for the first tile, or the first two, and must leave zeros in the dense output; one below the edge it must not fire.  Reads
+    with an empty 6-mer vector (pcf = 0): with another empty one mmax = 0 and `lut[0]` = 0xFFFF, the pair survives on no strand
+    but for the forward bypass at thr == 0.0 (cluster.cpp:19) -- the reference expression says so by itself, 0 / 0 >= thr being
+    false.  A 60 kb read whose vector is nearly full (lut[4096]).  Both strands (bv_filter_kernel<true>) and forward only."""
+    reads, bf, br, pcf = tile_reads
+    gpu_ctx.load_reads(reads, 10, both)
+    n = len(reads)
+    rng = np.random.default_rng(73)
+    special = np.array([n - 3, n - 2, n - 1])
+    fired = zero_max = 0
+    for thr in (0.4, 0.0):
+        lut = min_common_lut(thr)
+        for n_seeds in (1, 31, 32, 33, 65):
+            for n_cands in (1, 255, 256, 257, 513):
+                # the special reads among the seeds and among the candidates, wherever the rectangle has room for them
+                seeds = rng.permutation(n)[:n_seeds]
+                cands = rng.permutation(n)[:n_cands]
+                if n_seeds >= 3:
+                    seeds[[0, n_seeds // 2, n_seeds - 1]] = special
+                if n_cands >= 3:
+                    cands[[0, n_cands // 2, n_cands - 1]] = special
+                firsts = [np.zeros(n_seeds, np.int64), np.arange(n_seeds) + 1] + [np.full(n_seeds, f) for f in sorted({255, 256, 257, 512, n_cands}) if f <= n_cands]
+                common_f = np.bitwise_count(bf[seeds][:, None, :] & bf[cands][None, :, :]).sum(2).astype(np.float64)
+                common_r = np.bitwise_count(bf[seeds][:, None, :] & br[cands][None, :, :]).sum(2).astype(np.float64)
+                mmax = np.maximum(pcf[seeds][:, None], pcf[cands][None, :]).astype(np.float64)
+                with np.errstate(invalid="ignore", divide="ignore"):
+                    ok_f = (common_f / mmax >= thr) | (thr == 0.0)
+                    ok_r = (common_r / mmax >= thr) & both
+                zero_max += int((mmax == 0).sum())
+                for first in firsts:
+                    got = gpu_ctx.bv_filter(seeds, cands, first, lut, thr == 0.0)
+                    live = np.arange(n_cands)[None, :] >= first[:, None]
+                    want = ((ok_f & live) * 1 + (ok_r & live) * 2).astype(np.uint8)
+                    bad = np.argwhere(got != want)
+                    assert len(bad) == 0, (thr, n_seeds, n_cands, int(first[0]), int(first[-1]), bad[:5].tolist(),
+                                           [(int(got[s, c]), int(want[s, c])) for s, c in bad[:5]])
+                    fired += int(first.min()) >= 256
+    assert fired >= 10 and zero_max >= 10
 
 
 @pytest.mark.parametrize("k", [10, 11, 6])
