@@ -185,6 +185,55 @@ int rattle_hip_cluster_report(const rattle_cluster_set *cs, rattle_cluster_repor
 void rattle_hip_cluster_report_free(rattle_cluster_report *r);
 
 /* ------------------------------------------------------------------------------------
+ * assign: reads placed on a GIVEN set of targets (a transcriptome and a second sample, a replicate, the reads --min-reads left out)
+ * by the comparison that decides cluster membership, cluster_together (/root/reference/cluster.cpp:13-61); the reference has no
+ * counterpart.  For read r the ACCEPTED comparisons are the (target t, strand) for which cluster_together(T[t], R[r]) accepts on that
+ * strand -- the target takes the seed's role whatever the two lengths are: the 6-mer bit-vector test at bv_threshold (with the forward
+ * bypass of bv_threshold == 0), then score >= t_s && variance < t_v with score = (use_hc ? hc_bases : bases) / min(len) in the
+ * reference's double arithmetic (a NaN variance rejects); strand 1 exists only when !is_rna.  There are no falloff or merge passes.
+ *   best          the accepted comparison with the largest score (compared as doubles); ties: lowest target index, then forward
+ *   n_accepted    the number of accepted (target, strand) comparisons
+ *   second_score  the largest score among the accepted comparisons of OTHER targets than best's (two identical targets: == score;
+ *                 the other strand of the same target does not count); -1.0 if there is none
+ * target, rev, bases, hc_bases, min_len, score, variance describe the winning comparison (the fields of a line of cluster_report.tsv);
+ * a read nothing accepts -- one shorter than kmer_size among them -- has target -1, score -1.0, second_score -1.0 and zeros elsewhere.
+ * The result does not depend on target_batch, read_chunk, count_pass or the order in which the device scores the pairs: the accepted
+ * comparisons are reduced per read ON THE DEVICE (csrc/assign.hip) and one 40-byte record per read is all that returns to the host.
+ */
+typedef struct {
+    double t_s, t_v;
+    double bv_threshold;
+    int use_hc;
+    int is_rna;
+    uint32_t target_batch;  /* targets per evaluation against all reads; 0 = the default (512) */
+    uint32_t read_chunk;    /* rattle_hip_assign_reads: reads indexed at a time; 0 = the default (2^20) */
+    int count_pass;         /* 0 = automatic; 1 seed-major, 2 per-pair search, 3 seed-batch index, as in rattle_hip_debug_evaluate */
+} rattle_assign_params;
+
+typedef struct {
+    uint32_t n;             /* reads; every array has n entries, in the order the reads were given */
+    int32_t  *target;       /* index into the targets as given, or -1 */
+    uint8_t  *rev;
+    int32_t  *bases, *hc_bases;
+    uint32_t *min_len;
+    double   *score, *variance, *second_score;
+    uint32_t *n_accepted;
+} rattle_assignment;
+
+/* The core: targets and reads are ids into the set rattle_hip_load_reads loaded (strands as for cluster_reads: both_strands = !is_rna).
+ * The targets go in batches of target_batch seeds against all the reads.  n_targets == 0 or n_reads == 0: every read unassigned.
+ * RATTLE_ERR_STATE, before anything is exchanged, on a context that is one rank of several: sharded jobs are not built. */
+int rattle_hip_assign_loaded(rattle_ctx *ctx, const rattle_assign_params *params, const uint32_t *target_ids, uint32_t n_targets,
+                             const uint32_t *read_ids, uint32_t n_reads, rattle_assignment **out);
+/* Targets and reads from two buffers, in any order (no length sort is needed).  The reads go through in chunks of read_chunk, each
+ * indexed together with the targets (replacing the loaded read set), so the device memory is bounded by the chunk, not by the sample;
+ * the records come back in the caller's read order. */
+int rattle_hip_assign_reads(rattle_ctx *ctx, const uint8_t *target_concat, const uint64_t *target_offsets, uint32_t n_targets,
+                            const uint8_t *read_concat, const uint64_t *read_offsets, uint32_t n_reads, int kmer_size,
+                            const rattle_assign_params *params, rattle_assignment **out);
+void rattle_hip_assignment_free(rattle_assignment *a);
+
+/* ------------------------------------------------------------------------------------
  * a15  spoa engine + graph as called from /root/reference/correct.cpp:395-405,428-436,520-532
  * (createAlignmentEngine(kSW,5,-4,-8,-6); align + add_alignment per sequence;
  * generate_multiple_sequence_alignment).  Packs are independent; pack p holds sequences
@@ -530,7 +579,8 @@ void rattle_hip_debug_consensus_support_free(rattle_debug_support *d);
 
 /* ------------------------------------------------------------------------------------
  * Per-kernel timing measured with HIP events on the stream the kernels run on.
- * kernel: 0 kmer_extract, 1 bv_filter, 2 pair_score, 3 poa_align, 4 post_msa.  Accumulated since
+ * kernel: 0 kmer_extract, 1 bv_filter, 2 pair_score, 3 poa_align, 4 post_msa, 5 the per-read reduction of
+ * assign (alg_bytes: the bytes of its records copied to the host).  Accumulated since
  * the last reset: total milliseconds, number of launches, algorithmic bytes moved.
  */
 int rattle_hip_kernel_stats(rattle_ctx *ctx, int kernel, double *total_ms, uint64_t *launches, uint64_t *alg_bytes);

@@ -131,6 +131,20 @@ class ClusterReport(C.Structure):
     _fields_ = [("n", C.c_uint64)] + [(f, C.POINTER(t)) for f, t in CLUSTER_REPORT_FIELDS]
 
 
+class AssignParams(C.Structure):
+    _fields_ = [("t_s", C.c_double), ("t_v", C.c_double), ("bv_threshold", C.c_double), ("use_hc", C.c_int), ("is_rna", C.c_int),
+                ("target_batch", C.c_uint32), ("read_chunk", C.c_uint32), ("count_pass", C.c_int)]
+
+
+# the per-read record of assign (rattle_assignment): one entry per read
+ASSIGN_FIELDS = (("target", C.c_int32), ("rev", C.c_uint8), ("bases", C.c_int32), ("hc_bases", C.c_int32), ("min_len", C.c_uint32),
+                 ("score", C.c_double), ("variance", C.c_double), ("second_score", C.c_double), ("n_accepted", C.c_uint32))
+
+
+class Assignment(C.Structure):
+    _fields_ = [("n", C.c_uint32)] + [(f, C.POINTER(t)) for f, t in ASSIGN_FIELDS]
+
+
 # int fn(void *user, const void *send, uint64 send_bytes, void *recv, const uint64 *recv_bytes)
 ALLGATHERV_FN = C.CFUNCTYPE(C.c_int, C.c_void_p, C.c_void_p, C.c_uint64, C.c_void_p, C.POINTER(C.c_uint64))
 
@@ -173,6 +187,10 @@ SIGNATURES = {
     "rattle_hip_set_cluster_report": (C.c_int, [C.c_void_p, C.c_int]),
     "rattle_hip_cluster_report": (C.c_int, [_P(ClusterSet), _P(_P(ClusterReport))]),
     "rattle_hip_cluster_report_free": (None, [_P(ClusterReport)]),
+    "rattle_hip_assign_loaded": (C.c_int, [C.c_void_p, _P(AssignParams), _u32p, C.c_uint32, _u32p, C.c_uint32, _P(_P(Assignment))]),
+    "rattle_hip_assign_reads": (C.c_int, [C.c_void_p, _u8p, _u64p, C.c_uint32, _u8p, _u64p, C.c_uint32, C.c_int, _P(AssignParams),
+                                          _P(_P(Assignment))]),
+    "rattle_hip_assignment_free": (None, [_P(Assignment)]),
     "rattle_hip_poa_msa": (C.c_int, [C.c_void_p, _u8p, _u64p, C.c_uint32, _u32p, C.c_uint32, _P(_P(MsaSet))]),
     "rattle_hip_msa_set_free": (None, [_P(MsaSet)]),
     "rattle_hip_correct_reads": (C.c_int, [C.c_void_p, _u8p, _u8p, _u64p, C.c_uint32, C.c_uint32, _u32p, _i32p, _u8p,

@@ -18,7 +18,7 @@ import numpy as np
 from . import _lib
 from ._lib import ClusterParams, ClusterSet, Correction, CorrectParams, MsaSet, check
 
-K_KMER, K_FILTER, K_SCORE, K_POA, K_POST = 0, 1, 2, 3, 4
+K_KMER, K_FILTER, K_SCORE, K_POA, K_POST, K_ASSIGN = 0, 1, 2, 3, 4, 5
 
 
 def _ptr(a: np.ndarray, t):
@@ -569,6 +569,48 @@ class Context:
         check(self.lib.rattle_hip_comm_stats(self.h, C.byref(a), C.byref(b)))
         return a.value, b.value
 
+    # assign
+    def _take_assignment(self, out) -> dict:
+        n = int(out.contents.n)
+        res = {f: np.ctypeslib.as_array(getattr(out.contents, f), (max(n, 1),))[:n].copy() for f, _ in _lib.ASSIGN_FIELDS}
+        self.lib.rattle_hip_assignment_free(out)
+        return res
+
+    def assign_loaded(self, target_ids, read_ids, t_s=0.2, t_v=1000000.0, bv_threshold=0.4, use_hc=False, is_rna=False,
+                      target_batch=0, count_pass="auto") -> dict:
+        """The loaded reads `read_ids` placed on the loaded reads `target_ids` by their best cluster_together score
+        (rattle_hip_assign_loaded).  Returns a dict of arrays with one entry per read (_lib.ASSIGN_FIELDS): target (index into
+        target_ids, -1: unassigned), rev, bases, hc_bases, min_len, score, variance, second_score (-1.0: no other target accepts),
+        n_accepted.  count_pass as for debug_evaluate."""
+        P = _lib.AssignParams(t_s, t_v, bv_threshold, int(use_hc), int(is_rna), int(target_batch), 0,
+                              {"auto": 0, "seed": 1, "search": 2, "index": 3}[count_pass])
+        t = np.ascontiguousarray(target_ids, np.uint32)
+        r = np.ascontiguousarray(read_ids, np.uint32)
+        out = C.POINTER(_lib.Assignment)()
+        check(self.lib.rattle_hip_assign_loaded(self.h, C.byref(P), _ptr(t, C.c_uint32) if len(t) else None, len(t),
+                                                _ptr(r, C.c_uint32) if len(r) else None, len(r), C.byref(out)))
+        return self._take_assignment(out)
+
+    def assign(self, targets: Sequence[bytes], reads: Sequence[bytes], k=10, t_s=0.2, t_v=1000000.0, bv_threshold=0.4, use_hc=False,
+               is_rna=False, target_batch=0, read_chunk=0, count_pass="auto") -> dict:
+        """`reads` placed on `targets` (rattle_hip_assign_reads): both in any order, the reads indexed read_chunk at a time together
+        with the targets (this replaces the context's loaded reads).  The result as for assign_loaded, target = index into `targets`."""
+        P = _lib.AssignParams(t_s, t_v, bv_threshold, int(use_hc), int(is_rna), int(target_batch), int(read_chunk),
+                              {"auto": 0, "seed": 1, "search": 2, "index": 3}[count_pass])
+        tcat, toff = pack_reads(targets)
+        rcat, roff = pack_reads(reads)
+        return self.assign_packed(tcat, toff, rcat, roff, k, P)
+
+    def assign_packed(self, tcat: np.ndarray, toff: np.ndarray, rcat: np.ndarray, roff: np.ndarray, k=10, params=None) -> dict:
+        """assign() on packed arrays (pack_reads); params: an _lib.AssignParams, None = the defaults of assign()."""
+        P = params if params is not None else _lib.AssignParams(0.2, 1000000.0, 0.4, 0, 0, 0, 0, 0)
+        out = C.POINTER(_lib.Assignment)()
+        check(self.lib.rattle_hip_assign_reads(self.h, _ptr(tcat, C.c_uint8) if len(tcat) else None, _ptr(toff, C.c_uint64), len(toff) - 1,
+                                               _ptr(rcat, C.c_uint8) if len(rcat) else None, _ptr(roff, C.c_uint64), len(roff) - 1, k,
+                                               C.byref(P), C.byref(out)))
+        self.n = self.k = 0               # the loaded read set was replaced by the last chunk's
+        return self._take_assignment(out)
+
     def debug_evaluate(self, rects, t_s=0.2, t_v=1000000.0, use_hc=False, is_rna=False, count_pass="auto"):
         """One evaluation of the greedy clustering on the loaded reads (rattle_hip_debug_evaluate, a test hook).
         rects: list of (seed_ids, cand_ids, thr); cand_ids None = triangular (the seeds against each other, pairs s < c).
@@ -841,3 +883,56 @@ def correct_command(ctx: Context, headers: Sequence[bytes], seqs: Sequence[bytes
         names = [(b"gene_cluster_%d" if gene_mode else b"transcript_cluster_%d") % r[1] for r in res["consensi"]]
         out = out + (support_tsv(names, [r[2] for r in res["consensi"]], res["support"]),)
     return out
+
+
+def _first_token(header: bytes) -> bytes:
+    """the id of a record: the first token of its header, without its '@' / '>'"""
+    h = (header[1:] if header[:1] in (b"@", b">") else header).lstrip(b" \t")
+    return h.replace(b"\t", b" ").split(b" ", 1)[0]
+
+
+def unassigned_records(n: int) -> dict:
+    """n records of assign as the library makes them for reads that nothing accepts"""
+    rec = {f: np.zeros(n, np.dtype(t)) for f, t in _lib.ASSIGN_FIELDS}
+    rec["target"][:] = -1
+    rec["score"][:] = -1.0
+    rec["second_score"][:] = -1.0
+    return rec
+
+
+def assignments_tsv(read_names: Sequence[bytes], target_names: Sequence[bytes], rec: dict) -> bytes:
+    """assignments.tsv as `rattle assign` writes it: a header line, then one line per read in file order: read, target ('*':
+    unassigned), strand (+ / - / *), score, second_score, n_accepted, bases, hc_bases, min_len, variance; doubles as %.17g."""
+    lines = [b"read\ttarget\tstrand\tscore\tsecond_score\tn_accepted\tbases\thc_bases\tmin_len\tvariance\n"]
+    for i, name in enumerate(read_names):
+        t = int(rec["target"][i])
+        lines.append(b"%s\t%s\t%s\t%s\t%s\t%d\t%d\t%d\t%d\t%s\n" % (
+            name, target_names[t] if t >= 0 else b"*", b"*" if t < 0 else b"-" if rec["rev"][i] else b"+",
+            ("%.17g" % rec["score"][i]).encode(), ("%.17g" % rec["second_score"][i]).encode(), int(rec["n_accepted"][i]),
+            int(rec["bases"][i]), int(rec["hc_bases"][i]), int(rec["min_len"][i]), ("%.17g" % rec["variance"][i]).encode()))
+    return b"".join(lines)
+
+
+def target_counts_tsv(target_names: Sequence[bytes], target_lengths: Sequence[int], rec: dict) -> bytes:
+    """target_counts.tsv: a header line, then one line per target in file order: target, length, reads (the reads whose best is this
+    target), unique_reads (those among them that no other target accepts: second_score < 0)."""
+    t = np.asarray(rec["target"], np.int64)
+    hit = t >= 0
+    reads = np.bincount(t[hit], minlength=len(target_names))
+    uniq = np.bincount(t[hit & (np.asarray(rec["second_score"]) < 0)], minlength=len(target_names))
+    return b"target\tlength\treads\tunique_reads\n" + b"".join(
+        b"%s\t%d\t%d\t%d\n" % (n, int(l), int(reads[i]), int(uniq[i])) for i, (n, l) in enumerate(zip(target_names, target_lengths)))
+
+
+def assign_command(ctx: Context, read_headers: Sequence[bytes], reads: Sequence[bytes], target_headers: Sequence[bytes],
+                   targets: Sequence[bytes], *, k=10, t_s=0.2, t_v=1000000.0, bv_threshold=0.4, is_rna=False, count_pass="auto",
+                   target_batch=0, read_chunk=0):
+    """`rattle assign -i reads -x transcripts` after input parsing: every record of both files takes part, in file order.  Returns the
+    bytes of assignments.tsv and of target_counts.tsv.  A read with a base other than A, C, G, T, U is not compared: unassigned."""
+    sent = [i for i, s in enumerate(reads) if not s.translate(None, b"ACGTU")]
+    got = ctx.assign(targets, [reads[i] for i in sent], k, t_s, t_v, bv_threshold, False, is_rna, target_batch, read_chunk, count_pass)
+    rec = unassigned_records(len(reads))
+    for f in rec:
+        rec[f][sent] = got[f]
+    tn = [_first_token(h) for h in target_headers]
+    return (assignments_tsv([_first_token(h) for h in read_headers], tn, rec), target_counts_tsv(tn, [len(s) for s in targets], rec))

@@ -607,6 +607,94 @@ void rattle_hip_cluster_report_free(rattle_cluster_report *r) {
     free(r);
 }
 
+// ---- assign ---------------------------------------------------------------------------------------------------------------
+// n records, every read unassigned
+static rattle_assignment *new_assignment(uint32_t n) {
+    const size_t m = std::max<size_t>(1, n);
+    rattle_assignment *A = (rattle_assignment *)calloc(1, sizeof(rattle_assignment));
+    A->n = n;
+    A->target = (int32_t *)malloc(4 * m); A->rev = (uint8_t *)calloc(m, 1);
+    A->bases = (int32_t *)calloc(m, 4); A->hc_bases = (int32_t *)calloc(m, 4); A->min_len = (uint32_t *)calloc(m, 4);
+    A->score = (double *)malloc(8 * m); A->variance = (double *)calloc(m, 8); A->second_score = (double *)malloc(8 * m);
+    A->n_accepted = (uint32_t *)calloc(m, 4);
+    for (size_t i = 0; i < m; ++i) { A->target[i] = -1; A->score[i] = -1.0; A->second_score[i] = -1.0; }
+    return A;
+}
+
+// what both entry points require of their parameters and of the context, in the order the header promises: arguments, then the
+// refusal of a sharded job (before anything is exchanged), then the device
+static int assign_enter(rattle_ctx *c, const rattle_assign_params *P) {
+    if (P->count_pass < 0 || P->count_pass > 3) { set_error("count_pass must be 0 (auto), 1 (seed-major), 2 (search) or 3 (index)"); return RATTLE_ERR_ARG; }
+    if (c->xchg.nranks > 1) {
+        set_error("assign is not available on a context that is one rank of several: sharded jobs are not built, assign on one device");
+        return RATTLE_ERR_STATE;
+    }
+    return use_device(c);
+}
+
+int rattle_hip_assign_loaded(rattle_ctx *c, const rattle_assign_params *P, const uint32_t *tids, uint32_t nt, const uint32_t *rids,
+                             uint32_t nr, rattle_assignment **out) {
+    if (out) *out = nullptr;
+    if (!c || !P || !out || (nt && !tids) || (nr && !rids)) { set_error("null argument"); return RATTLE_ERR_ARG; }
+    if (nt >= (1u << 31)) { set_error("too many targets"); return RATTLE_ERR_ARG; }
+    RT_TRY(assign_enter(c, P));
+    if (nt && nr) {
+        if (c->idx.k == 0) { set_error("no reads loaded"); return RATTLE_ERR_STATE; }
+        if (!P->is_rna && !c->idx.both) { set_error("cDNA mode needs the reads loaded with both_strands=1"); return RATTLE_ERR_STATE; }
+        if (P->is_rna && c->idx.both) { set_error("--rna mode needs the reads loaded with both_strands=0"); return RATTLE_ERR_STATE; }
+        for (uint32_t i = 0; i < nt; ++i) if (tids[i] >= c->idx.n) { set_error("target id out of range"); return RATTLE_ERR_ARG; }
+        for (uint32_t i = 0; i < nr; ++i) if (rids[i] >= c->idx.n) { set_error("read id out of range"); return RATTLE_ERR_ARG; }
+    }
+    rattle_assignment *A = new_assignment(nr);
+    const int rc = assign_driver(c, P, tids, nt, rids, nr, A, 0);
+    if (rc != 0) { rattle_hip_assignment_free(A); return rc; }
+    *out = A;
+    return 0;
+}
+
+int rattle_hip_assign_reads(rattle_ctx *c, const uint8_t *tseq, const uint64_t *toff, uint32_t nt, const uint8_t *rseq, const uint64_t *roff,
+                            uint32_t nr, int k, const rattle_assign_params *P, rattle_assignment **out) {
+    if (out) *out = nullptr;
+    if (!c || !P || !out || !toff || !roff || (nt && !tseq) || (nr && !rseq)) { set_error("null argument"); return RATTLE_ERR_ARG; }
+    if (k < 1 || k > 16) { set_error("kmer size must be in [1,16] (main.cpp:223)"); return RATTLE_ERR_ARG; }
+    if (nt >= (1u << 31)) { set_error("too many targets"); return RATTLE_ERR_ARG; }
+    RT_TRY(assign_enter(c, P));
+    phase_timer T_all("assign_reads: total");
+    rattle_assignment *A = new_assignment(nr);
+    struct freer { rattle_assignment *p; ~freer() { rattle_hip_assignment_free(p); } } guard{A};
+    const uint64_t tbytes = nt ? toff[nt] - toff[0] : 0;
+    const uint32_t chunk = (uint32_t)std::min<uint64_t>(P->read_chunk ? P->read_chunk : 1u << 20, 0xFFFFFFF0ull - nt);
+    std::vector<uint32_t> tids(nt), rids;
+    for (uint32_t i = 0; i < nt; ++i) tids[i] = i;
+    std::vector<uint64_t> off;
+    std::unique_ptr<uint8_t[]> cat;
+    size_t cat_cap = 0;
+    for (uint64_t r0 = 0; nt && r0 < nr; r0 += chunk) {
+        // the targets, then the chunk's reads, as ONE read set: ids [0, nt) and [nt, nt + m)
+        const uint32_t m = (uint32_t)std::min<uint64_t>(chunk, nr - r0);
+        const uint64_t rbytes = roff[r0 + m] - roff[r0];
+        if (tbytes + rbytes + 1 > cat_cap) { cat_cap = tbytes + rbytes + 1; cat.reset(new uint8_t[cat_cap]); if (tbytes) memcpy(cat.get(), tseq + toff[0], tbytes); }
+        if (rbytes) memcpy(cat.get() + tbytes, rseq + roff[r0], rbytes);
+        off.resize((size_t)nt + m + 1);
+        for (uint32_t i = 0; i <= nt; ++i) off[i] = toff[i] - toff[0];
+        for (uint32_t i = 0; i <= m; ++i) off[(size_t)nt + i] = tbytes + (roff[r0 + i] - roff[r0]);
+        RT_TRY(build_index(c, cat.get(), off.data(), nt + m, k, P->is_rna ? 0 : 1));
+        rids.resize(m);
+        for (uint32_t i = 0; i < m; ++i) rids[i] = nt + i;
+        RT_TRY(assign_driver(c, P, tids.data(), nt, rids.data(), m, A, (uint32_t)r0));
+    }
+    guard.p = nullptr;
+    *out = A;
+    return 0;
+}
+
+void rattle_hip_assignment_free(rattle_assignment *a) {
+    if (!a) return;
+    free(a->target); free(a->rev); free(a->bases); free(a->hc_bases); free(a->min_len); free(a->score); free(a->variance);
+    free(a->second_score); free(a->n_accepted);
+    free(a);
+}
+
 int rattle_hip_poa_msa(rattle_ctx *c, const uint8_t *seq, const uint64_t *off, uint32_t n_seqs, const uint32_t *pack_first,
                        uint32_t n_packs, rattle_msa_set **out) {
     if (!c || !off || !pack_first || !out) { set_error("null argument"); return RATTLE_ERR_ARG; }

@@ -207,6 +207,10 @@ struct evaluator {
     int count_mode = 0;                       // 0: RATTLE_PAIR_COUNT, else the nsurv >= 64 ns rule; 1: seed-major; 2: search; 3: index
     uint64_t n_form[3] = {0, 0, 0};           // evaluations whose count pass was seed-major / search / index (RATTLE_TIMING)
     eval_sink *sink = nullptr;                // test hook only
+    // `assign`: the evaluation ends in the per-read reduction of assign.hip instead of the hit list (one rectangular request per
+    // evaluation: target batch x reads); the batch's state and the index of the batch's first target
+    const assign_dev *best = nullptr;
+    uint32_t best_base = 0;
     // RATTLE_TIMING: where the host's wall time of a clustering goes
     double t_split[6] = {0, 0, 0, 0, 0, 0};
     std::chrono::steady_clock::time_point t_mark;
@@ -464,6 +468,7 @@ struct evaluator {
         struct unswap { rattle_ctx *c; ~unswap() { c->d_pi.swap(c->d_pi2); c->d_pj.swap(c->d_pj2); c->d_ps.swap(c->d_ps2); } } back{ctx};
         RT_TRY(launch_pair_score(ctx, n2));
         ++launches;
+        if (best) return reduce_best(n2, nrect);
         // verdicts on the device: d_surv (free since the count pass compacted it into d_slot2) takes the accepted pairs, the tail
         // of the statistics buffer the three counters, d_pi2 (= the swapped-out d_pi: n2 <= nsurv words) the oversize list
         unsigned long long *vout = ctx->d_bound_stats.p + 2 + 3 * (size_t)nrect;
@@ -534,6 +539,39 @@ struct evaluator {
             if (report) reqs[rect_req[rj]]->ev.push_back(ctx->h_hit_ev.p[q]);
         }
         for (uint32_t j = 0; j < nrect; ++j) if (reqs[rect_req[j]]->triangular) sort_hits(*reqs[rect_req[j]]);      // level 2 takes them in any order
+        lap(4);
+        return 0;
+    }
+
+    // The other ending of an evaluation (`assign`): no hit list; every accepted pair goes into the per-read reduction.  Pass 1 also lists
+    // the pairs whose match list did not fit LDS, as the verdict kernel does; the oversize pass fills their res / var in place and pass
+    // 1 takes them in, before passes 2 and 3 run over all n2 pairs.  The host reads the three counters (and the oversize slots).
+    int reduce_best(uint32_t n2, uint32_t nrect) {
+        hipStream_t st = ctx->stream;
+        if (nrect != 1 || rects[0].s_base != 0 || rects[0].c_base != 0) { set_error("assign: one rectangular request per evaluation"); return RATTLE_ERR_STATE; }
+        unsigned long long *vout = ctx->d_bound_stats.p + 2 + 3 * (size_t)nrect, *hv = ctx->h_bound_stats.p + 2 + 3 * (size_t)nrect;
+        uint32_t *d_big = ctx->d_pi2.p;                   // (= the swapped-out d_pi: n2 <= nsurv words)
+        const int use_hc = P->use_hc ? 1 : 0;
+        RT_TRY(launch_assign_max(ctx, n2, nullptr, use_hc, P->t_s, P->t_v, vout, d_big, *best));
+        ++launches;
+        RT_HIP(hipMemcpyAsync(hv, vout, 24, hipMemcpyDeviceToHost, st));
+        RT_HIP(hipStreamSynchronize(st));
+        if (hv[1]) {
+            const uint32_t nbig = (uint32_t)hv[1], big_m = (uint32_t)hv[2];
+            if (hv[1] > n2) { set_error("assign: more oversize pairs than full comparisons"); return RATTLE_ERR_HIP; }
+            std::vector<uint32_t> big(nbig);
+            RT_HIP(hipMemcpyAsync(big.data(), d_big, (size_t)nbig * 4, hipMemcpyDeviceToHost, st));
+            RT_HIP(hipStreamSynchronize(st));
+            RT_TRY(launch_pair_score_oversize(ctx, big, big_m));
+            RT_HIP(hipMemsetAsync(vout + 1, 0, 16, st));
+            RT_TRY(launch_assign_max(ctx, nbig, d_big, use_hc, P->t_s, P->t_v, vout, d_big, *best));
+            launches += 2;
+            RT_HIP(hipMemcpyAsync(hv, vout, 24, hipMemcpyDeviceToHost, st));
+            RT_HIP(hipStreamSynchronize(st));
+            if (hv[1]) { set_error("pair_score: a pair is still oversize after the oversize pass"); return RATTLE_ERR_HIP; }
+        }
+        RT_TRY(launch_assign_pick(ctx, n2, use_hc, P->t_s, P->t_v, best_base, *best));
+        launches += 2;
         lap(4);
         return 0;
     }
@@ -977,6 +1015,67 @@ int debug_evaluate(rattle_ctx *ctx, const rattle_cluster_params *P, int count_mo
     D->filter_launches = sink.filter_launches;
     D->oversize_pairs = sink.oversize;
     *out = D;
+    return 0;
+}
+
+// `assign`: the loaded reads read_ids against the loaded reads target_ids, the targets as seeds in batches against all the reads, every
+// batch one evaluation that ends in the per-read reduction; the batches' states are folded on the device in target order and the
+// call's state -- 40 bytes per read -- is the only thing copied back.
+int assign_driver(rattle_ctx *ctx, const rattle_assign_params *AP, const uint32_t *tids, uint32_t nt, const uint32_t *rids, uint32_t nr,
+                  rattle_assignment *A, uint32_t out_base) {
+    if (nt == 0 || nr == 0) return 0;                    // (the records start out unassigned)
+    hipStream_t st = ctx->stream;
+    const read_index &X = ctx->idx;
+    rattle_cluster_params CP;
+    memset(&CP, 0, sizeof CP);
+    CP.t_s = AP->t_s; CP.t_v = AP->t_v; CP.bv_threshold = AP->bv_threshold; CP.use_hc = AP->use_hc; CP.is_rna = AP->is_rna;
+    assign_state batch, call;                            // allocated once per call, released when it returns
+    RT_TRY(batch.reserve(nr)); RT_TRY(call.reserve(nr));
+    RT_TRY(batch.clear(st, nr)); RT_TRY(call.clear(st, nr));
+    const assign_dev B = batch.dev(), G = call.dev();
+    evaluator E{ctx, &CP};
+    E.count_mode = AP->count_pass;
+    E.best = &B;
+    uint64_t counters[8] = {0, 0, 0, 0, 0, 0, 0, 0};
+    request rq;
+    rq.cands.assign(rids, rids + nr);
+    rq.thr = AP->bv_threshold; rq.counters = counters;
+    // seeds x reads x strands below the evaluator's per-launch bounds even if every pair survives (as job::step sizes its rounds)
+    const uint64_t per_seed = (uint64_t)nr * (X.both ? 2u : 1u);
+    const uint64_t cap = rq.thr == 0.0 ? (64ull << 20) : (1ull << 31);
+    const uint32_t step = (uint32_t)std::max<uint64_t>(1, std::min<uint64_t>(AP->target_batch ? AP->target_batch : 512u, cap / per_seed));
+    std::vector<request *> reqs{&rq};
+    for (uint32_t t0 = 0; t0 < nt; t0 += step) {
+        rq.seeds.assign(tids + t0, tids + std::min<uint64_t>(nt, (uint64_t)t0 + step));
+        E.best_base = t0;
+        RT_TRY(E.run_chunks(reqs));
+        RT_TRY(launch_assign_merge(ctx, nr, B, G));
+    }
+    std::vector<unsigned long long> best(nr), second(nr);
+    std::vector<uint32_t> key(nr), n(nr);
+    std::vector<hit_evidence> ev(nr);
+    static_assert(sizeof(hit_evidence) == sizeof(uint4), "the evidence record is one 16-byte store");
+    RT_HIP(hipMemcpyAsync(best.data(), G.best, (size_t)nr * 8, hipMemcpyDeviceToHost, st));
+    RT_HIP(hipMemcpyAsync(second.data(), G.second, (size_t)nr * 8, hipMemcpyDeviceToHost, st));
+    RT_HIP(hipMemcpyAsync(key.data(), G.key, (size_t)nr * 4, hipMemcpyDeviceToHost, st));
+    RT_HIP(hipMemcpyAsync(n.data(), G.n, (size_t)nr * 4, hipMemcpyDeviceToHost, st));
+    RT_HIP(hipMemcpyAsync(ev.data(), G.ev, (size_t)nr * sizeof(uint4), hipMemcpyDeviceToHost, st));
+    RT_HIP(hipStreamSynchronize(st));
+    ctx->stats[K_ASSIGN].bytes += 40ull * nr;
+    auto score_of = [](unsigned long long pat) { double d; const unsigned long long b = pat - 1; memcpy(&d, &b, 8); return d; };
+    for (uint32_t r = 0; r < nr; ++r) {
+        if (best[r] == 0) continue;
+        const size_t o = (size_t)out_base + r;
+        const uint32_t t = key[r] >> 1;
+        if (t >= nt) { set_error("assign: a winner outside the targets"); return RATTLE_ERR_HIP; }
+        const uint32_t li = X.h_len[tids[t]], lj = X.h_len[rids[r]];
+        A->target[o] = (int32_t)t; A->rev[o] = (uint8_t)(key[r] & 1u);
+        A->bases[o] = ev[r].bases; A->hc_bases[o] = ev[r].hc; A->variance[o] = ev[r].var;
+        A->min_len[o] = li < lj ? li : lj;
+        A->score[o] = score_of(best[r]);
+        A->second_score[o] = second[r] ? score_of(second[r]) : -1.0;
+        A->n_accepted[o] = n[r];
+    }
     return 0;
 }
 

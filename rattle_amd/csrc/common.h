@@ -129,7 +129,7 @@ struct hbuf {
     }
 };
 
-enum { K_KMER = 0, K_FILTER = 1, K_SCORE = 2, K_POA = 3, K_POST = 4, K_COUNT = 5 };
+enum { K_KMER = 0, K_FILTER = 1, K_SCORE = 2, K_POA = 3, K_POST = 4, K_ASSIGN = 5, K_COUNT = 6 };
 
 struct kstat {
     double ms = 0;
@@ -323,6 +323,19 @@ struct cluster_box {
 rattle_cluster_set *new_cluster_set();
 cluster_box *cluster_box_of(const rattle_cluster_set *cs);
 
+// `assign` (assign.hip): the reduction's state per read, as the kernels see it and as its owner holds it.  best / second: bit pattern of
+// a score + 1 (0: none); key: target index << 1 | strand of the winner (0xFFFFFFFF: none); n: accepted comparisons; ev: the winner's
+// bases, hc_bases and the variance's 64 bits.  40 bytes per read.
+struct assign_dev { unsigned long long *best, *second; uint32_t *key, *n; uint4 *ev; };
+struct assign_state {
+    dbuf<unsigned long long> best, second;
+    dbuf<uint32_t> key, n;
+    dbuf<uint4> ev;
+    int reserve(size_t nr);
+    int clear(hipStream_t st, size_t nr);
+    assign_dev dev() const { return assign_dev{best.p, second.p, key.p, n.p, ev.p}; }
+};
+
 int hw_queues();      // hardware queues the HIP runtime of this process hands out (settled when the library is loaded, abi.hip)
 
 }  // namespace rattle
@@ -442,6 +455,11 @@ int launch_pair_count(rattle_ctx *ctx, uint32_t n_pairs);
 // pair_index.hip : the count pass over an inverted k-mer index of the evaluation's seeds (survivors grouped by candidate)
 int group_survivors_by_cand(rattle_ctx *ctx, uint32_t n, uint64_t n_cands);
 int launch_pair_count_index(rattle_ctx *ctx, uint32_t n_pairs, const uint32_t *h_seed, uint32_t ns, uint32_t nc, bool many);
+// assign.hip : the per-read reduction over the kept pairs of the evaluation in flight (ctx->d_res / d_var / d_pi / d_pj / d_slot2)
+int launch_assign_max(rattle_ctx *ctx, uint32_t n, const uint32_t *d_remap, int use_hc, double t_s, double t_v, unsigned long long *d_out,
+                      uint32_t *d_big, const assign_dev &B);
+int launch_assign_pick(rattle_ctx *ctx, uint32_t n, int use_hc, double t_s, double t_v, uint32_t target_base, const assign_dev &B);
+int launch_assign_merge(rattle_ctx *ctx, uint32_t nr, const assign_dev &B, const assign_dev &G);
 // poa.hip : the words of kernel C's counter block (poa_args::counters, POA_CNT_WORDS on the device); poa_device_run hands the first
 // POA_CNT_PUBLIC of them back in h_cnt.  The only place that says which slot is what.  The measurement builds reuse slots by number:
 // POA_PREDSTAT 4 .. 6, POA_PROFILE 2 and 4 .. 7, POA_BARPROF 8 .. 15 (and POA_CNT_BARPROF ..), POA_HIST 16 + d and 80 + d.
@@ -477,6 +495,9 @@ int cluster_driver(rattle_ctx *ctx, const rattle_cluster_params *P, const uint32
                    rattle_cluster_set **out);
 int debug_evaluate(rattle_ctx *ctx, const rattle_cluster_params *P, int count_mode, const rattle_debug_rect *R, uint32_t n_rects,
                    rattle_debug_eval **out);
+// records [out_base, out_base + n_reads) of A: the loaded reads read_ids placed on the loaded reads target_ids
+int assign_driver(rattle_ctx *ctx, const rattle_assign_params *P, const uint32_t *target_ids, uint32_t n_targets, const uint32_t *read_ids,
+                  uint32_t n_reads, rattle_assignment *A, uint32_t out_base);
 
 // correct_driver.hip
 int debug_post_msa(rattle_ctx *ctx, const rattle_correct_params *P, int mode, const rattle_debug_msa *in, rattle_debug_post **out);

@@ -782,6 +782,101 @@ int mode_cluster(int argc, char **argv) {
     return EXIT_SUCCESS;
 }
 
+// `rattle assign`: the reads of -i placed on the transcripts of -x by their best cluster_together score (include/rattle_hip.h, "assign").
+// Every record of both files takes part, in file order: there is no length filter and no sort.  A read with a base other than A, C,
+// G, T, U is not compared and comes out unassigned (`cluster` skips such reads).
+int mode_assign(int argc, char **argv) {
+    std::vector<opt_def> defs = {
+        {"help", {"-h", "--help"}, false}, {"input", {"-i", "--input"}, true}, {"targets", {"-x", "--transcripts"}, true},
+        {"output", {"-o", "--output"}, true}, {"kmer_size", {"-k", "--kmer-size"}, true}, {"t_s", {"-s", "--score-threshold"}, true},
+        {"t_v", {"-v", "--max-variance"}, true}, {"bv_threshold", {"-B", "--bv-start-threshold"}, true}, {"rna", {"--rna"}, false},
+        {"count-pass", {"--count-pass"}, true}, {"device", {"--device"}, true}, {"devices", {"--devices"}, true},
+        {"target-batch", {"--target-batch"}, true}, {"read-chunk", {"--read-chunk"}, true}};
+    args_t a = parse(argc, argv, defs);
+    const char *usage = "rattle assign -i reads.fq -x transcripts.fq [-o dir] [-k 10] [-s 0.2] [-v 1000000] [-B 0.4] [--rna] [--device n]\n"
+                        "  places every read of -i on the transcript of -x that accepts it with the best score (the comparison `cluster` joins\n"
+                        "  reads by, the transcript in the seed's role) and writes assignments.tsv (one line per read: target, strand, score,\n"
+                        "  second_score, n_accepted, bases, hc_bases, min_len, variance) and target_counts.tsv (reads per transcript)\n"
+                        "  --count-pass auto|seed|search|index   form of the count pass (default auto)\n"
+                        "  --target-batch n / --read-chunk n     transcripts per evaluation / reads indexed at a time (the result does not depend on them)\n";
+    if (a.has("help")) { std::cerr << usage; return EXIT_SUCCESS; }
+    if (!a.has("input")) die("ERROR: No input file provided (-i reads)");
+    if (!a.has("targets")) die("ERROR: No transcript file provided (-x transcripts)");
+    if (a.has("devices")) die("\nError: assign runs on one device: --devices is not available, use --device\n");
+    rattle_assign_params P;
+    memset(&P, 0, sizeof P);
+    const std::string form = a.str("count-pass", "auto");
+    if (form == "auto") P.count_pass = 0; else if (form == "seed") P.count_pass = 1; else if (form == "search") P.count_pass = 2;
+    else if (form == "index") P.count_pass = 3;
+    else { std::cerr << "ERROR: --count-pass takes auto, seed, search or index (got '" << form << "')\nusage: " << usage; return EXIT_FAILURE; }
+    const int k = a.i("kmer_size", 10);
+    if (k > 16) die("\nError: maximum kmer size = 16 \n");
+    const std::string outdir = a.str("output", ".");
+    if (a.has("output") && access(outdir.c_str(), F_OK)) die("\nOutput folder doesn't exit. Please create it first. \n");
+    P.t_s = a.d("t_s", 0.2); P.t_v = a.d("t_v", 1000000); P.bv_threshold = a.d("bv_threshold", 0.4);
+    P.is_rna = a.has("rna") ? 1 : 0;
+    P.target_batch = (uint32_t)std::max(0, a.i("target-batch", 0)); P.read_chunk = (uint32_t)std::max(0, a.i("read-chunk", 0));
+    std::cerr << "RNA mode: " << std::boolalpha << (P.is_rna != 0) << std::endl;
+    device_team team;
+    team_opener opener(team, a, 0);
+    read_table R, X;
+    { cli_timer t("read input"); read_table_inputs(R, split_string(a.str("input", ""), ','), {}, false); read_table_inputs(X, split_string(a.str("targets", ""), ','), {}, false); }
+    auto clean = [](const span &s) { for (uint32_t i = 0; i < s.n; ++i) if (!strchr("ACGTU", s.p[i]) || !s.p[i]) return false; return true; };
+    std::vector<uint32_t> rid, xid(X.n());
+    for (size_t i = 0; i < X.n(); ++i) {
+        if (!clean(X.seq[i])) die("\nError: transcript " + X.head(i) + " has a base other than A, C, G, T, U\n");
+        xid[i] = (uint32_t)i;
+    }
+    for (size_t i = 0; i < R.n(); ++i) if (clean(R.seq[i])) rid.push_back((uint32_t)i);
+    if (rid.size() != R.n()) std::cerr << "\n" << R.n() - rid.size() << "  reads with a base other than A, C, G, T, U are left unassigned" << std::endl;
+    std::cout << "Reads: " << R.n() << ", transcripts: " << X.n() << std::endl;
+    byte_buf rcat, xcat;
+    std::vector<uint64_t> roff, xoff;
+    gather_reads(R, rid, rcat, nullptr, roff);
+    gather_reads(X, xid, xcat, nullptr, xoff);
+    opener.wait();
+    rattle_assignment *A = nullptr;
+    { cli_timer t("library: assign"); chk(rattle_hip_assign_reads(team.ctx[0], xcat.data(), xoff.data(), (uint32_t)xid.size(), rcat.data(), roff.data(), (uint32_t)rid.size(), k, &P, &A)); }
+    auto name = [](const span &h) {                                               // the id: the header's first token, without its '@' / '>'
+        const char *b = h.p, *e = h.p + h.n;
+        if (b < e && (*b == '@' || *b == '>')) ++b;
+        while (b < e && (*b == ' ' || *b == '\t')) ++b;
+        const char *t = b;
+        while (t < e && *t != ' ' && *t != '\t') ++t;
+        return std::string(b, t - b);
+    };
+    std::vector<uint64_t> n_best(X.n(), 0), n_unique(X.n(), 0);
+    std::string text = "read\ttarget\tstrand\tscore\tsecond_score\tn_accepted\tbases\thc_bases\tmin_len\tvariance\n";
+    char num[3][40];
+    size_t at = 0;                                                                // next submitted read
+    for (size_t i = 0; i < R.n(); ++i) {
+        const bool sent = at < rid.size() && rid[at] == i;
+        const int32_t t = sent ? A->target[at] : -1;
+        snprintf(num[0], sizeof num[0], "%.17g", sent ? A->score[at] : -1.0);
+        snprintf(num[1], sizeof num[1], "%.17g", sent ? A->second_score[at] : -1.0);
+        snprintf(num[2], sizeof num[2], "%.17g", sent ? A->variance[at] : 0.0);
+        text += name(R.header[i]) + "\t" + (t >= 0 ? name(X.header[t]) : std::string("*")) + "\t" + (t < 0 ? "*" : A->rev[at] ? "-" : "+") + "\t" +
+                num[0] + "\t" + num[1] + "\t" + std::to_string(sent ? A->n_accepted[at] : 0u) + "\t" + std::to_string(sent ? A->bases[at] : 0) + "\t" +
+                std::to_string(sent ? A->hc_bases[at] : 0) + "\t" + std::to_string(sent ? A->min_len[at] : 0u) + "\t" + num[2] + "\n";
+        if (t >= 0) { ++n_best[t]; if (A->second_score[at] < 0) ++n_unique[t]; }
+        if (sent) ++at;
+    }
+    rattle_hip_assignment_free(A);
+    std::string counts = "target\tlength\treads\tunique_reads\n";
+    for (size_t t = 0; t < X.n(); ++t)
+        counts += name(X.header[t]) + "\t" + std::to_string(X.seq[t].n) + "\t" + std::to_string(n_best[t]) + "\t" + std::to_string(n_unique[t]) + "\n";
+    for (auto &f : {std::make_pair(std::string("assignments.tsv"), &text), std::make_pair(std::string("target_counts.tsv"), &counts)}) {
+        const std::string path = outdir + "/" + f.first;
+        std::ofstream o(path);
+        o << *f.second;
+        o.close();
+        if (!o) die("Error: cannot write " + path);
+    }
+    team.close();
+    std::cerr << "Done" << std::endl;
+    return EXIT_SUCCESS;
+}
+
 int mode_correct(int argc, char **argv) {
     std::vector<opt_def> defs = {
         {"help", {"-h", "--help"}, false}, {"input", {"-i", "--input"}, true}, {"label", {"-l", "--label"}, true},
@@ -1226,19 +1321,20 @@ int mode_polish(int argc, char **argv) {
 int main(int argc, char **argv) {
     setenv("GPU_MAX_HW_QUEUES", "12", 0);      // before the HIP runtime starts: the POA column classes of a pass run concurrently, one hardware queue each (poa.hip)
     if (argc < 2) {
-        std::cout << "Run with mode: ./rattle <cluster|cluster_summary|extract_clusters|correct|polish>" << std::endl;
+        std::cout << "Run with mode: ./rattle <cluster|cluster_summary|extract_clusters|correct|polish|assign>" << std::endl;
         return EXIT_FAILURE;
     }
     try {
         if (!strcmp(argv[1], "cluster")) return mode_cluster(argc, argv);
         if (!strcmp(argv[1], "correct")) return mode_correct(argc, argv);
         if (!strcmp(argv[1], "polish")) return mode_polish(argc, argv);
+        if (!strcmp(argv[1], "assign")) return mode_assign(argc, argv);
         if (!strcmp(argv[1], "cluster_summary")) return mode_cluster_summary(argc, argv);
         if (!strcmp(argv[1], "extract_clusters")) return mode_extract_clusters(argc, argv);
     } catch (const std::exception &e) {
         std::cerr << e.what() << std::endl;
         return EXIT_FAILURE;
     }
-    std::cout << "Run with mode: ./rattle <cluster|cluster_summary|extract_clusters|correct|polish>" << std::endl;
+    std::cout << "Run with mode: ./rattle <cluster|cluster_summary|extract_clusters|correct|polish|assign>" << std::endl;
     return EXIT_FAILURE;
 }
