@@ -131,7 +131,7 @@ int assign_state::clear(hipStream_t st, size_t nr) {
     return 0;
 }
 
-// the pairs are the kept pairs of the evaluation in flight (run_local): ctx->d_res / d_var / d_pi / d_pj / d_slot2
+// the pairs are the kept pairs of the evaluation in flight (evaluator::run_local, after its full_pass): ctx->d_res / d_var / d_pi / d_pj / d_slot2
 int launch_assign_max(rattle_ctx *ctx, uint32_t n, const uint32_t *d_remap, int use_hc, double t_s, double t_v, unsigned long long *d_out,
                       uint32_t *d_big, const assign_dev &B) {
     if (n == 0) return 0;

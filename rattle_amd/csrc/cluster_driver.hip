@@ -30,8 +30,6 @@
 
 namespace rattle {
 
-int launch_pair_score_oversize(rattle_ctx *ctx, const std::vector<uint32_t> &slots, uint32_t max_matches);
-
 // survivor list (seed_slot<<1|strand, cand_slot) -> explicit (read i, read j, strand) pairs
 __global__ void expand_pairs_kernel(const uint32_t *__restrict__ surv, uint32_t n, const uint32_t *__restrict__ seed_ids,
                                     const uint32_t *__restrict__ cand_ids, uint32_t *__restrict__ pi, uint32_t *__restrict__ pj,
@@ -44,7 +42,7 @@ __global__ void expand_pairs_kernel(const uint32_t *__restrict__ surv, uint32_t 
     ps[t] = (uint8_t)(a & 1u);
 }
 
-// cluster.cpp:23-27 turned into an exact rejection on |common| (see run_local): pairs that can still reach t_s are compacted
+// cluster.cpp:23-27 turned into an exact rejection on |common| (see evaluator::count_pass): pairs that can still reach t_s are compacted
 // for the full comparison; survivors / matches per rectangle and the algorithmic bytes are summed on the way.
 // stats: [0] pairs kept, [1] algorithmic bytes, then per rectangle (survivors, matches, pairs kept)
 __global__ __launch_bounds__(256) void count_bound_kernel(const uint32_t *__restrict__ surv, const int32_t *__restrict__ common, uint32_t n,
@@ -199,7 +197,40 @@ struct eval_sink {
     uint64_t filter_launches = 0, oversize = 0;
 };
 
+// Every pair can survive the filter, and in the thr == 0 pass every pair does (cluster.cpp:19,43): one launch keeps its
+// pairs x strands below the 32-bit survivor counter, and below 64 M where all of them survive.
+constexpr uint64_t LAUNCH_PAIRS = 1ull << 31, LAUNCH_PAIRS_SURE = 64ull << 20;
+// the seeds of a batch of `want` whose seeds x candidates x strands stay below these bounds even if every pair survives
+uint32_t max_seeds_per_launch(uint64_t want, uint64_t cands, uint64_t strands, double thr) {
+    const uint64_t per_seed = cands * strands, cap = thr == 0.0 ? LAUNCH_PAIRS_SURE : LAUNCH_PAIRS;
+    return (uint32_t)std::max<uint64_t>(1, std::min<uint64_t>(want, cap / std::max<uint64_t>(per_seed, 1)));
+}
+
 // ---- device evaluation of a set of rectangles -------------------------------------------------------------
+// what one evaluation (evaluator::run_local) hands from step to step
+struct evaluation {
+    rattle_ctx *ctx;
+    request **reqs;
+    size_t nreq;
+    uint64_t ns = 0, nc = 0, npairs = 0;      // seeds, candidates and pairs of all rectangles side by side
+    uint32_t tiles = 0, nrect = 0;
+    bool many = false;                        // more than one request: the statistics go by seed_req
+    std::vector<uint32_t> rect_req;           // rectangle -> its request (empty requests get no rectangle)
+    uint32_t nsurv = 0, n2 = 0;               // survivors of the filter, pairs the count bound kept
+    int form = 0;                             // the count pass: 1 seed-major, 2 search, 3 index
+    // full_pass on: d_surv (free since the count pass compacted it into d_slot2) takes the accepted pairs, the tail of the statistics
+    // buffer the three counters (device, host), d_pi2 (= the swapped-out d_pi: n2 <= nsurv words) the oversize list
+    unsigned long long *vout = nullptr, *hv = nullptr;
+    uint32_t *d_hits = nullptr, *d_big = nullptr;
+    // the cluster report: the evidence of the accepted pairs (at most n2 of them over both verdict launches) beside them
+    bool report = false;
+    uint4 *d_ev = nullptr;
+    // the launchers read d_pi / d_pj / d_ps: full_pass puts the kept pairs there, and they go back on every way out
+    bool swapped = false;
+    void swap_pairs() { ctx->d_pi.swap(ctx->d_pi2); ctx->d_pj.swap(ctx->d_pj2); ctx->d_ps.swap(ctx->d_ps2); swapped = !swapped; }
+    ~evaluation() { if (swapped) swap_pairs(); }
+};
+
 struct evaluator {
     rattle_ctx *ctx;
     const rattle_cluster_params *P;
@@ -211,8 +242,9 @@ struct evaluator {
     // evaluation: target batch x reads); the batch's state and the index of the batch's first target
     const assign_dev *best = nullptr;
     uint32_t best_base = 0;
-    // RATTLE_TIMING: where the host's wall time of a clustering goes
-    double t_split[6] = {0, 0, 0, 0, 0, 0};
+    // RATTLE_TIMING: where the host's wall time of a clustering goes, by run_local's laps.  Lap 3 is the crediting of the count bound's
+    // statistics to the jobs (the line prints it as "host bound test": the test itself has run on the device since round 3).
+    double t_split[5] = {0, 0, 0, 0, 0};
     std::chrono::steady_clock::time_point t_mark;
     void mark() { t_mark = std::chrono::steady_clock::now(); }
     void lap(int i) { const auto now = std::chrono::steady_clock::now(); t_split[i] += std::chrono::duration<double, std::milli>(now - t_mark).count(); t_mark = now; }
@@ -247,60 +279,65 @@ struct evaluator {
         return 0;
     }
 
+    // The piece a rank contributes to the hit exchange of a sharded evaluation: the three counter deltas since `before`, then the hits as
+    // (seed, candidate position, strand) triples.  A rank that scored the candidates at positions r, r + R, ... gives its stride and
+    // offset, so that the positions are the whole request's; the whole request itself takes (1, 0).
+    static std::vector<uint8_t> pack_piece(const uint64_t *counters, const uint64_t *before, const std::vector<hit_t> &hits, uint32_t R, uint32_t r) {
+        std::vector<uint8_t> pay(24 + hits.size() * 12);
+        for (int i = 0; i < 3; ++i) { const uint64_t d = counters[i] - before[i]; memcpy(pay.data() + 8 * i, &d, 8); }
+        for (size_t i = 0; i < hits.size(); ++i) {
+            const uint32_t t[3] = {hits[i].seed, hits[i].cand * R + r, hits[i].rev};
+            memcpy(pay.data() + 24 + 12 * i, t, 12);
+        }
+        return pay;
+    }
+
+    // ... and a piece read back: its deltas added to counters (unless nullptr), its hits appended, except those at the candidate
+    // positions drop, drop + R, ... (drop < 0: none)
+    static int unpack_piece(const std::vector<uint8_t> &b, uint64_t *counters, std::vector<hit_t> &hits, uint32_t R, int drop) {
+        if (b.size() < 24 || (b.size() - 24) % 12) { set_error("cluster exchange: malformed hit list"); return RATTLE_ERR_HIP; }
+        if (counters) for (int i = 0; i < 3; ++i) { uint64_t d; memcpy(&d, b.data() + 8 * i, 8); counters[i] += d; }
+        for (size_t at = 24; at < b.size(); at += 12) {
+            uint32_t t[3];
+            memcpy(t, b.data() + at, 12);
+            if (drop >= 0 && t[1] % R == (uint32_t)drop) continue;
+            hits.push_back(hit_t{t[0], t[1], (uint8_t)t[2]});
+        }
+        return 0;
+    }
+
     // All requests of one greedy step.  shard: this rank scores the candidates at positions rank, rank + nranks, ...
     // of the (single, rectangular) request and the hits of all ranks are all-gathered.
     int run(std::vector<request *> &reqs, bool shard) {
         const int R = ctx->xchg.nranks, r = ctx->xchg.rank;
-        if (shard && R > 1) {
-            if (reqs.size() != 1 || reqs[0]->triangular) { set_error("sharded evaluation takes one rectangular request"); return RATTLE_ERR_STATE; }
-            request &q = *reqs[0];
-            request mine;
-            mine.seeds = q.seeds; mine.thr = q.thr; mine.counters = q.counters;
-            for (uint32_t c = (uint32_t)r; c < q.cands.size(); c += (uint32_t)R) mine.cands.push_back(q.cands[c]);
-            uint64_t before[3] = {q.counters[0], q.counters[1], q.counters[2]};
-            std::vector<request *> one{&mine};
-            RT_TRY(run_chunks(one));
-            // payload: three counter deltas, then (seed, global candidate position, strand) triples
-            std::vector<uint8_t> pay(24 + mine.hits.size() * 12);
-            for (int i = 0; i < 3; ++i) { const uint64_t d = q.counters[i] - before[i]; memcpy(pay.data() + 8 * i, &d, 8); q.counters[i] = before[i]; }
-            for (size_t i = 0; i < mine.hits.size(); ++i) {
-                const uint32_t t[3] = {mine.hits[i].seed, mine.hits[i].cand * (uint32_t)R + (uint32_t)r, mine.hits[i].rev};
-                memcpy(pay.data() + 24 + 12 * i, t, 12);
-            }
-            std::vector<std::vector<uint8_t>> all;
-            RT_TRY(xchg_allgatherv(ctx, pay, all));
-            q.hits.clear();
-            const bool replay = xchg_replaying(ctx);      // (measurement aid, common.h: the piece beside this rank's own is the WHOLE job's hit list)
-            for (int p = 0; p < R; ++p) {
-                const std::vector<uint8_t> &b = all[(size_t)p];
-                if (replay && b.empty()) continue;
-                if (b.size() < 24 || (b.size() - 24) % 12) { set_error("cluster exchange: malformed hit list"); return RATTLE_ERR_HIP; }
-                if (!(replay && p == r)) for (int i = 0; i < 3; ++i) { uint64_t d; memcpy(&d, b.data() + 8 * i, 8); q.counters[i] += d; }
-                for (size_t at = 24; at < b.size(); at += 12) {
-                    uint32_t t[3];
-                    memcpy(t, b.data() + at, 12);
-                    if (replay && p != r && t[1] % (uint32_t)R == (uint32_t)r) continue;      // this rank's own hits arrived in its own piece
-                    q.hits.push_back(hit_t{t[0], t[1], (uint8_t)t[2]});
-                }
-            }
-            return 0;
-        }
-        if (shard && xchg_recording(ctx)) {
+        const bool sharded = shard && R > 1;
+        if (!sharded && !(shard && xchg_recording(ctx))) return run_chunks(reqs);
+        if (reqs.size() != 1 || reqs[0]->triangular) { set_error("sharded evaluation takes one rectangular request"); return RATTLE_ERR_STATE; }
+        request &q = *reqs[0];
+        const uint64_t before[3] = {q.counters[0], q.counters[1], q.counters[2]};
+        std::vector<std::vector<uint8_t>> all;
+        if (!sharded) {
             // single rank, recording: the same payload a sharded job exchanges here, for the whole request
-            if (reqs.size() != 1 || reqs[0]->triangular) { set_error("sharded evaluation takes one rectangular request"); return RATTLE_ERR_STATE; }
-            request &q = *reqs[0];
-            uint64_t before[3] = {q.counters[0], q.counters[1], q.counters[2]};
             RT_TRY(run_chunks(reqs));
-            std::vector<uint8_t> pay(24 + q.hits.size() * 12);
-            for (int i = 0; i < 3; ++i) { const uint64_t d = q.counters[i] - before[i]; memcpy(pay.data() + 8 * i, &d, 8); }
-            for (size_t i = 0; i < q.hits.size(); ++i) {
-                const uint32_t t[3] = {q.hits[i].seed, q.hits[i].cand, q.hits[i].rev};
-                memcpy(pay.data() + 24 + 12 * i, t, 12);
-            }
-            std::vector<std::vector<uint8_t>> all;
-            return xchg_allgatherv(ctx, pay, all);
+            return xchg_allgatherv(ctx, pack_piece(q.counters, before, q.hits, 1, 0), all);
         }
-        return run_chunks(reqs);
+        request mine;
+        mine.seeds = q.seeds; mine.thr = q.thr; mine.counters = q.counters;
+        for (uint32_t c = (uint32_t)r; c < q.cands.size(); c += (uint32_t)R) mine.cands.push_back(q.cands[c]);
+        std::vector<request *> one{&mine};
+        RT_TRY(run_chunks(one));
+        const std::vector<uint8_t> pay = pack_piece(q.counters, before, mine.hits, (uint32_t)R, (uint32_t)r);
+        for (int i = 0; i < 3; ++i) q.counters[i] = before[i];       // every rank's deltas, this one's among them, come back below
+        RT_TRY(xchg_allgatherv(ctx, pay, all));
+        q.hits.clear();
+        const bool replay = xchg_replaying(ctx);      // (measurement aid, common.h: the piece beside this rank's own is the WHOLE job's hit list)
+        for (int p = 0; p < R; ++p) {
+            const std::vector<uint8_t> &b = all[(size_t)p];
+            if (replay && b.empty()) continue;
+            // replaying: this rank's own counters and hits arrived in its own piece
+            RT_TRY(unpack_piece(b, replay && p == r ? nullptr : q.counters, q.hits, (uint32_t)R, replay && p != r ? r : -1));
+        }
+        return 0;
     }
 
     static void sort_hits(request &Q) {
@@ -319,8 +356,7 @@ struct evaluator {
         hits.swap(h2); Q.ev.swap(e2);
     }
 
-    // Every pair can survive the filter, and in the thr == 0 pass every pair does (cluster.cpp:19,43): one launch
-    // keeps its pairs x strands below the 32-bit survivor counter, and below 64 M where all of them survive.
+    // the requests in runs that stay below the per-launch bounds, one evaluation each
     int run_chunks(std::vector<request *> &reqs) {
         const uint64_t strands = ctx->idx.both ? 2u : 1u;
         size_t a = 0;
@@ -330,7 +366,7 @@ struct evaluator {
             while (b < reqs.size()) {
                 const uint64_t p = reqs[b]->n_pairs() * strands;
                 const uint64_t s = reqs[b]->thr == 0.0 ? p : 0;
-                if (b > a && (all_pairs + p > (1ull << 31) || sure + s > (64ull << 20))) break;
+                if (b > a && (all_pairs + p > LAUNCH_PAIRS || sure + s > LAUNCH_PAIRS_SURE)) break;
                 all_pairs += p; sure += s;
                 ++b;
             }
@@ -340,27 +376,45 @@ struct evaluator {
         return 0;
     }
 
+    // one evaluation: the hits of every request (or, with `best` set, the batch's reduction) from the device
     int run_local(request **reqs, size_t nreq) {
-        hipStream_t st = ctx->stream;
-        const read_index &X = ctx->idx;
+        evaluation V{ctx, reqs, nreq};
         mark();
-        // ---- the rectangles side by side in one seed array and one candidate array
-        uint64_t ns = 0, nc = 0, npairs = 0;
-        for (size_t q = 0; q < nreq; ++q) {
-            reqs[q]->hits.clear(); reqs[q]->ev.clear();
-            if (reqs[q]->seeds.empty() || reqs[q]->n_cands() == 0) continue;
-            ns += reqs[q]->seeds.size(); nc += reqs[q]->n_cands();
+        RT_TRY(lay_out(V));
+        if (V.ns == 0 || V.nc == 0) return 0;
+        lap(0);
+        RT_TRY(filter(V));
+        lap(1);
+        if (V.nsurv == 0) return 0;
+        RT_TRY(count_pass(V));
+        lap(2);
+        RT_TRY(credit(V));
+        lap(3);
+        if (V.n2 == 0) return 0;
+        RT_TRY(full_pass(V));
+        RT_TRY(best ? reduce_best(V) : verdicts(V));
+        lap(4);
+        return 0;
+    }
+
+    // the rectangles side by side in one seed array and one candidate array, and on the device
+    int lay_out(evaluation &V) {
+        hipStream_t st = ctx->stream;
+        for (size_t q = 0; q < V.nreq; ++q) {
+            V.reqs[q]->hits.clear(); V.reqs[q]->ev.clear();
+            if (V.reqs[q]->seeds.empty() || V.reqs[q]->n_cands() == 0) continue;
+            V.ns += V.reqs[q]->seeds.size(); V.nc += V.reqs[q]->n_cands();
         }
+        const uint64_t ns = V.ns, nc = V.nc;
         if (ns == 0 || nc == 0) return 0;
         if (ns >= (1u << 31) || nc >= 0xFFFFFFF0ull) { set_error("cluster evaluation: too many seeds or candidates in one step"); return RATTLE_ERR_ARG; }
         h_seed.resize(ns); h_first.resize(ns); h_cand.resize(nc);
         rects.clear();
-        const bool many = nreq > 1;
-        if (many) seed_req.resize(ns);
-        std::vector<uint32_t> rect_req;
-        uint32_t sb = 0, cb = 0, tiles = 0;
-        for (size_t q = 0; q < nreq; ++q) {
-            request &Q = *reqs[q];
+        V.many = V.nreq > 1;
+        if (V.many) seed_req.resize(ns);
+        uint32_t sb = 0, cb = 0;
+        for (size_t q = 0; q < V.nreq; ++q) {
+            request &Q = *V.reqs[q];
             const uint32_t qs = (uint32_t)Q.seeds.size(), qc = Q.n_cands();
             if (qs == 0 || qc == 0) continue;
             uint32_t row = 0;
@@ -368,211 +422,221 @@ struct evaluator {
             memcpy(h_seed.data() + sb, Q.seeds.data(), (size_t)qs * 4);
             memcpy(h_cand.data() + cb, Q.triangular ? Q.seeds.data() : Q.cands.data(), (size_t)qc * 4);
             for (uint32_t s = 0; s < qs; ++s) h_first[sb + s] = cb + (Q.triangular ? s + 1 : 0u);
-            if (many) for (uint32_t s = 0; s < qs; ++s) seed_req[sb + s] = (uint32_t)rects.size();
-            rects.push_back(bvf_rect{sb, qs, cb, qc, tiles, row * 4097u, Q.thr == 0.0 ? 1u : 0u, 0u});
-            rect_req.push_back((uint32_t)q);
-            tiles += ((qc + 255u) / 256u) * ((qs + 31u) / 32u);
+            if (V.many) for (uint32_t s = 0; s < qs; ++s) seed_req[sb + s] = (uint32_t)rects.size();
+            rects.push_back(bvf_rect{sb, qs, cb, qc, V.tiles, row * 4097u, Q.thr == 0.0 ? 1u : 0u, 0u});
+            V.rect_req.push_back((uint32_t)q);
+            V.tiles += ((qc + 255u) / 256u) * ((qs + 31u) / 32u);
             const uint64_t p = Q.n_pairs();
             Q.counters[0] += p;
-            npairs += p;
+            V.npairs += p;
             sb += qs; cb += qc;
         }
-        const uint32_t nrect = (uint32_t)rects.size();
+        V.nrect = (uint32_t)rects.size();
         RT_TRY(ctx->d_seed.reserve(ns)); RT_TRY(ctx->d_first.reserve(ns)); RT_TRY(ctx->d_cand.reserve(nc));
-        RT_TRY(ctx->d_rect.reserve(nrect));
+        RT_TRY(ctx->d_rect.reserve(V.nrect));
         RT_TRY(ctx->d_counter.reserve(4)); RT_TRY(ctx->h_counter.reserve(4));
         RT_HIP(hipMemcpyAsync(ctx->d_seed.p, h_seed.data(), ns * 4, hipMemcpyHostToDevice, st));
         RT_HIP(hipMemcpyAsync(ctx->d_first.p, h_first.data(), ns * 4, hipMemcpyHostToDevice, st));
         RT_HIP(hipMemcpyAsync(ctx->d_cand.p, h_cand.data(), nc * 4, hipMemcpyHostToDevice, st));
-        RT_HIP(hipMemcpyAsync(ctx->d_rect.p, rects.data(), (size_t)nrect * sizeof(bvf_rect), hipMemcpyHostToDevice, st));
+        RT_HIP(hipMemcpyAsync(ctx->d_rect.p, rects.data(), (size_t)V.nrect * sizeof(bvf_rect), hipMemcpyHostToDevice, st));
+        return 0;
+    }
 
-        lap(0);
-        // survivor capacity: grow and retry on overflow (count is exact even when truncated)
+    // kernel A over the rectangle list.  Survivor capacity: grow and retry on overflow (the count is exact even when truncated)
+    int filter(evaluation &V) {
+        hipStream_t st = ctx->stream;
         size_t cap = std::max<size_t>(ctx->d_surv.cap / 2, 1u << 20);
-        uint32_t nsurv = 0;
         while (true) {
             RT_TRY(ctx->d_surv.reserve(cap * 2));
             cap = ctx->d_surv.cap / 2;
             RT_HIP(hipMemsetAsync(ctx->d_counter.p, 0, 16, st));
-            RT_TRY(launch_bv_filter_rects(ctx, nrect, tiles, npairs, false, true, (uint32_t)std::min<size_t>(cap, 0xFFFFFFF0u)));
+            RT_TRY(launch_bv_filter_rects(ctx, V.nrect, V.tiles, V.npairs, false, true, (uint32_t)std::min<size_t>(cap, 0xFFFFFFF0u)));
             ++launches;
             if (sink) ++sink->filter_launches;
             RT_HIP(hipMemcpyAsync(ctx->h_counter.p, ctx->d_counter.p, 4, hipMemcpyDeviceToHost, st));
             RT_HIP(hipStreamSynchronize(st));
-            nsurv = ctx->h_counter.p[0];
-            if ((uint64_t)nsurv > npairs * 2) { set_error("bv_filter: survivor counter overflow"); return RATTLE_ERR_HIP; }
-            if (nsurv <= cap) break;
-            cap = (size_t)nsurv + nsurv / 8;
+            V.nsurv = ctx->h_counter.p[0];
+            if ((uint64_t)V.nsurv > V.npairs * 2) { set_error("bv_filter: survivor counter overflow"); return RATTLE_ERR_HIP; }
+            if (V.nsurv <= cap) return 0;
+            cap = (size_t)V.nsurv + V.nsurv / 8;
         }
-        lap(1);
-        if (nsurv == 0) return 0;
+    }
 
+    // Three count passes.  "seed" (1): survivors sorted by seed, the seed's k-mer set as a bit set in LDS, its candidates' lists
+    // streamed past it (pair_count.hip) -- pays where a seed has many surviving candidates (gene level: hundreds).
+    // "search" (2): one wavefront per pair, binary searches in the candidate's list (pair_score.hip) -- better for the short
+    // runs of the --iso level.  "index" (3): an inverted k-mer index over the seeds, every candidate's list streamed once
+    // (pair_index.hip) -- for long reads, where the bit-vector filter lets every pair through.  RATTLE_PAIR_COUNT=
+    // seed|search|index forces one of them (any other value: search); the automatic rule picks between the first two.
+    int choose_form(uint64_t nsurv, uint64_t ns) const {
+        static const char *force = getenv("RATTLE_PAIR_COUNT");
+        return count_mode ? count_mode
+               : force    ? (!strcmp(force, "seed") ? 1 : !strcmp(force, "index") ? 3 : 2)
+                          : nsurv >= 64ull * ns ? 1 : 2;
+    }
+
+    // pass 1: |common| of every surviving pair.  bases <= k * |LIS| <= k * |common| (similarity.cpp:52-85), so a pair
+    // with double(k * |common|) / min_len < t_s cannot pass cluster.cpp:23-27 whatever its chain looks like: exact
+    // rejection without the patience search.  In the low-threshold merge passes that is nearly every pair.  The test
+    // (same double expression) and the compaction of the pairs that pass run on the device (count_bound_kernel).
+    int count_pass(evaluation &V) {
+        hipStream_t st = ctx->stream;
+        const uint32_t nsurv = V.nsurv;
+        const size_t nstat = 2 + 3 * (size_t)V.nrect;
         RT_TRY(ctx->d_pi.reserve(nsurv));
         RT_TRY(ctx->d_pj.reserve(nsurv));
         RT_TRY(ctx->d_ps.reserve(nsurv));
         RT_TRY(ctx->d_res.reserve((size_t)nsurv * 4));
         RT_TRY(ctx->d_pi2.reserve(nsurv)); RT_TRY(ctx->d_pj2.reserve(nsurv)); RT_TRY(ctx->d_ps2.reserve(nsurv)); RT_TRY(ctx->d_slot2.reserve((size_t)nsurv * 2));
-        RT_TRY(ctx->d_bound_stats.reserve(2 + 3 * (size_t)nrect + 4)); RT_TRY(ctx->h_bound_stats.reserve(2 + 3 * (size_t)nrect + 4));
-        if (many) {
-            RT_TRY(ctx->d_seed_rect.reserve(ns));
-            RT_HIP(hipMemcpyAsync(ctx->d_seed_rect.p, seed_req.data(), ns * 4, hipMemcpyHostToDevice, st));
+        RT_TRY(ctx->d_bound_stats.reserve(nstat + 4)); RT_TRY(ctx->h_bound_stats.reserve(nstat + 4));
+        if (V.many) {
+            RT_TRY(ctx->d_seed_rect.reserve(V.ns));
+            RT_HIP(hipMemcpyAsync(ctx->d_seed_rect.p, seed_req.data(), V.ns * 4, hipMemcpyHostToDevice, st));
         }
-        RT_HIP(hipMemsetAsync(ctx->d_bound_stats.p, 0, (2 + 3 * (size_t)nrect + 4) * 8, st));
-        // Three count passes.  "seed": survivors sorted by seed, the seed's k-mer set as a bit set in LDS, its candidates' lists
-        // streamed past it (pair_count.hip) -- pays where a seed has many surviving candidates (gene level: hundreds).
-        // "search": one wavefront per pair, binary searches in the candidate's list (pair_score.hip) -- better for the short
-        // runs of the --iso level.  "index": an inverted k-mer index over the seeds, every candidate's list streamed once
-        // (pair_index.hip) -- for long reads, where the bit-vector filter lets every pair through.  RATTLE_PAIR_COUNT=
-        // seed|search|index forces one of them (any other value: search); the automatic rule picks between the first two.
-        static const char *force = getenv("RATTLE_PAIR_COUNT");
-        const int form = count_mode ? count_mode
-                         : force ? (!strcmp(force, "seed") ? 1 : !strcmp(force, "index") ? 3 : 2)
-                                 : (uint64_t)nsurv >= 64ull * ns ? 1 : 2;
-        const bool seed_major = form == 1, indexed = form == 3;
-        if (sink) sink->count_pass |= 1 << (form - 1);
-        ++n_form[form - 1];
-        if (seed_major) RT_TRY(sort_survivors_by_seed(ctx, nsurv, ns));
-        if (indexed) RT_TRY(group_survivors_by_cand(ctx, nsurv, nc));
+        RT_HIP(hipMemsetAsync(ctx->d_bound_stats.p, 0, (nstat + 4) * 8, st));
+        V.form = choose_form(nsurv, V.ns);
+        if (sink) sink->count_pass |= 1 << (V.form - 1);
+        ++n_form[V.form - 1];
+        if (V.form == 1) RT_TRY(sort_survivors_by_seed(ctx, nsurv, V.ns));
+        if (V.form == 3) RT_TRY(group_survivors_by_cand(ctx, nsurv, V.nc));
         hipLaunchKernelGGL(expand_pairs_kernel, dim3((nsurv + 255) / 256), dim3(256), 0, st, ctx->d_surv.p, nsurv,
                            ctx->d_seed.p, ctx->d_cand.p, ctx->d_pi.p, ctx->d_pj.p, ctx->d_ps.p);
-        // ---- pass 1: |common| of every surviving pair.  bases <= k * |LIS| <= k * |common| (similarity.cpp:52-85), so a pair
-        // with double(k * |common|) / min_len < t_s cannot pass cluster.cpp:23-27 whatever its chain looks like: exact
-        // rejection without the patience search.  In the low-threshold merge passes that is nearly every pair.  The test
-        // (same double expression) and the compaction of the pairs that pass run on the device.
-        if (seed_major) RT_TRY(launch_pair_count_seed(ctx, nsurv));
-        else if (indexed) RT_TRY(launch_pair_count_index(ctx, nsurv, h_seed.data(), (uint32_t)ns, (uint32_t)nc, many));
+        if (V.form == 1) RT_TRY(launch_pair_count_seed(ctx, nsurv));
+        else if (V.form == 3) RT_TRY(launch_pair_count_index(ctx, nsurv, h_seed.data(), (uint32_t)V.ns, (uint32_t)V.nc, V.many));
         else RT_TRY(launch_pair_count(ctx, nsurv));
-        const double t_s = P->t_s, t_v = P->t_v;
-        const uint32_t kk = (uint32_t)X.k;
         hipLaunchKernelGGL(count_bound_kernel, dim3((nsurv + 255) / 256), dim3(256), 0, st, ctx->d_surv.p, ctx->d_res.p, nsurv,
-                           ctx->d_pi.p, ctx->d_pj.p, ctx->d_ps.p, X.len.p, kk, t_s, many ? ctx->d_seed_rect.p : (const uint32_t *)nullptr,
+                           ctx->d_pi.p, ctx->d_pj.p, ctx->d_ps.p, ctx->idx.len.p, (uint32_t)ctx->idx.k, P->t_s,
+                           V.many ? ctx->d_seed_rect.p : (const uint32_t *)nullptr,
                            ctx->d_bound_stats.p, ctx->d_pi2.p, ctx->d_pj2.p, ctx->d_ps2.p, ctx->d_slot2.p);
         launches += 3;
-        RT_HIP(hipMemcpyAsync(ctx->h_bound_stats.p, ctx->d_bound_stats.p, (2 + 3 * (size_t)nrect) * 8, hipMemcpyDeviceToHost, st));
+        RT_HIP(hipMemcpyAsync(ctx->h_bound_stats.p, ctx->d_bound_stats.p, nstat * 8, hipMemcpyDeviceToHost, st));
         RT_HIP(hipStreamSynchronize(st));
-        lap(2);
-        const uint32_t n2 = (uint32_t)ctx->h_bound_stats.p[0];
-        if (sink) RT_TRY(take_pairs(reqs, rect_req, nsurv, n2));      // before pass 2 overwrites d_res
-        ctx->stats[K_SCORE].bytes += ctx->h_bound_stats.p[1];
-        for (uint32_t j = 0; j < nrect; ++j) {
-            uint64_t *cn = reqs[rect_req[j]]->counters;
-            cn[1] += ctx->h_bound_stats.p[2 + 3 * (size_t)j]; cn[2] += ctx->h_bound_stats.p[3 + 3 * (size_t)j];
-            cn[5] += ctx->h_bound_stats.p[4 + 3 * (size_t)j];                  // full comparisons (cluster.cpp:20 / :44 calls that ran)
-        }
-        lap(3);
-        if (n2 == 0) return 0;
-        // ---- pass 2: the reference's full comparison for the pairs that can still be accepted
-        RT_TRY(ctx->d_res.reserve((size_t)n2 * 4));
-        RT_TRY(ctx->d_var.reserve(n2));
-        ctx->d_pi.swap(ctx->d_pi2); ctx->d_pj.swap(ctx->d_pj2); ctx->d_ps.swap(ctx->d_ps2);       // the launchers read d_pi / d_pj / d_ps
-        struct unswap { rattle_ctx *c; ~unswap() { c->d_pi.swap(c->d_pi2); c->d_pj.swap(c->d_pj2); c->d_ps.swap(c->d_ps2); } } back{ctx};
-        RT_TRY(launch_pair_score(ctx, n2));
-        ++launches;
-        if (best) return reduce_best(n2, nrect);
-        // verdicts on the device: d_surv (free since the count pass compacted it into d_slot2) takes the accepted pairs, the tail
-        // of the statistics buffer the three counters, d_pi2 (= the swapped-out d_pi: n2 <= nsurv words) the oversize list
-        unsigned long long *vout = ctx->d_bound_stats.p + 2 + 3 * (size_t)nrect;
-        uint32_t *d_hits = ctx->d_surv.p, *d_big = ctx->d_pi2.p;
-        const int use_hc = P->use_hc ? 1 : 0;
-        // the cluster report: the evidence of the accepted pairs (at most n2 of them over both verdict launches) beside them
-        const bool report = ctx->cluster_report;
-        uint4 *d_ev = nullptr;
-        if (report) { RT_TRY(ctx->d_hit_ev.reserve(n2)); d_ev = (uint4 *)ctx->d_hit_ev.p; }
-        if (report)
-            hipLaunchKernelGGL(verdict_report_kernel, dim3((n2 + 255) / 256), dim3(256), 0, st, ctx->d_res.p, ctx->d_var.p, n2, (const uint32_t *)nullptr,
-                               ctx->d_pi.p, ctx->d_pj.p, ctx->d_slot2.p, X.len.p, use_hc, t_s, t_v, vout, d_hits, d_big, d_ev);
-        else
-            hipLaunchKernelGGL(verdict_kernel, dim3((n2 + 255) / 256), dim3(256), 0, st, ctx->d_res.p, ctx->d_var.p, n2, (const uint32_t *)nullptr,
-                               ctx->d_pi.p, ctx->d_pj.p, ctx->d_slot2.p, X.len.p, use_hc, t_s, t_v, vout, d_hits, d_big);
-        ++launches;
-        unsigned long long *hv = ctx->h_bound_stats.p + 2 + 3 * (size_t)nrect;
-        // the first accepted pairs travel with the counters (one synchronisation per evaluation instead of two: the --iso level
-        // runs ~1000 evaluations of ~1000 accepted pairs each)
-        const uint32_t spec = std::min<uint32_t>(n2, 8192u);
-        RT_TRY(ctx->h_surv.reserve((size_t)spec * 2 + 2));
-        RT_HIP(hipMemcpyAsync(hv, vout, 24, hipMemcpyDeviceToHost, st));
-        RT_HIP(hipMemcpyAsync(ctx->h_surv.p, d_hits, (size_t)spec * 8, hipMemcpyDeviceToHost, st));
-        if (report) {
-            RT_TRY(ctx->h_hit_ev.reserve(spec));
-            RT_HIP(hipMemcpyAsync(ctx->h_hit_ev.p, d_ev, (size_t)spec * sizeof(hit_evidence), hipMemcpyDeviceToHost, st));
-        }
-        RT_HIP(hipStreamSynchronize(st));
-        const bool nbig_seen = hv[1] != 0;
-        if (hv[1]) {
-            // pairs whose match list did not fit LDS: rerun through the global-scratch variant, then judge them
-            const uint32_t nbig = (uint32_t)hv[1], big_m = (uint32_t)hv[2];
-            std::vector<uint32_t> big(nbig);
-            RT_HIP(hipMemcpyAsync(big.data(), d_big, (size_t)nbig * 4, hipMemcpyDeviceToHost, st));
-            RT_HIP(hipStreamSynchronize(st));
-            RT_TRY(launch_pair_score_oversize(ctx, big, big_m));
-            ++launches;
-            if (sink) sink->oversize += nbig;
-            RT_HIP(hipMemsetAsync(vout + 1, 0, 16, st));
-            if (report)
-                hipLaunchKernelGGL(verdict_report_kernel, dim3((nbig + 255) / 256), dim3(256), 0, st, ctx->d_res.p, ctx->d_var.p, nbig, (const uint32_t *)d_big,
-                                   ctx->d_pi.p, ctx->d_pj.p, ctx->d_slot2.p, X.len.p, use_hc, t_s, t_v, vout, d_hits, d_big, d_ev);
-            else
-                hipLaunchKernelGGL(verdict_kernel, dim3((nbig + 255) / 256), dim3(256), 0, st, ctx->d_res.p, ctx->d_var.p, nbig, (const uint32_t *)d_big,
-                                   ctx->d_pi.p, ctx->d_pj.p, ctx->d_slot2.p, X.len.p, use_hc, t_s, t_v, vout, d_hits, d_big);
-            ++launches;
-            RT_HIP(hipMemcpyAsync(hv, vout, 24, hipMemcpyDeviceToHost, st));
-            RT_HIP(hipStreamSynchronize(st));
-            if (hv[1]) { set_error("pair_score: a pair is still oversize after the oversize pass"); return RATTLE_ERR_HIP; }
-        }
-        const uint32_t nhit = (uint32_t)hv[0];
-        if (hv[0] > n2) { set_error("verdicts: more accepted pairs than full comparisons"); return RATTLE_ERR_HIP; }
-        if (nhit > spec || nbig_seen) {                  // more than came along (or the oversize pass appended some): fetch them all
-            RT_TRY(ctx->h_surv.reserve((size_t)nhit * 2 + 2));
-            if (nhit) RT_HIP(hipMemcpyAsync(ctx->h_surv.p, d_hits, (size_t)nhit * 8, hipMemcpyDeviceToHost, st));
-            if (report && nhit) {
-                RT_TRY(ctx->h_hit_ev.reserve(nhit));
-                RT_HIP(hipMemcpyAsync(ctx->h_hit_ev.p, d_ev, (size_t)nhit * sizeof(hit_evidence), hipMemcpyDeviceToHost, st));
-            }
-            RT_HIP(hipStreamSynchronize(st));
-        }
-        // accepted pairs back to their rectangle
-        for (uint32_t q = 0; q < nhit; ++q) {
-            const uint32_t a = ctx->h_surv.p[2 * (size_t)q], c = ctx->h_surv.p[2 * (size_t)q + 1];
-            const uint32_t rj = many ? seed_req[a >> 1] : 0;
-            const bvf_rect &J = rects[rj];
-            reqs[rect_req[rj]]->hits.push_back(hit_t{(a >> 1) - J.s_base, c - J.c_base, (uint8_t)(a & 1u)});
-            if (report) reqs[rect_req[rj]]->ev.push_back(ctx->h_hit_ev.p[q]);
-        }
-        for (uint32_t j = 0; j < nrect; ++j) if (reqs[rect_req[j]]->triangular) sort_hits(*reqs[rect_req[j]]);      // level 2 takes them in any order
-        lap(4);
+        V.n2 = (uint32_t)ctx->h_bound_stats.p[0];
         return 0;
     }
 
-    // The other ending of an evaluation (`assign`): no hit list; every accepted pair goes into the per-read reduction.  Pass 1 also lists
-    // the pairs whose match list did not fit LDS, as the verdict kernel does; the oversize pass fills their res / var in place and pass
-    // 1 takes them in, before passes 2 and 3 run over all n2 pairs.  The host reads the three counters (and the oversize slots).
-    int reduce_best(uint32_t n2, uint32_t nrect) {
-        hipStream_t st = ctx->stream;
-        if (nrect != 1 || rects[0].s_base != 0 || rects[0].c_base != 0) { set_error("assign: one rectangular request per evaluation"); return RATTLE_ERR_STATE; }
-        unsigned long long *vout = ctx->d_bound_stats.p + 2 + 3 * (size_t)nrect, *hv = ctx->h_bound_stats.p + 2 + 3 * (size_t)nrect;
-        uint32_t *d_big = ctx->d_pi2.p;                   // (= the swapped-out d_pi: n2 <= nsurv words)
-        const int use_hc = P->use_hc ? 1 : 0;
-        RT_TRY(launch_assign_max(ctx, n2, nullptr, use_hc, P->t_s, P->t_v, vout, d_big, *best));
-        ++launches;
-        RT_HIP(hipMemcpyAsync(hv, vout, 24, hipMemcpyDeviceToHost, st));
-        RT_HIP(hipStreamSynchronize(st));
-        if (hv[1]) {
-            const uint32_t nbig = (uint32_t)hv[1], big_m = (uint32_t)hv[2];
-            if (hv[1] > n2) { set_error("assign: more oversize pairs than full comparisons"); return RATTLE_ERR_HIP; }
-            std::vector<uint32_t> big(nbig);
-            RT_HIP(hipMemcpyAsync(big.data(), d_big, (size_t)nbig * 4, hipMemcpyDeviceToHost, st));
-            RT_HIP(hipStreamSynchronize(st));
-            RT_TRY(launch_pair_score_oversize(ctx, big, big_m));
-            RT_HIP(hipMemsetAsync(vout + 1, 0, 16, st));
-            RT_TRY(launch_assign_max(ctx, nbig, d_big, use_hc, P->t_s, P->t_v, vout, d_big, *best));
-            launches += 2;
-            RT_HIP(hipMemcpyAsync(hv, vout, 24, hipMemcpyDeviceToHost, st));
-            RT_HIP(hipStreamSynchronize(st));
-            if (hv[1]) { set_error("pair_score: a pair is still oversize after the oversize pass"); return RATTLE_ERR_HIP; }
+    // the count bound's statistics to the jobs' counters
+    int credit(evaluation &V) {
+        if (sink) RT_TRY(take_pairs(V.reqs, V.rect_req, V.nsurv, V.n2));      // before pass 2 overwrites d_res
+        ctx->stats[K_SCORE].bytes += ctx->h_bound_stats.p[1];
+        for (uint32_t j = 0; j < V.nrect; ++j) {
+            uint64_t *cn = V.reqs[V.rect_req[j]]->counters;
+            cn[1] += ctx->h_bound_stats.p[2 + 3 * (size_t)j]; cn[2] += ctx->h_bound_stats.p[3 + 3 * (size_t)j];
+            cn[5] += ctx->h_bound_stats.p[4 + 3 * (size_t)j];                  // full comparisons (cluster.cpp:20 / :44 calls that ran)
         }
-        RT_TRY(launch_assign_pick(ctx, n2, use_hc, P->t_s, P->t_v, best_base, *best));
+        return 0;
+    }
+
+    // pass 2: the reference's full comparison for the pairs that can still be accepted
+    int full_pass(evaluation &V) {
+        RT_TRY(ctx->d_res.reserve((size_t)V.n2 * 4));
+        RT_TRY(ctx->d_var.reserve(V.n2));
+        V.swap_pairs();
+        V.vout = ctx->d_bound_stats.p + 2 + 3 * (size_t)V.nrect; V.hv = ctx->h_bound_stats.p + 2 + 3 * (size_t)V.nrect;
+        V.d_hits = ctx->d_surv.p; V.d_big = ctx->d_pi2.p;
+        RT_TRY(launch_pair_score(ctx, V.n2));
+        ++launches;
+        return 0;
+    }
+
+    // cluster.cpp:23-36 / :47-61 for all n kept pairs (remap == nullptr) or the n listed in remap: the one verdict launch
+    int judge(evaluation &V, uint32_t n, const uint32_t *remap) {
+        const dim3 grid((n + 255) / 256), block(256);
+        const int use_hc = P->use_hc ? 1 : 0;
+        if (V.report)
+            hipLaunchKernelGGL(verdict_report_kernel, grid, block, 0, ctx->stream, ctx->d_res.p, ctx->d_var.p, n, remap, ctx->d_pi.p, ctx->d_pj.p,
+                               ctx->d_slot2.p, ctx->idx.len.p, use_hc, P->t_s, P->t_v, V.vout, V.d_hits, V.d_big, V.d_ev);
+        else
+            hipLaunchKernelGGL(verdict_kernel, grid, block, 0, ctx->stream, ctx->d_res.p, ctx->d_var.p, n, remap, ctx->d_pi.p, ctx->d_pj.p,
+                               ctx->d_slot2.p, ctx->idx.len.p, use_hc, P->t_s, P->t_v, V.vout, V.d_hits, V.d_big);
+        ++launches;
+        return 0;
+    }
+
+    // Both endings' first judging launch listed the pairs whose match list did not fit LDS (hv[1] of them in d_big, the longest list
+    // hv[2]): rerun them through the global-scratch variant, which fills their res / var in place, and judge the list again.
+    template <class Judge>
+    int oversize_pass(evaluation &V, Judge again) {
+        hipStream_t st = ctx->stream;
+        const uint32_t nbig = (uint32_t)V.hv[1], big_m = (uint32_t)V.hv[2];
+        if (V.hv[1] > V.n2) { set_error("evaluation: more oversize pairs than full comparisons"); return RATTLE_ERR_HIP; }
+        std::vector<uint32_t> big(nbig);
+        RT_HIP(hipMemcpyAsync(big.data(), V.d_big, (size_t)nbig * 4, hipMemcpyDeviceToHost, st));
+        RT_HIP(hipStreamSynchronize(st));
+        RT_TRY(launch_pair_score_oversize(ctx, big, big_m));
+        ++launches;
+        if (sink) sink->oversize += nbig;
+        RT_HIP(hipMemsetAsync(V.vout + 1, 0, 16, st));
+        RT_TRY(again(nbig, (const uint32_t *)V.d_big));
+        RT_HIP(hipMemcpyAsync(V.hv, V.vout, 24, hipMemcpyDeviceToHost, st));
+        RT_HIP(hipStreamSynchronize(st));
+        if (V.hv[1]) { set_error("pair_score: a pair is still oversize after the oversize pass"); return RATTLE_ERR_HIP; }
+        return 0;
+    }
+
+    // the first n accepted pairs, and their evidence, to the host; the three counters with them if asked
+    int fetch_hits(evaluation &V, uint32_t n, bool counters) {
+        hipStream_t st = ctx->stream;
+        RT_TRY(ctx->h_surv.reserve((size_t)n * 2 + 2));
+        if (counters) RT_HIP(hipMemcpyAsync(V.hv, V.vout, 24, hipMemcpyDeviceToHost, st));
+        if (n) RT_HIP(hipMemcpyAsync(ctx->h_surv.p, V.d_hits, (size_t)n * 8, hipMemcpyDeviceToHost, st));
+        if (V.report && n) {
+            RT_TRY(ctx->h_hit_ev.reserve(n));
+            RT_HIP(hipMemcpyAsync(ctx->h_hit_ev.p, V.d_ev, (size_t)n * sizeof(hit_evidence), hipMemcpyDeviceToHost, st));
+        }
+        RT_HIP(hipStreamSynchronize(st));
+        return 0;
+    }
+
+    // accepted pairs back to their rectangle
+    void deal_hits(evaluation &V, uint32_t nhit) {
+        for (uint32_t q = 0; q < nhit; ++q) {
+            const uint32_t a = ctx->h_surv.p[2 * (size_t)q], c = ctx->h_surv.p[2 * (size_t)q + 1];
+            const uint32_t rj = V.many ? seed_req[a >> 1] : 0;
+            const bvf_rect &J = rects[rj];
+            request &Q = *V.reqs[V.rect_req[rj]];
+            Q.hits.push_back(hit_t{(a >> 1) - J.s_base, c - J.c_base, (uint8_t)(a & 1u)});
+            if (V.report) Q.ev.push_back(ctx->h_hit_ev.p[q]);
+        }
+        for (uint32_t j = 0; j < V.nrect; ++j) if (V.reqs[V.rect_req[j]]->triangular) sort_hits(*V.reqs[V.rect_req[j]]);      // level 2 takes them in any order
+    }
+
+    // The ending of a clustering's evaluation: the verdicts on the device, the accepted pairs as each request's hit list.
+    int verdicts(evaluation &V) {
+        V.report = ctx->cluster_report;
+        if (V.report) { RT_TRY(ctx->d_hit_ev.reserve(V.n2)); V.d_ev = (uint4 *)ctx->d_hit_ev.p; }
+        RT_TRY(judge(V, V.n2, nullptr));
+        // the first accepted pairs travel with the counters (one synchronisation per evaluation instead of two: the --iso level
+        // runs ~1000 evaluations of ~1000 accepted pairs each)
+        const uint32_t spec = std::min<uint32_t>(V.n2, 8192u);
+        RT_TRY(fetch_hits(V, spec, true));
+        const bool nbig_seen = V.hv[1] != 0;
+        if (nbig_seen) RT_TRY(oversize_pass(V, [&](uint32_t n, const uint32_t *remap) { return judge(V, n, remap); }));
+        const uint32_t nhit = (uint32_t)V.hv[0];
+        if (V.hv[0] > V.n2) { set_error("verdicts: more accepted pairs than full comparisons"); return RATTLE_ERR_HIP; }
+        // more than came along (or the oversize pass appended some): fetch them all
+        if (nhit > spec || nbig_seen) RT_TRY(fetch_hits(V, nhit, false));
+        deal_hits(V, nhit);
+        return 0;
+    }
+
+    // The other ending (`assign`): no hit list; every accepted pair goes into the per-read reduction.  Pass 1 also lists the pairs whose
+    // match list did not fit LDS, as the verdict kernel does, and takes them in again after the oversize pass, before passes 2 and 3
+    // run over all n2 pairs.  The host reads the three counters (and the oversize slots).
+    int reduce_best(evaluation &V) {
+        if (V.nrect != 1 || rects[0].s_base != 0 || rects[0].c_base != 0) { set_error("assign: one rectangular request per evaluation"); return RATTLE_ERR_STATE; }
+        const int use_hc = P->use_hc ? 1 : 0;
+        auto pass1 = [&](uint32_t n, const uint32_t *remap) {
+            RT_TRY(launch_assign_max(ctx, n, remap, use_hc, P->t_s, P->t_v, V.vout, V.d_big, *best));
+            ++launches;
+            return 0;
+        };
+        RT_TRY(pass1(V.n2, nullptr));
+        RT_HIP(hipMemcpyAsync(V.hv, V.vout, 24, hipMemcpyDeviceToHost, ctx->stream));
+        RT_HIP(hipStreamSynchronize(ctx->stream));
+        if (V.hv[1]) RT_TRY(oversize_pass(V, pass1));
+        RT_TRY(launch_assign_pick(ctx, V.n2, use_hc, P->t_s, P->t_v, best_base, *best));
         launches += 2;
-        lap(4);
         return 0;
     }
 
@@ -766,6 +830,87 @@ struct job {
         next_merge(t);
     }
 
+    // ---- the four phases of a greedy round (step).  The two that ask for an evaluation fill rq and say so (true).
+    // the round's seeds; level 1: seeds x seeds
+    bool round_setup() {
+        if (remaining.empty()) { end_pass(); return false; }
+        counters[3]++;
+        // seeds x candidates x strands below the evaluator's per-launch bounds even if every pair survives
+        B = max_seeds_per_launch(std::min<size_t>(batch_now, remaining.size()), remaining.size(), X->both ? 2u : 1u, thr);
+        seeds_local.resize(B);
+        for (uint32_t s = 0; s < B; ++s) seeds_local[s] = items[remaining[s]];
+        taken.assign(B, 0);
+        if (B == 1) { phase = FOUNDERS; return false; }
+        rq.seeds.resize(B);
+        for (uint32_t s = 0; s < B; ++s) rq.seeds[s] = rid(seeds_local[s]);
+        rq.cands.clear();
+        rq.triangular = true; rq.thr = thr;
+        phase = WAIT_L1;
+        return true;
+    }
+
+    // the seeds no earlier seed absorbed; level 2: founders x rest
+    bool pick_founders() {
+        founders.clear();
+        for (uint32_t s = 0; s < B; ++s) if (!taken[s]) founders.push_back(s);
+        uint32_t want = 8;
+        while (want < 2 * founders.size() && want < max_batch()) want *= 2;
+        batch_now = std::min(want, max_batch());
+        const uint32_t nrest = (uint32_t)remaining.size() - B;
+        next.clear();
+        if (nrest == 0) { remaining.swap(next); phase = ROUND; return false; }
+        rq.seeds.resize(founders.size());
+        for (size_t f = 0; f < founders.size(); ++f) rq.seeds[f] = rid(seeds_local[founders[f]]);
+        rq.cands.resize(nrest);
+        for (uint32_t c = 0; c < nrest; ++c) rq.cands[c] = rid(items[remaining[B + c]]);
+        rq.triangular = false; rq.thr = thr;
+        phase = WAIT_L2;
+        return true;
+    }
+
+    // hits grouped by seed; forward verdict wins over reverse (cluster.cpp:19-40 before :43)
+    void resolve_level1() {
+        const std::vector<hit_t> &hits = rq.hits;
+        size_t h = 0;
+        for (uint32_t s = 0; s < B; ++s) {
+            while (h < hits.size() && hits[h].seed < s) ++h;
+            if (taken[s]) continue;
+            for (size_t q = h; q < hits.size() && hits[q].seed == s; ++q) {
+                uint32_t c = hits[q].cand;
+                if (taken[c]) continue;
+                taken[c] = 1;
+                owner[remaining[c]] = remaining[s];
+                rev[remaining[c]] = hits[q].rev;
+                if (report) why[remaining[c]] = rq.ev[q];
+            }
+        }
+        phase = FOUNDERS;
+    }
+
+    // founders in order, the first accepting founder wins, forward before reverse: the smallest (founder, strand)
+    // key per candidate, whatever order the hits arrive in
+    void resolve_level2() {
+        const uint32_t nrest = (uint32_t)remaining.size() - B;
+        best.assign(nrest, 0xFFFFFFFFu);
+        if (!report) for (const hit_t &q : rq.hits) best[q.cand] = std::min(best[q.cand], (q.seed << 1) | q.rev);
+        else {                                            // ... and which hit that was (a key occurs once per candidate)
+            best_at.resize(nrest);
+            for (uint32_t h = 0; h < rq.hits.size(); ++h) {
+                const hit_t &q = rq.hits[h];
+                const uint32_t key = (q.seed << 1) | q.rev;
+                if (key < best[q.cand]) { best[q.cand] = key; best_at[q.cand] = h; }
+            }
+        }
+        for (uint32_t c = 0; c < nrest; ++c) {
+            if (best[c] == 0xFFFFFFFFu) { next.push_back(remaining[B + c]); continue; }
+            owner[remaining[B + c]] = remaining[founders[best[c] >> 1]];
+            rev[remaining[B + c]] = (uint8_t)(best[c] & 1u);
+            if (report) why[remaining[B + c]] = rq.ev[best_at[c]];
+        }
+        remaining.swap(next);
+        phase = ROUND;
+    }
+
     // advance until the job needs a rectangle evaluated (true, *out) or is finished (false)
     bool step(request **out) {
         while (stage != DONE) {
@@ -773,100 +918,14 @@ struct job {
                            ~lapse() { acc += std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t0).count(); } };
             const bool ending = phase == ROUND && remaining.empty();
             lapse L{t_phase[ending ? 4 : (int)phase]};
+            bool ask = false;
             switch (phase) {
-            case ROUND: {
-                if (remaining.empty()) { end_pass(); break; }
-                counters[3]++;
-                B = (uint32_t)std::min<size_t>(batch_now, remaining.size());
-                {
-                    // seeds x candidates x strands below the evaluator's per-launch bounds even if every pair survives
-                    const uint64_t per_seed = (uint64_t)remaining.size() * (X->both ? 2u : 1u);
-                    const uint64_t cap = thr == 0.0 ? (64ull << 20) : (1ull << 31);
-                    B = (uint32_t)std::max<uint64_t>(1, std::min<uint64_t>(B, cap / std::max<uint64_t>(per_seed, 1)));
-                }
-                seeds_local.resize(B);
-                for (uint32_t s = 0; s < B; ++s) seeds_local[s] = items[remaining[s]];
-                taken.assign(B, 0);
-                if (B > 1) {                                      // ---- level 1: seeds x seeds
-                    rq.seeds.resize(B);
-                    for (uint32_t s = 0; s < B; ++s) rq.seeds[s] = rid(seeds_local[s]);
-                    rq.cands.clear();
-                    rq.triangular = true; rq.thr = thr;
-                    phase = WAIT_L1;
-                    *out = &rq;
-                    return true;
-                }
-                phase = FOUNDERS;
-                break;
+            case ROUND: ask = round_setup(); break;
+            case WAIT_L1: resolve_level1(); break;
+            case FOUNDERS: ask = pick_founders(); break;
+            case WAIT_L2: resolve_level2(); break;
             }
-            case WAIT_L1: {
-                // hits grouped by seed; forward verdict wins over reverse (cluster.cpp:19-40 before :43)
-                const std::vector<hit_t> &hits = rq.hits;
-                size_t h = 0;
-                for (uint32_t s = 0; s < B; ++s) {
-                    while (h < hits.size() && hits[h].seed < s) ++h;
-                    if (taken[s]) continue;
-                    for (size_t q = h; q < hits.size() && hits[q].seed == s; ++q) {
-                        uint32_t c = hits[q].cand;
-                        if (taken[c]) continue;
-                        taken[c] = 1;
-                        owner[remaining[c]] = remaining[s];
-                        rev[remaining[c]] = hits[q].rev;
-                        if (report) why[remaining[c]] = rq.ev[q];
-                    }
-                }
-                phase = FOUNDERS;
-                break;
-            }
-            case FOUNDERS: {
-                founders.clear();
-                for (uint32_t s = 0; s < B; ++s) if (!taken[s]) founders.push_back(s);
-                {
-                    uint32_t want = 8;
-                    while (want < 2 * founders.size() && want < max_batch()) want *= 2;
-                    batch_now = std::min(want, max_batch());
-                }
-                const uint32_t nrest = (uint32_t)remaining.size() - B;
-                next.clear();
-                if (nrest > 0) {                                  // ---- level 2: founders x rest
-                    rq.seeds.resize(founders.size());
-                    for (size_t f = 0; f < founders.size(); ++f) rq.seeds[f] = rid(seeds_local[founders[f]]);
-                    rq.cands.resize(nrest);
-                    for (uint32_t c = 0; c < nrest; ++c) rq.cands[c] = rid(items[remaining[B + c]]);
-                    rq.triangular = false; rq.thr = thr;
-                    phase = WAIT_L2;
-                    *out = &rq;
-                    return true;
-                }
-                remaining.swap(next);
-                phase = ROUND;
-                break;
-            }
-            case WAIT_L2: {
-                const uint32_t nrest = (uint32_t)remaining.size() - B;
-                // founders in order, the first accepting founder wins, forward before reverse: the smallest (founder, strand)
-                // key per candidate, whatever order the hits arrive in
-                best.assign(nrest, 0xFFFFFFFFu);
-                if (!report) for (const hit_t &q : rq.hits) best[q.cand] = std::min(best[q.cand], (q.seed << 1) | q.rev);
-                else {                                            // ... and which hit that was (a key occurs once per candidate)
-                    best_at.resize(nrest);
-                    for (uint32_t h = 0; h < rq.hits.size(); ++h) {
-                        const hit_t &q = rq.hits[h];
-                        const uint32_t key = (q.seed << 1) | q.rev;
-                        if (key < best[q.cand]) { best[q.cand] = key; best_at[q.cand] = h; }
-                    }
-                }
-                for (uint32_t c = 0; c < nrest; ++c) {
-                    if (best[c] == 0xFFFFFFFFu) { next.push_back(remaining[B + c]); continue; }
-                    owner[remaining[B + c]] = remaining[founders[best[c] >> 1]];
-                    rev[remaining[B + c]] = (uint8_t)(best[c] & 1u);
-                    if (report) why[remaining[B + c]] = rq.ev[best_at[c]];
-                }
-                remaining.swap(next);
-                phase = ROUND;
-                break;
-            }
-            }
+            if (ask) { *out = &rq; return true; }
         }
         return false;
     }
@@ -1040,10 +1099,8 @@ int assign_driver(rattle_ctx *ctx, const rattle_assign_params *AP, const uint32_
     request rq;
     rq.cands.assign(rids, rids + nr);
     rq.thr = AP->bv_threshold; rq.counters = counters;
-    // seeds x reads x strands below the evaluator's per-launch bounds even if every pair survives (as job::step sizes its rounds)
-    const uint64_t per_seed = (uint64_t)nr * (X.both ? 2u : 1u);
-    const uint64_t cap = rq.thr == 0.0 ? (64ull << 20) : (1ull << 31);
-    const uint32_t step = (uint32_t)std::max<uint64_t>(1, std::min<uint64_t>(AP->target_batch ? AP->target_batch : 512u, cap / per_seed));
+    // seeds x reads x strands below the evaluator's per-launch bounds even if every pair survives
+    const uint32_t step = max_seeds_per_launch(AP->target_batch ? AP->target_batch : 512u, nr, X.both ? 2u : 1u, rq.thr);
     std::vector<request *> reqs{&rq};
     for (uint32_t t0 = 0; t0 < nt; t0 += step) {
         rq.seeds.assign(tids + t0, tids + std::min<uint64_t>(nt, (uint64_t)t0 + step));

@@ -447,6 +447,8 @@ int launch_bv_filter(rattle_ctx *ctx, uint32_t n_seeds, uint32_t n_cands, int fw
 int launch_bv_filter_rects(rattle_ctx *ctx, uint32_t n_rects, uint32_t n_tiles, uint64_t pairs, bool dense, bool list, uint32_t list_cap);
 // pair_score.hip : pairs in ctx->d_pi/d_pj/d_ps; results in ctx->d_res (4 ints per pair) + ctx->d_var.
 int launch_pair_score(rattle_ctx *ctx, uint32_t n_pairs);
+// the pairs `slots` (host) whose match list did not fit LDS, again, their lists in a global slab sized for max_matches
+int launch_pair_score_oversize(rattle_ctx *ctx, const std::vector<uint32_t> &slots, uint32_t max_matches);
 // pair_count.hip : the count pass, seed-major (survivors sorted by seed, the seed's k-mer set as an LDS bit set)
 int sort_survivors_by_seed(rattle_ctx *ctx, uint32_t n, uint64_t n_seeds);
 int launch_pair_count_seed(rattle_ctx *ctx, uint32_t n_pairs);

@@ -1,4 +1,4 @@
-"""One evaluation of the greedy clustering (cluster_driver.hip: evaluator::run_local) pair by pair against a plain reference, through
+"""One evaluation of the greedy clustering (cluster_driver.hip: the steps of evaluator::run_local) pair by pair against a plain reference, through
 the test hook rattle_hip_debug_evaluate: kernel A's survivor list over many rectangles (and its capacity retry), the survivor sort,
 both count passes for |common| (the seed-major LDS bit set of pair_count.hip and the per-pair search of pair_score.hip), the exact
 rejection of count_bound_kernel with its per-rectangle statistics, the full pass with its oversize relaunch, and the verdicts.
