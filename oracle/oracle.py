@@ -99,6 +99,52 @@ class Oracle(_Lib):
         raw = buf.raw
         return [raw[i * w:(i + 1) * w] for i in range(n)], cells.value
 
+    def poa_graph(self, seqs):
+        """The graph every alignment of poa_msa's loop is computed against.  A list with one entry per alignment k = 1 .. n-1 (the
+        graph after sequences 0 .. k-1): (indeg, off, dist) -- indeg[r] the in-degree of rank r (DP row r + 1), and
+        dist[off[r]:off[r + 1]] the distances rank(node) - rank(predecessor) in the node's in-edge order."""
+        n = len(seqs)
+        off = np.zeros(n + 1, np.uint64)
+        off[1:] = np.cumsum([len(s) for s in seqs], dtype=np.uint64)
+        cat = b"".join(seqs)
+        ao = _P(C.c_uint64)(); deg = _P(C.c_uint32)(); dst = _P(C.c_uint32)(); nn = C.c_uint64()
+        self.lib.orc_poa_graph.restype = C.c_uint64
+        ne = self.lib.orc_poa_graph(C.c_char_p(cat), _ptr(off, C.c_uint64), C.c_uint32(n), C.byref(ao), C.byref(deg), C.byref(dst), C.byref(nn))
+        try:
+            ao_a = np.array(ao[:max(n, 1)], np.int64)
+            deg_a = np.ctypeslib.as_array(deg, (nn.value,)).astype(np.int64) if nn.value else np.zeros(0, np.int64)
+            dst_a = np.ctypeslib.as_array(dst, (ne,)).astype(np.int64) if ne else np.zeros(0, np.int64)
+        finally:
+            for x in (ao, deg, dst):
+                self.lib.orc_free(x)
+        eoff = np.zeros(len(deg_a) + 1, np.int64)
+        eoff[1:] = np.cumsum(deg_a)
+        out = []
+        for k in range(1, n):
+            a, b = int(ao_a[k - 1]), int(ao_a[k])
+            out.append((deg_a[a:b], eoff[a:b + 1] - eoff[a], dst_a[eoff[a]:eoff[b]]))
+        return out
+
+    def poa_msa_blind(self, seqs, kind, value=0):
+        """poa_msa with a deliberately wrong row loop (orc_poa_msa_blind), for proving that a pack would notice one.  kind "from": a row's
+        in-edges from index `value` on are not seen; "at": in-edges exactly `value` rows back; "beyond": `value` or more rows back;
+        "start": a row without in-edge takes the row before it as predecessor.  Returns the rows."""
+        n = len(seqs)
+        off = np.zeros(n + 1, np.uint64)
+        off[1:] = np.cumsum([len(s) for s in seqs], dtype=np.uint64)
+        cat = b"".join(seqs)
+        self.lib.orc_poa_msa_blind.restype = C.c_int64
+        cap = 64 * (int(off[-1]) + 1024) + n * 1024
+        while True:
+            buf = C.create_string_buffer(cap)
+            w = self.lib.orc_poa_msa_blind(C.c_char_p(cat), _ptr(off, C.c_uint64), C.c_uint32(n), C.c_int({"from": 1, "at": 2, "beyond": 3, "start": 4}[kind]),
+                                           C.c_uint32(value), buf, C.c_uint64(cap))
+            if w >= 0:
+                break
+            cap *= 4
+        raw = buf.raw
+        return [raw[i * w:(i + 1) * w] for i in range(n)]
+
     def set_cv_order(self, order: bytes):
         assert len(order) == 6
         self.lib.orc_set_cv_order(C.c_char_p(order))

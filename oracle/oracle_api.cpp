@@ -194,6 +194,81 @@ void orc_post_msa(const char *rows, uint32_t n, uint32_t width, const char *qual
     out_off[n] = at;
 }
 
+// The graph every alignment of orc_poa_msa's loop is computed against (tests: which graph shape a pack really produces).  For
+// k = 1 .. n-1, the graph after sequences 0 .. k-1 were added, by rank (= DP row - 1): aln_off[k-1] .. aln_off[k] index that
+// graph's ranks in indeg[]; dist[] holds, rank after rank and in each node's in-edge order, rank(node) - rank(predecessor).
+// aln_off [n], indeg and dist are malloc'd (orc_free); returns the length of dist, *n_nodes that of indeg.
+uint64_t orc_poa_graph(const char *seqs, const uint64_t *off, uint32_t n, uint64_t **aln_off, uint32_t **indeg, uint32_t **dist, uint64_t *n_nodes) {
+    poa_graph_t G;
+    poa_engine_t eng;
+    eng.simd = poa_simd_default();
+    std::vector<uint64_t> ao(std::max<uint32_t>(n, 1), 0);
+    std::vector<uint32_t> deg, dst;
+    for (uint32_t k = 0; k < n; ++k) {
+        const std::string s(seqs + off[k], seqs + off[k + 1]);
+        if (k > 0) {
+            std::vector<uint32_t> rank(G.nodes.size());
+            for (size_t r = 0; r < G.rank_to_node.size(); ++r) rank[G.rank_to_node[r]] = (uint32_t)r;
+            for (size_t r = 0; r < G.rank_to_node.size(); ++r) {
+                const poa_node_t &nd = G.nodes[G.rank_to_node[r]];
+                deg.push_back((uint32_t)nd.in_edges.size());
+                for (uint32_t ei : nd.in_edges) dst.push_back((uint32_t)r - rank[G.edges[ei].begin]);
+            }
+            ao[k] = deg.size();
+        }
+        poa_alignment_t a = eng.align(s, G);
+        G.add_alignment(a, s);
+    }
+    auto dump = [](const auto &v) {
+        typedef typename std::decay<decltype(v)>::type::value_type T;
+        T *p = (T *)malloc((v.size() + 1) * sizeof(T));
+        memcpy(p, v.data(), v.size() * sizeof(T));
+        return p;
+    };
+    *aln_off = dump(ao); *indeg = dump(deg); *dist = dump(dst);
+    *n_nodes = deg.size();
+    return dst.size();
+}
+
+// poa_msa's loop with a deliberately WRONG row loop (tests: a constructed pack must notice).  Every alignment is computed against a
+// copy of the graph in which the row loop's view of the in-edges is spoilt; the alignment is then added to the true graph.
+// kind 1: a row's in-edges from the value-th on (0-based, in in-edge order) are not seen; 2: in-edges exactly `value` rows back are not
+// seen; 3: in-edges `value` or more rows back are not seen; 4: a row without in-edge (not the first) takes the row before it as predecessor.
+int64_t orc_poa_msa_blind(const char *seqs, const uint64_t *off, uint32_t n, int kind, uint32_t value, char *msa_out, uint64_t cap) {
+    poa_graph_t G;
+    poa_engine_t eng;
+    eng.simd = poa_simd_default();
+    for (uint32_t k = 0; k < n; ++k) {
+        const std::string s(seqs + off[k], seqs + off[k + 1]);
+        poa_graph_t M = G;
+        std::vector<uint32_t> rank(M.nodes.size());
+        for (size_t r = 0; r < M.rank_to_node.size(); ++r) rank[M.rank_to_node[r]] = (uint32_t)r;
+        for (size_t v = 0; v < M.nodes.size(); ++v) {
+            std::vector<uint32_t> &in = M.nodes[v].in_edges, kept;
+            if (kind == 4) {
+                if (in.empty() && rank[v] > 0) {
+                    M.edges.push_back(poa_edge_t{M.rank_to_node[rank[v] - 1], (uint32_t)v, {}});
+                    in.push_back((uint32_t)M.edges.size() - 1);
+                }
+                continue;
+            }
+            for (size_t i = 0; i < in.size(); ++i) {
+                const uint32_t d = rank[v] - rank[M.edges[in[i]].begin];
+                if ((kind == 1 && i >= value) || (kind == 2 && d == value) || (kind == 3 && d >= value)) continue;
+                kept.push_back(in[i]);
+            }
+            in = kept;
+        }
+        poa_alignment_t a = eng.align(s, M);
+        G.add_alignment(a, s);
+    }
+    std::vector<std::string> msa = G.msa();
+    size_t W = msa.empty() ? 0 : msa[0].size();
+    if (W * n > cap) return -1;
+    for (uint32_t i = 0; i < n; ++i) memcpy(msa_out + (size_t)i * W, msa[i].data(), W);
+    return (int64_t)W;
+}
+
 void orc_free(void *p) { free(p); }
 
 // AVX2 int16 row fill of the POA matrices (orc_poa.hpp); returns whether this CPU can run it.

@@ -3,6 +3,7 @@ byte-identical (same width, same column for every base)."""
 import numpy as np
 import pytest
 
+import constructed_graphs
 from rattle_amd import synth
 
 pytestmark = pytest.mark.gpu
@@ -149,32 +150,20 @@ def test_fallback_paths_match_oracle(gpu_ctx, oracle, monkeypatch, env):
                                  {"RATTLE_POA_MODE": "mt2"}, {"RATTLE_POA_MODE": "mt1"}, {"RATTLE_POA_MODE": "mt4", "RATTLE_POA_MT_SLOTS": "11"}])
 def test_predecessors_hundreds_of_rows_back_and_many_in_edges(gpu_ctx, oracle, monkeypatch, env):
     """The row loop reads a COMPACT plan record: the distances to a row's first eight predecessor rows in a byte each, saturated
-    at 255, the in-degree capped at 255 (poa.hip, round 4).  Reads that skip 300-600 bases of the others (an exon left out) give
-    nodes whose predecessor lies far more than 255 rows back; reads that resume at many different places give one node more than
-    eight in-edges (the edge-list walk); both next to ordinary rows, in the barrier form and the team forms of the loop."""
+    at 255, the in-degree capped at 255 (poa.hip, round 4).  A noisy pack (constructed_graphs.old_far_pack), sorted and reversed: reads
+    that leave out 300-620 bases of the others and reads that resume at many different places.  What the oracle's graphs of it show
+    (tests/test_constructed_graphs.py::test_reach_of_the_old_far_pack): the local alignment does not bridge such long skips, the skipped
+    read's other half becomes a branch of its own, and that gives six (reversed: five) predecessors 255 or more rows back, rows whose
+    every predecessor lies beyond the ring and, reversed, a row without in-edge in the middle of the order -- but never more than eight
+    (reversed: five) in-edges.  The edge-list walk beyond the eighth in-edge comes from the third pack, a constructed fan whose node has
+    ten in-edges (tests/test_gpu_poa_graph_edges.py has the whole family); all next to ordinary rows, in the barrier form and the team
+    forms of the loop."""
     for k, v in env.items():
         monkeypatch.setenv(k, v)
-    rng = np.random.default_rng(77)
-    acgt = np.frombuffer(b"ACGT", np.uint8)
-    tx = acgt[rng.integers(0, 4, 1400)]
-
-    def noisy(a, err=0.06):
-        r = rng.random(len(a))
-        b = a.copy()
-        sub = r < err * 0.4
-        b[sub] = acgt[rng.integers(0, 4, int(sub.sum()))]
-        return b[(r >= err * 0.7) | (r < err * 0.4)]          # a few deletions too
-
-    pack = [noisy(tx).tobytes() for _ in range(10)]
-    # exon skipping: 300 .. 620 bases left out at different places
-    for a, n in ((200, 300), (450, 620), (800, 410), (150, 505)):
-        pack.append(noisy(np.concatenate([tx[:a], tx[a + n:]])).tobytes())
-    # many different resume points into the same downstream node: prefixes of different lengths glued to the common tail from 1000 on
-    for cut in range(300, 960, 55):
-        pack.append(noisy(np.concatenate([tx[:cut], tx[1000:]]), 0.03).tobytes())
-    pack.sort(key=lambda s: -len(s))
-    rows, width, counters = gpu_ctx.poa_msa([pack, pack[::-1]])
-    for got, p in zip(rows, (pack, pack[::-1])):
+    pack = constructed_graphs.old_far_pack()
+    fan = constructed_graphs.fan(9, 2)[0]
+    rows, width, counters = gpu_ctx.poa_msa([pack, pack[::-1], fan])
+    for got, p in zip(rows, (pack, pack[::-1], fan)):
         want, _ = oracle.poa_msa(p)
         assert got == want
 

@@ -64,7 +64,7 @@ POA_SHALLOW_READS = 40
 CLASS_COLS = (1024, 1536, 2048, 2560, 4096, 6144, 8192)
 
 _LINE = re.compile(r"poa class (?P<prefix>.*?)(?P<cols>\d+) cols \((?P<nw>\d+) waves x (?P<cpl>\d+), (?:ring|teams) (?P<ring>\d+)"
-                   r"(?:, ring (?P<slots>\d+) reach \d+)?\) pass (?P<pass>\d+): (?P<packs>\d+) packs, \d+ slots x (?P<mb>[\d.]+) MB, "
+                   r"(?:, ring (?P<slots>\d+) reach (?P<reach>\d+))?\) pass (?P<pass>\d+): (?P<packs>\d+) packs, \d+ slots x (?P<mb>[\d.]+) MB, "
                    r"\d+ blocks/CU, group (?P<group>\d+) pk (?P<pk>\d+)(?: band (?P<band>\d+))?")
 _SLOTS = re.compile(r"packs, (\d+) slots x ")          # the arena slots of a line (`slots` above is the teams' LDS ring)
 
