@@ -239,6 +239,11 @@ void rattle_hip_assignment_free(rattle_assignment *a);
  * generate_multiple_sequence_alignment).  Packs are independent; pack p holds sequences
  * [pack_first[p], pack_first[p+1]) of the concatenated input, aligned in that order.
  * Result: for each pack its MSA width and rows (one row per sequence, '-' for gaps).
+ * Letters: every byte except 0 (the padding of the device's rows) and '-' (the gap of the rows returned) is a letter; a sequence that
+ * holds one of the two is refused with RATTLE_ERR_ARG, before the device is looked at.  Two letters match iff their bytes are equal
+ * (T and U, upper and lower case differ), as in the reference.  One limit the reference does not have: an MSA column holds at most
+ * five distinct letters (A, C, G, T and U fit); a pack that would need a sixth ends the call with RATTLE_ERR_ARG and a message that
+ * names the pack and the limit.
  */
 typedef struct {
     uint32_t n_packs;

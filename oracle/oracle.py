@@ -145,6 +145,24 @@ class Oracle(_Lib):
         raw = buf.raw
         return [raw[i * w:(i + 1) * w] for i in range(n)]
 
+    def poa_msa_table(self, seqs):
+        """poa_msa with a deliberately wrong scoring rule (orc_poa_msa_table), for proving that a pack would notice it: two letters match
+        when (c >> 1) & 3 is the same for both, as a score table indexed by those bits sees them (T = U, A = @ = a ...).  Returns the rows."""
+        n = len(seqs)
+        off = np.zeros(n + 1, np.uint64)
+        off[1:] = np.cumsum([len(s) for s in seqs], dtype=np.uint64)
+        cat = b"".join(seqs)
+        self.lib.orc_poa_msa_table.restype = C.c_int64
+        cap = 64 * (int(off[-1]) + 1024) + n * 1024
+        while True:
+            buf = C.create_string_buffer(cap)
+            w = self.lib.orc_poa_msa_table(C.c_char_p(cat), _ptr(off, C.c_uint64), C.c_uint32(n), buf, C.c_uint64(cap))
+            if w >= 0:
+                break
+            cap *= 4
+        raw = buf.raw
+        return [raw[i * w:(i + 1) * w] for i in range(n)]
+
     def set_cv_order(self, order: bytes):
         assert len(order) == 6
         self.lib.orc_set_cv_order(C.c_char_p(order))

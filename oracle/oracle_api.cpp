@@ -269,6 +269,32 @@ int64_t orc_poa_msa_blind(const char *seqs, const uint64_t *off, uint32_t n, int
     return (int64_t)W;
 }
 
+// poa_msa's loop with a deliberately WRONG scoring rule (tests: a pack of several alphabets must notice): two letters match when
+// (c >> 1) & 3 is the same for both, which is how a score table indexed by those two bits sees them (T = U, A = @ = a, ...).  Every
+// alignment is computed for the sequence and a copy of the graph with every letter replaced by "ACTG"[(c >> 1) & 3]; the alignment is
+// then added to the true graph with the true letters, where nodes are told apart by byte as ever.
+int64_t orc_poa_msa_table(const char *seqs, const uint64_t *off, uint32_t n, char *msa_out, uint64_t cap) {
+    poa_graph_t G;
+    poa_engine_t eng;
+    eng.simd = poa_simd_default();
+    auto twin = [](char c) { return "ACTG"[((unsigned char)c >> 1) & 3]; };
+    for (uint32_t k = 0; k < n; ++k) {
+        const std::string s(seqs + off[k], seqs + off[k + 1]);
+        std::string t = s;
+        for (char &c : t) c = twin(c);
+        poa_graph_t M = G;
+        for (auto &nd : M.nodes) nd.letter = twin(nd.letter);
+        poa_alignment_t a = eng.align(t, M);
+        G.dp_cells = M.dp_cells;
+        G.add_alignment(a, s);
+    }
+    std::vector<std::string> msa = G.msa();
+    size_t W = msa.empty() ? 0 : msa[0].size();
+    if (W * n > cap) return -1;
+    for (uint32_t i = 0; i < n; ++i) memcpy(msa_out + (size_t)i * W, msa[i].data(), W);
+    return (int64_t)W;
+}
+
 void orc_free(void *p) { free(p); }
 
 // AVX2 int16 row fill of the POA matrices (orc_poa.hpp); returns whether this CPU can run it.

@@ -699,6 +699,19 @@ int rattle_hip_poa_msa(rattle_ctx *c, const uint8_t *seq, const uint64_t *off, u
                        uint32_t n_packs, rattle_msa_set **out) {
     if (!c || !off || !pack_first || !out) { set_error("null argument"); return RATTLE_ERR_ARG; }
     *out = nullptr;
+    // byte 0 pads the rows' columns beyond a sequence and '-' is the gap of the rows that come back: neither can be a letter (checked on the
+    // host, before the device is looked at)
+    for (uint32_t q = 0; q < n_seqs; ++q) {
+        if (off[q + 1] < off[q]) { set_error("offsets must not decrease"); return RATTLE_ERR_ARG; }
+        const uint64_t len = off[q + 1] - off[q];
+        if (!len) continue;
+        if (!seq) { set_error("null argument"); return RATTLE_ERR_ARG; }
+        const bool nul = memchr(seq + off[q], 0, len) != nullptr;
+        if (nul || memchr(seq + off[q], '-', len)) {
+            set_error("poa_msa: sequence " + std::to_string(q) + " holds " + (nul ? "a zero byte" : "'-'") + ": every byte but 0 and '-' is a letter");
+            return RATTLE_ERR_ARG;
+        }
+    }
     RT_TRY(use_device(c));
     return poa_msa_run(c, seq, off, n_seqs, pack_first, n_packs, out);
 }

@@ -105,7 +105,8 @@ struct poa_args {
 #endif
 
 enum { POA_OK = 0, POA_ERR_NODES = 1, POA_ERR_CELLS = 2, POA_ERR_EDGES = 3, POA_ERR_ALN = 4, POA_ERR_SPILL = 5, POA_ERR_GRAPH = 6, POA_ERR_SYNC = 7,
-       POA_ERR_BAND = 8 /* (PK == 8) an alignment of the pack has no certified band: the pack goes to the full-row kernels */ };
+       POA_ERR_BAND = 8 /* (PK == 8) an alignment of the pack has no certified band: the pack goes to the full-row kernels */,
+       POA_ERR_LETTERS = 9 /* an aligned group would need a sixth node (the group record is a uint4: five distinct letters per MSA column): the caller's input */ };
 
 struct poa_ws {                    // per-block workspace: global pointers + LDS + wave-uniform state
     uint4 *nrec, *nal, *plan, *planb, *planc, *pland;
@@ -3344,7 +3345,7 @@ __global__ __launch_bounds__(64 * NW * pk_teams(RING, PK), poa_min_waves(CPL, NW
                                 const uint32_t n_al = rd_nal(nd.x);
                                 uint4 al = make_uint4(0, 0, 0, 0);
                                 if (n_al) al = S.nal[an];
-                                if (n_al >= 4) { S.err = POA_ERR_GRAPH; break; }
+                                if (n_al >= 4) { S.err = POA_ERR_LETTERS; break; }
                                 cur = g_add_node(S, A, letter);
                                 if (S.err) break;
                                 nn_push(cur, inf.w);
@@ -3354,7 +3355,7 @@ __global__ __launch_bounds__(64 * NW * pk_teams(RING, PK), poa_min_waves(CPL, NW
                                     u4_set(cal, k, a);
                                     uint4 ar = S.nrec[a];
                                     const uint32_t c = rd_nal(ar.x);
-                                    if (c >= 4) { S.err = POA_ERR_GRAPH; break; }
+                                    if (c >= 4) { S.err = POA_ERR_LETTERS; break; }
                                     uint4 aal = c ? S.nal[a] : make_uint4(0, 0, 0, 0);
                                     u4_set(aal, c, cur);
                                     S.nal[a] = aal;
@@ -4033,6 +4034,9 @@ struct poa_run {
                     // protocol error): the pack is dropped and run again in the barrier form, which cannot time out
                     again.push_back(p); sync_retry = true;
                     if (ENV.timing) fprintf(stderr, "[rattle]     poa: pack %u gave up %s: again in the barrier form\n", p, sync_diagnosis(false).c_str());
+                } else if (s == POA_ERR_LETTERS) {
+                    set_error("poa: pack " + std::to_string(p) + " holds more than five distinct letters in one MSA column (letters match by byte equality; an aligned group holds at most five nodes)");
+                    return RATTLE_ERR_ARG;
                 } else {
                     std::string msg = "poa_kernel: pack " + std::to_string(p) + " failed with status " + std::to_string(s);
                     if (s == POA_ERR_SYNC) msg += " (" + sync_diagnosis(true) + ")";

@@ -516,3 +516,79 @@ def test_rna_alphabet(chk, mode):
     rows = to_rows(noisy_msa(rng, 33, 150, alphabet=b"ACGU"))
     want, _ = chk.run(rows, quals_for(rows, rng), mode)
     assert want["consensus"].count(b"U") > 20 and b"T" not in want["consensus"] and want["erased"].sum() > 0
+
+
+# ---- T and U in one column ----------------------------------------------------------------------------------------------
+T, U = ord("T"), ord("U")
+
+
+def t_and_u_packs(rng):
+    """Two packs of 6 and 10 rows built like vote_packs (every row a full window, a gapless column between any two chosen ones), whose
+    chosen columns split between T and U: 3 : 3 (a tie), 4 : 2, 2 : 4 and T : U : '-' at 2 : 2 : 2; and winners whose share lies on both
+    sides of the literal 0.3 -- of 6 rows, 2 (0.33) and 1 (0.17: 1.8 falls between the counts), of 10 rows, 3 (exactly 0.3) and 2."""
+    A, C, G = b"ACG"
+    chosen = {
+        6: [[(T, 3), (U, 3)], [(T, 4), (U, 2)], [(T, 2), (U, 4)], [(T, 2), (U, 2), (GAP, 2)],
+            [(T, 2), (U, 1), (A, 1), (C, 1), (G, 1)], [(U, 2), (T, 1), (A, 1), (C, 1), (G, 1)], [(T, 2), (U, 2), (A, 1), (C, 1)],
+            [(T, 1), (U, 1), (A, 1), (C, 1), (G, 1), (GAP, 1)]],
+        10: [[(T, 5), (U, 5)], [(T, 6), (U, 4)], [(T, 4), (U, 6)], [(T, 4), (U, 4), (GAP, 2)],
+             [(T, 3), (U, 2), (A, 2), (C, 2), (G, 1)], [(U, 3), (T, 2), (A, 2), (C, 2), (G, 1)], [(T, 3), (U, 3), (A, 2), (C, 2)],
+             [(T, 2), (U, 2), (A, 2), (C, 2), (G, 2)], [(T, 2), (U, 2), (GAP, 2), (A, 2), (C, 2)]],
+    }
+    packs = []
+    abc = np.frombuffer(b"ACGTU", np.uint8)
+    for R, cols in chosen.items():
+        cols = cols * 6                                                # six draws of every column: other rows, other qualities
+        body = np.stack([column_of(rng, c, R) for c in cols], 1)
+        W = 12 + 2 * len(cols) + 12
+        mat = np.tile(abc[rng.integers(0, 5, W)], (R, 1))
+        mat[:, 12:12 + 2 * len(cols):2] = body
+        qmat = rng.integers(33, 127, mat.shape).astype(np.uint8)
+        packs.append((mat, qmat, cols))
+    return packs
+
+
+@pytest.mark.parametrize("mode", [1, 2])
+@pytest.mark.parametrize("order", [b"U-GTCA", b"U-GTAC"])
+def test_t_and_u_in_one_column(chk, order, mode):
+    """What POA #1 of reads written with U gives when some members were reverse-complemented (their A became T): T and U vote in slots of
+    their own.  A tie goes to the slot that comes first in the order (strict >: U before '-' before T, in both orders); in mode 1 the
+    qualities cover 33 .. 126, so that `err_ratio * perr[q] > cerr` holds and fails for T rows under a U winner and for U rows under a T winner."""
+    rng = np.random.default_rng(900)
+    packs = t_and_u_packs(rng)
+    inputs = [(to_rows(mat), quals_of_matrix(mat, qmat)) for mat, qmat, _ in packs]
+    want = [chk.want(rows, q, mode, order=order) for rows, q in inputs]
+    got = chk.got(inputs, mode, order=order)
+    n_ties, flags = 0, set()
+    made = {(T, U): set(), (U, T): set()}                              # (row's letter, winner) -> outcomes of the substitution test
+    for (mat, qmat, cols), (rows, q), w, g in zip(packs, inputs, want, got):
+        R = len(rows)
+        chk.compare(g, w, rows, mode, tag=f"{R} rows")
+        assert w["erased"].sum() == 0 and np.all(w["rfirst"] == 0)
+        for j, counts in enumerate(cols):
+            k = 12 + 2 * j
+            t = tied(counts)
+            first = min(t, key=order.index)
+            assert w["winner"][k] == first and w["occ"][k] == max(n for _, n in counts) and w["total_occ"][k] == R
+            n_ties += len(t) > 1 and T in t and U in t
+            if len(t) > 1 and T in t and U in t:
+                assert first == U                                       # U is slot 0
+            ratio = w["occ"][k] / w["total_occ"][k]
+            flags.add(int(ratio >= 0.3))
+            if mode == 1 and first in (T, U) and ratio >= 0.3:
+                cerr = float(w["err_bits"][k:k + 1].view(np.float64)[0])
+                for i in np.nonzero(mat[:, k] == (T if first == U else U))[0]:
+                    made[(int(mat[i, k]), first)].add(bool(30.0 * 10.0 ** (-(int(qmat[i, k]) - 33) / 10.0) > cerr))
+    assert n_ties >= 6 * 9 and flags == {0, 1}
+    assert 2 / 6 > 0.3 > 1 / 6 and 3 / 10 == 0.3 > 2 / 10
+    if mode == 1:
+        assert made == {(T, U): {True, False}, (U, T): {True, False}}, made
+        # the corrected reads hold both letters, and some T became U and some U became T
+        out = b"".join(s for w in want for s, _ in w["reads"])
+        assert out.count(b"T") > 20 and out.count(b"U") > 20
+        for (mat, _, _), w in zip(packs, want):
+            before = (int((mat == T).sum()), int((mat == U).sum()))
+            after = (sum(s.count(b"T") for s, _ in w["reads"]), sum(s.count(b"U") for s, _ in w["reads"]))
+            assert before != after
+    else:
+        assert all(b"T" in w["consensus"] and b"U" in w["consensus"] for w in want)
