@@ -130,118 +130,90 @@ std::vector<std::string> split_string(const std::string &s, char d) {           
     return out;
 }
 
-// ---- input: fasta.cpp:7-31 (gz), :33-205 (fasta), :207-370 (fastq) ------------------------------
-std::string unzip_file(const std::string &filename, int index) {
-    gzFile in = gzopen(filename.c_str(), "rb");
-    std::cerr << "Start decompressing file" << std::endl;
-    std::string out = filename.substr(0, index);
-    if (!in) die("Error: Failed to decompress the file");
-    FILE *f = fopen(out.c_str(), "wb");
-    if (!f) die("Error: Failed to decompress the file");
-    std::vector<unsigned char> buf(1 << 20);
-    int n;
-    while ((n = gzread(in, buf.data(), (unsigned)buf.size())) > 0) fwrite(buf.data(), 1, n, f);
-    fclose(f);
-    gzclose(in);
-    std::cerr << "Decompressing file Complete" << std::endl;
-    return out;
+// the name of a record: the first token of its header, without the '@' / '>' (what api._first_token returns)
+std::string record_name(const char *p, size_t n) {
+    const char *e = p + n;
+    if (p < e && (*p == '@' || *p == '>')) ++p;
+    while (p < e && (*p == ' ' || *p == '\t')) ++p;
+    const char *t = p;
+    while (t < e && *t != ' ' && *t != '\t') ++t;
+    return std::string(p, t - p);
+}
+std::string record_name(const std::string &h) { return record_name(h.data(), h.size()); }
+
+std::string g17(double x) { char b[40]; snprintf(b, sizeof b, "%.17g", x); return b; }   // a double that reads back exactly
+
+void write_text(const std::string &path, const std::string &text) {
+    std::ofstream f(path);
+    f << text;
+    f.close();
+    if (!f) die("Error: cannot write " + path);
 }
 
-struct line_reader {
-    std::ifstream in;
-    bool dos = false, first = true;
-    explicit line_reader(const std::string &p) : in(p) {}
-    bool next(std::string &l) {
-        if (!std::getline(in, l)) return false;
-        if (first) { dos = !l.empty() && l[l.size() - 1] == '\r'; first = false; }
-        if (dos && !l.empty()) l.erase(l.size() - 1);
-        return true;
-    }
-};
+// --report / --support: made on one device
+void one_device_only(const args_t &a, const char *flag, const char *what) {
+    if (a.has(flag) && a.has("devices") && split_string(a.str("devices", ""), ',').size() > 1)
+        die(std::string("\nError: --") + flag + " cannot be combined with --devices naming more than one device: the " + what + " is made on one device\n");
+}
 
-// Records of a FASTQ (4 lines each) or FASTA (header + joined, upper-cased sequence lines; quality '~').
-void for_each_record(const std::string &file, bool fastq,
-                     const std::function<void(const std::string &, const std::string &, const std::string &, const std::string &)> &f) {
-    if (fastq) {
-        // whole file in memory, lines by memchr (std::getline was the slowest part of a run once the kernels were fast);
-        // same line semantics: '\n' separated, a final line without one counts, DOS endings detected on line 1
-        FILE *fp = fopen(file.c_str(), "rb");
-        if (!fp) return;
-        std::string buf;
-        {
-            fseek(fp, 0, SEEK_END);
-            const long sz = ftell(fp);
-            fseek(fp, 0, SEEK_SET);
-            buf.resize(sz > 0 ? (size_t)sz : 0);
-            size_t got = 0;
-            while (got < buf.size()) { const size_t n = fread(&buf[got], 1, buf.size() - got, fp); if (n == 0) break; got += n; }
-            buf.resize(got);
-            fclose(fp);
-        }
-        std::string fld[4];
-        bool dos = false, first = true;
-        int id = 0;
-        size_t pos = 0;
-        while (pos < buf.size()) {
-            const char *nl = (const char *)memchr(buf.data() + pos, '\n', buf.size() - pos);
-            size_t end = nl ? (size_t)(nl - buf.data()) : buf.size();
-            size_t len = end - pos;
-            if (first) { dos = len > 0 && buf[end - 1] == '\r'; first = false; }
-            if (dos && len > 0) --len;
-            fld[id].assign(buf.data() + pos, len);
-            pos = end + 1;
-            if (++id == 4) { f(fld[0], fld[1], fld[2], fld[3]); id = 0; }
-        }
-        return;
-    }
-    line_reader R(file);
-    std::string l;
+// --count-pass auto|seed|search|index -> 0..3 (rattle_assign_params::count_pass; the names are what RATTLE_PAIR_COUNT takes)
+int count_pass_of(const std::string &form, const char *usage) {
+    const char *forms[] = {"auto", "seed", "search", "index"};
+    for (int i = 0; i < 4; ++i) if (form == forms[i]) return i;
+    std::cerr << "ERROR: --count-pass takes auto, seed, search or index (got '" << form << "')\nusage: " << usage;
+    exit(EXIT_FAILURE);
+}
+
+std::string output_dir(const args_t &a) {
+    const std::string dir = a.str("output", ".");
+    if (a.has("output") && access(dir.c_str(), F_OK)) die("\nOutput folder doesn't exit. Please create it first. \n");
+    return dir;
+}
+
+rattle_cluster_params default_cluster_params() {                                  // main.cpp:133-324, `cluster`'s defaults
+    rattle_cluster_params P;
+    P.t_s = 0.2; P.t_v = 1000000; P.bv_threshold = 0.4; P.min_bv_threshold = 0.2; P.bv_falloff = 0.05;
+    P.min_reads_cluster = 0; P.use_hc = 0; P.repr_percentile = 0.15; P.is_rna = 0;
+    return P;
+}
+rattle_correct_params default_correct_params() {                                  // main.cpp:325-412, `correct`'s defaults
+    rattle_correct_params P;
+    memset(&P, 0, sizeof(P));
+    P.min_occ = 0.3; P.gap_occ = 0.3; P.err_ratio = 30.0; P.split = 200; P.min_reads = 5; P.n_threads = 0;
+    return P;
+}
+
+// ---- input of `polish`: the records of a FASTQ file (4 lines each), fasta.cpp:207-270 --------------
+void for_each_fastq_record(const std::string &file, const std::function<void(const std::string &, const std::string &, const std::string &, const std::string &)> &f) {
+    // whole file in memory, lines by memchr (std::getline was the slowest part of a run once the kernels were fast);
+    // same line semantics: '\n' separated, a final line without one counts, DOS endings detected on line 1
+    FILE *fp = fopen(file.c_str(), "rb");
+    if (!fp) return;
+    std::string buf;
     {
-        std::string h, s;
-        bool have = false;
-        while (R.next(l)) {
-            if (l.empty()) continue;
-            if (l[0] == '>') {
-                if (have) f(h, s, "", std::string(s.size(), '~'));
-                h = l; s.clear(); have = true;
-            } else {
-                for (char &c : l) c = (char)toupper((unsigned char)c);          // fasta.cpp:60,131
-                s += l;
-            }
-        }
-        if (have) f(h, s, "", std::string(s.size(), '~'));
+        fseek(fp, 0, SEEK_END);
+        const long sz = ftell(fp);
+        fseek(fp, 0, SEEK_SET);
+        buf.resize(sz > 0 ? (size_t)sz : 0);
+        size_t got = 0;
+        while (got < buf.size()) { const size_t n = fread(&buf[got], 1, buf.size() - got, fp); if (n == 0) break; got += n; }
+        buf.resize(got);
+        fclose(fp);
     }
-}
-
-void resolve_input(std::string &filename, bool &fastq) {                           // main.cpp:35-57
-    if (access(filename.c_str(), F_OK)) die("\nError: Input file not found! \n");
-    int index = (int)filename.find_last_of(".");
-    std::string ext = filename.substr(index + 1);
-    if (ext == "gz") {
-        filename = unzip_file(filename, index);
-        index = (int)filename.find_last_of(".");
-        ext = filename.substr(index + 1);
+    std::string fld[4];
+    bool dos = false, first = true;
+    int id = 0;
+    size_t pos = 0;
+    while (pos < buf.size()) {
+        const char *nl = (const char *)memchr(buf.data() + pos, '\n', buf.size() - pos);
+        size_t end = nl ? (size_t)(nl - buf.data()) : buf.size();
+        size_t len = end - pos;
+        if (first) { dos = len > 0 && buf[end - 1] == '\r'; first = false; }
+        if (dos && len > 0) --len;
+        fld[id].assign(buf.data() + pos, len);
+        pos = end + 1;
+        if (++id == 4) { f(fld[0], fld[1], fld[2], fld[3]); id = 0; }
     }
-    if (ext == "fq" || ext == "fastq") fastq = true;
-    else if (ext == "fasta" || ext == "fa") fastq = false;
-    else die("\nError: Input file format incorrect! Please use fasta/fastq file. \n");
-}
-
-// main.cpp:66-112 + fasta.cpp:207-270: everything, file order, with qualities.
-read_set_t read_inputs(const std::vector<std::string> &files, const std::vector<std::string> &labels) {
-    if (!labels.empty() && labels.size() != files.size()) die("\nError: Number of input files and number of label files do not match\n");
-    read_set_t reads;
-    int sample = 0;
-    for (std::string fn : files) {
-        bool fastq;
-        resolve_input(fn, fastq);
-        std::string lab = labels.empty() ? "" : "," + labels[sample];
-        for_each_record(fn, fastq, [&](const std::string &h, const std::string &s, const std::string &a, const std::string &q) {
-            reads.push_back(read_t{h + lab, s, a, q});
-        });
-        ++sample;
-    }
-    return reads;
 }
 
 void write_fastq_file(const read_set_t &reads, const std::string &file) {        // fasta.cpp:436-445
@@ -314,6 +286,7 @@ cluster_set_t read_clusters(const std::string &path) {            // current 3-f
 // takes are gathered from the spans in parallel.  Same semantics: '\n' separated lines, a last line without one counts, DOS
 // endings detected on the first line, FASTA sequence lines joined and upper-cased, quality '~' for FASTA.
 struct span { const char *p; uint32_t n; };
+std::string record_name(const span &h) { return record_name(h.p, h.n); }
 struct read_table {
     std::vector<std::unique_ptr<std::string>> pools;       // owned bytes (inflated input, joined FASTA sequences, label suffixes)
     std::vector<std::pair<void *, size_t>> maps;           // mapped files
@@ -458,6 +431,16 @@ void read_table_inputs(read_table &T, const std::vector<std::string> &files, con
     }
 }
 
+// the same as owned strings, for the host-only modes (the reference's side effect included: a .gz input is also inflated next to itself)
+read_set_t read_inputs(const std::vector<std::string> &files, const std::vector<std::string> &labels) {
+    read_table T;
+    read_table_inputs(T, files, labels, true);
+    auto str = [](const span &x) { return std::string(x.p, x.n); };
+    read_set_t reads;
+    for (size_t i = 0; i < T.n(); ++i) reads.push_back(read_t{T.head(i), str(T.seq[i]), str(T.ann[i]), str(T.qual[i])});
+    return reads;
+}
+
 // concatenated bases (and qualities, padded with '!' / cut to the sequence length) of the records `ids` in that order
 // bytes that are filled right away by all threads: no zero fill by one thread first (a GB-sized std::vector costs 0.1 s that way)
 struct byte_buf {
@@ -551,13 +534,6 @@ struct device_team {
 };
 
 // ---- device calls --------------------------------------------------------------------------------
-void load(rattle_ctx *ctx, const read_set_t &reads, int k, bool both) {
-    std::string cat;
-    std::vector<uint64_t> off(1, 0);
-    for (auto &r : reads) { cat += r.seq; off.push_back(cat.size()); }
-    chk(rattle_hip_load_reads(ctx, (const uint8_t *)cat.data(), off.data(), (uint32_t)reads.size(), k, both ? 1 : 0));
-}
-
 cluster_set_t to_set(rattle_cluster_set *cs) {
     cluster_set_t out(cs->n_clusters);
     for (uint32_t c = 0; c < cs->n_clusters; ++c) {
@@ -571,9 +547,8 @@ cluster_set_t to_set(rattle_cluster_set *cs) {
 // context creation (HIP start-up, ~0.5 s) and, for `correct`, the POA arena allocation (seconds for > 100 GB) run on a helper
 // thread while the main thread reads the input
 struct team_opener {
-    device_team &team;
     std::thread th;
-    team_opener(device_team &t, const args_t &a, uint64_t arena_hint) : team(t) {
+    void start(device_team &t, const args_t &a, uint64_t arena_hint) {
         th = std::thread([&t, &a, arena_hint] {
             t.open(a);
             if (arena_hint) t.run([&](int, rattle_ctx *c) { (void)rattle_hip_reserve_arena(c, arena_hint); });
@@ -583,71 +558,83 @@ struct team_opener {
     ~team_opener() { wait(); }
 };
 
+// the clusters' members as rattle_hip_correct_reads takes them
+void flatten_members(const cluster_set_t &clusters, std::vector<uint32_t> &coff, std::vector<int32_t> &mid, std::vector<uint8_t> &mrev) {
+    coff.assign(1, 0);
+    for (auto &c : clusters) {
+        for (auto &s : c.seqs) { mid.push_back(s.seq_id); mrev.push_back(s.rev ? 1 : 0); }
+        coff.push_back((uint32_t)mid.size());
+    }
+}
+
+// record i of a correction's consensi under the header the mode gives it
+read_t consensus_record(const rattle_read_set &S, uint32_t i, const std::string &header) {
+    return read_t{header, std::string(S.seq + S.off[i], S.seq + S.off[i + 1]), "+", std::string(S.qual + S.off[i], S.qual + S.off[i + 1])};
+}
+
 uint64_t input_bytes(const std::vector<std::string> &files) {
     uint64_t tot = 0;
     for (auto &f : files) { struct stat st; if (stat(f.c_str(), &st) == 0) tot += (uint64_t)st.st_size * (f.size() > 3 && f.substr(f.size() - 3) == ".gz" ? 4 : 1); }
     return tot;
 }
 
-// (Round 5 tried leaving through _exit() once every output is closed, instead of giving ~10 GB of host buffers and a ~100 GB device
-// arena back one by one: no gain -- the time outside the timers is process START, 0.5 s of library loading and HIP start-up -- and a
-// loss for the next process: the kernel reclaims the device memory of a process that just vanished in the background, and the
-// following `rattle correct` waited 1.1 s instead of 0.04 s for its arena, profiles/round5_cli_e2e_1M.txt.)
-int mode_cluster(int argc, char **argv) {
-    std::vector<opt_def> defs = {
-        {"help", {"-h", "--help"}, false}, {"input", {"-i", "--input"}, true}, {"label", {"-l", "--label"}, true},
-        {"output", {"-o", "--output"}, true}, {"threads", {"-t", "--threads"}, true}, {"kmer_size", {"-k", "--kmer-size"}, true},
-        {"t_s", {"-s", "--score-threshold"}, true}, {"t_v", {"-v", "--max-variance"}, true}, {"iso", {"--iso"}, false},
-        {"iso_kmer_size", {"--iso-kmer-size"}, true}, {"iso_t_s", {"--iso-score-threshold"}, true},
-        {"iso_t_v", {"--iso-max-variance"}, true}, {"bv_threshold", {"-B", "--bv-start-threshold"}, true},
-        {"bv_min_threshold", {"-b", "--bv-end-threshold"}, true}, {"bv_falloff", {"-f", "--bv-falloff"}, true},
-        {"min_reads_cluster", {"-r", "--min-reads-cluster"}, true}, {"repr_percentile", {"-p", "--repr-percentile"}, true},
-        {"rna", {"--rna"}, false}, {"verbose", {"--verbose"}, false}, {"raw", {"--raw"}, false},
-        {"lower_len", {"--lower-length"}, true}, {"upper_len", {"--upper-length"}, true}, {"device", {"--device"}, true},
-        {"devices", {"--devices"}, true}, {"host-exchange", {"--host-exchange"}, false}, {"write-unzipped", {"--write-unzipped"}, false},
-        {"count-pass", {"--count-pass"}, true}, {"report", {"--report"}, false}};
-    args_t a = parse(argc, argv, defs);
-    const char *usage = "rattle cluster -i reads.fq [-o dir] [--rna] [--iso] ... (flags of RATTLE's cluster mode)\n"
-                        "  --report           also write cluster_report.tsv: one line per join (a read joining a cluster's founder, or a cluster\n"
-                        "                     joining another through their representatives) with the comparison that decided it: pass,\n"
-                        "                     bit-vector threshold, strand, bases, hc_bases, min_len, score, variance (one device only)\n"
-                        "  --devices 0,1,..   one job over several GPUs (RCCL; --host-exchange: in-process exchange on host buffers)\n"
-                        "  --count-pass auto|seed|search|index   form of the count pass (what RATTLE_PAIR_COUNT sets; default auto)\n";
-    if (a.has("count-pass")) {
-        // the library reads the variable once, at its first evaluation: set it before any device thread starts
-        const std::string form = a.str("count-pass", "auto");
-        if (form == "auto") unsetenv("RATTLE_PAIR_COUNT");
-        else if (form == "seed" || form == "search" || form == "index") setenv("RATTLE_PAIR_COUNT", form.c_str(), 1);
-        else {
-            std::cerr << "ERROR: --count-pass takes auto, seed, search or index (got '" << form << "')\nusage: " << usage;
-            return EXIT_FAILURE;
-        }
-    }
-    if (a.has("help")) {
-        std::cerr << usage <<
-                     "  --write-unzipped   also write the inflated copy of a .gz input next to it, as the reference does\n";
-        return EXIT_SUCCESS;
-    }
-    if (!a.has("input")) die("ERROR: No input file provided");
-    int k = a.i("kmer_size", 10), iso_k = a.i("iso_kmer_size", 11);
-    if (k > 16 || iso_k > 16) die("\nError: maximum kmer size = 16 \n");
-    std::string outdir = a.str("output", ".");
-    if (a.has("output") && access(outdir.c_str(), F_OK)) die("\nOutput folder doesn't exit. Please create it first. \n");
-    bool is_rna = a.has("rna");
-    const bool want_report = a.has("report");
-    if (want_report && a.has("devices") && split_string(a.str("devices", ""), ',').size() > 1)
-        die("\nError: --report cannot be combined with --devices naming more than one device: the cluster report is made on one device\n");
-    std::cerr << "RNA mode: " << std::boolalpha << is_rna << std::endl;
-    std::cerr << "Reading fasta file... " << std::endl;
+// ---- `rattle cluster` ----------------------------------------------------------------------------------------------------
+struct cluster_job {
+    args_t a;
+    int k = 10, iso_k = 11;
+    bool is_rna = false, want_report = false;
+    std::string outdir;
     device_team team;
-    team_opener opener(team, a, 0);
+    team_opener opener;                           // opens `team` behind the reading of the input
+    read_table T;
+    std::vector<uint32_t> order;                  // processing position -> record index (= the reference's `ann`)
+    byte_buf cat;                                 // the bases of the reads in processing order
+    std::vector<uint64_t> off;                    // [n + 1] their offsets in `cat`
+    rattle_cluster_params P = default_cluster_params();
+    cluster_set_t clusters;                       // over processing positions: the gene clusters, then with --iso the isoform clusters
+    std::string report_text = "level\tpass\tbv_threshold\tabsorbed\tinto\tstrand\tbases\thc_bases\tmin_len\tscore\tvariance\n";
+    std::unique_ptr<cli_timer> t_out;
+    void options(int argc, char **argv) {
+        a = parse(argc, argv, {
+            {"help", {"-h", "--help"}, false}, {"input", {"-i", "--input"}, true}, {"label", {"-l", "--label"}, true},
+            {"output", {"-o", "--output"}, true}, {"threads", {"-t", "--threads"}, true}, {"kmer_size", {"-k", "--kmer-size"}, true},
+            {"t_s", {"-s", "--score-threshold"}, true}, {"t_v", {"-v", "--max-variance"}, true}, {"iso", {"--iso"}, false},
+            {"iso_kmer_size", {"--iso-kmer-size"}, true}, {"iso_t_s", {"--iso-score-threshold"}, true},
+            {"iso_t_v", {"--iso-max-variance"}, true}, {"bv_threshold", {"-B", "--bv-start-threshold"}, true},
+            {"bv_min_threshold", {"-b", "--bv-end-threshold"}, true}, {"bv_falloff", {"-f", "--bv-falloff"}, true},
+            {"min_reads_cluster", {"-r", "--min-reads-cluster"}, true}, {"repr_percentile", {"-p", "--repr-percentile"}, true},
+            {"rna", {"--rna"}, false}, {"verbose", {"--verbose"}, false}, {"raw", {"--raw"}, false},
+            {"lower_len", {"--lower-length"}, true}, {"upper_len", {"--upper-length"}, true}, {"device", {"--device"}, true},
+            {"devices", {"--devices"}, true}, {"host-exchange", {"--host-exchange"}, false}, {"write-unzipped", {"--write-unzipped"}, false},
+            {"count-pass", {"--count-pass"}, true}, {"report", {"--report"}, false}});
+        const char *usage = "rattle cluster -i reads.fq [-o dir] [--rna] [--iso] ... (flags of RATTLE's cluster mode)\n"
+                            "  --report           also write cluster_report.tsv: one line per join (a read joining a cluster's founder, or a cluster\n"
+                            "                     joining another through their representatives) with the comparison that decided it: pass,\n"
+                            "                     bit-vector threshold, strand, bases, hc_bases, min_len, score, variance (one device only)\n"
+                            "  --devices 0,1,..   one job over several GPUs (RCCL; --host-exchange: in-process exchange on host buffers)\n"
+                            "  --count-pass auto|seed|search|index   form of the count pass (what RATTLE_PAIR_COUNT sets; default auto)\n";
+        if (a.has("count-pass")) {
+            // the library reads the variable once, at its first evaluation: set it before any device thread starts
+            const std::string form = a.str("count-pass", "auto");
+            if (count_pass_of(form, usage) == 0) unsetenv("RATTLE_PAIR_COUNT");
+            else setenv("RATTLE_PAIR_COUNT", form.c_str(), 1);
+        }
+        if (a.has("help")) {
+            std::cerr << usage <<
+                         "  --write-unzipped   also write the inflated copy of a .gz input next to it, as the reference does\n";
+            exit(EXIT_SUCCESS);
+        }
+        if (!a.has("input")) die("ERROR: No input file provided");
+        k = a.i("kmer_size", 10); iso_k = a.i("iso_kmer_size", 11);
+        if (k > 16 || iso_k > 16) die("\nError: maximum kmer size = 16 \n");
+        outdir = output_dir(a);
+        is_rna = a.has("rna"); want_report = a.has("report");
+        one_device_only(a, "report", "cluster report");
+        std::cerr << "RNA mode: " << std::boolalpha << is_rna << std::endl;
+    }
     // main.cpp:16-64 + fasta.cpp:272-370: ann = running record index over ALL records, length filter unless --raw, reads that
     // contain 'N' skipped; then sort_read_set (fasta.cpp:458-464): stable, longest first (a counting sort over the lengths)
-    read_table T;
-    { cli_timer t("read input"); read_table_inputs(T, split_string(a.str("input", ""), ','), split_string(a.str("label", ""), ','), a.has("write-unzipped")); }
-    std::unique_ptr<cli_timer> t_sort(new cli_timer("filter + sort + gather"));
-    std::vector<uint32_t> order;                  // processing position -> record index (= the reference's `ann`)
-    {
+    void filter_and_sort() {
         const bool raw = a.has("raw");
         const int lo = a.i("lower_len", 150), hi = a.i("upper_len", 100000);
         const size_t n = T.n();
@@ -672,290 +659,302 @@ int mode_cluster(int argc, char **argv) {
         order.resize(start[(size_t)max_len + 1]);
         for (size_t i = 0; i < n; ++i) if (keep[i]) order[start[max_len - T.seq[i].n]++] = (uint32_t)i;
     }
-    std::cout << "Reads: " << order.size() << std::endl;
-    byte_buf cat;
-    std::vector<uint64_t> off;
-    gather_reads(T, order, cat, nullptr, off);
-    std::cerr << "Done" << std::endl;
-    const uint32_t n_reads = (uint32_t)order.size();
-
-    t_sort.reset();
-    { cli_timer t("wait for device"); opener.wait(); }
-    std::unique_ptr<cli_timer> t_lib(new cli_timer("library: load + cluster"));
-    rattle_cluster_params P;
-    P.t_s = a.d("t_s", 0.2); P.t_v = a.d("t_v", 1000000); P.bv_threshold = a.d("bv_threshold", 0.4);
-    P.min_bv_threshold = a.d("bv_min_threshold", 0.2); P.bv_falloff = a.d("bv_falloff", 0.05);
-    P.min_reads_cluster = a.i("min_reads_cluster", 0); P.use_hc = 0; P.repr_percentile = a.d("repr_percentile", 0.15);
-    P.is_rna = is_rna ? 1 : 0;
-    rattle_cluster_set *raw = nullptr;
+    // the devices open on a helper thread while the input is read, filtered, sorted and gathered
+    void read_input() {
+        std::cerr << "Reading fasta file... " << std::endl;
+        opener.start(team, a, 0);
+        { cli_timer t("read input"); read_table_inputs(T, split_string(a.str("input", ""), ','), split_string(a.str("label", ""), ','), a.has("write-unzipped")); }
+        {
+            cli_timer t("filter + sort + gather");
+            filter_and_sort();
+            std::cout << "Reads: " << order.size() << std::endl;
+            gather_reads(T, order, cat, nullptr, off);
+            std::cerr << "Done" << std::endl;
+        }
+        cli_timer t("wait for device");
+        opener.wait();
+    }
     // cluster_report.tsv: one line per join, in the library's order; ids_of: the set's ids -> processing positions (null: identity)
-    std::string report_text = "level\tpass\tbv_threshold\tabsorbed\tinto\tstrand\tbases\thc_bases\tmin_len\tscore\tvariance\n";
-    auto report_rows = [&](const rattle_cluster_set *cs, int level, const cseq_t *ids_of) {
+    void report_rows(const rattle_cluster_set *cs, int level, const cseq_t *ids_of) {
         rattle_cluster_report *rp = nullptr;
         chk(rattle_hip_cluster_report(cs, &rp));
-        auto name = [&](int32_t id) {                                           // the id: the header's first token, without its '@' / '>'
-            const span &h = T.header[order[ids_of ? (uint32_t)ids_of[id].seq_id : (uint32_t)id]];
-            const char *b = h.p, *e = h.p + h.n;
-            if (b < e && (*b == '@' || *b == '>')) ++b;
-            const char *t = b;
-            while (t < e && *t != ' ' && *t != '\t') ++t;
-            return std::string(b, t - b);
-        };
-        char num[3][40];
-        for (uint64_t i = 0; i < rp->n; ++i) {
-            snprintf(num[0], sizeof num[0], "%.17g", rp->bv_threshold[i]);
-            snprintf(num[1], sizeof num[1], "%.17g", rp->score[i]);
-            snprintf(num[2], sizeof num[2], "%.17g", rp->variance[i]);
-            report_text += std::to_string(level) + "\t" + std::to_string(rp->pass[i]) + "\t" + num[0] + "\t" + name(rp->absorbed[i]) + "\t" +
+        auto name = [&](int32_t id) { return record_name(T.header[order[ids_of ? (uint32_t)ids_of[id].seq_id : (uint32_t)id]]); };
+        for (uint64_t i = 0; i < rp->n; ++i)
+            report_text += std::to_string(level) + "\t" + std::to_string(rp->pass[i]) + "\t" + g17(rp->bv_threshold[i]) + "\t" + name(rp->absorbed[i]) + "\t" +
                            name(rp->into[i]) + "\t" + (rp->rev[i] ? "-" : "+") + "\t" + std::to_string(rp->bases[i]) + "\t" +
-                           std::to_string(rp->hc_bases[i]) + "\t" + std::to_string(rp->min_len[i]) + "\t" + num[1] + "\t" + num[2] + "\n";
-        }
+                           std::to_string(rp->hc_bases[i]) + "\t" + std::to_string(rp->min_len[i]) + "\t" + g17(rp->score[i]) + "\t" + g17(rp->variance[i]) + "\n";
         rattle_hip_cluster_report_free(rp);
-    };
-    auto write_report = [&]() {
-        const std::string path = outdir + "/cluster_report.tsv";
-        std::ofstream f(path);
-        f << report_text;
-        f.close();
-        if (!f) die("Error: cannot write " + path);
-    };
-    team.run([&](int r, rattle_ctx *ctx) {                                      // every rank ends up with the same clusters
-        if (want_report) chk(rattle_hip_set_cluster_report(ctx, 1));
-        chk(rattle_hip_load_reads(ctx, cat.data(), off.data(), n_reads, k, is_rna ? 0 : 1));
-        rattle_cluster_set *mine = nullptr;
-        chk(rattle_hip_cluster_reads(ctx, &P, &mine));
-        if (r == 0) raw = mine; else rattle_hip_cluster_set_free(mine);
-    });
-    t_lib.reset();
-    cli_timer t_out("to clusters.out");
-    if (want_report) report_rows(raw, 0, nullptr);
-    cluster_set_t gene = to_set(raw);
-    std::cerr << "Gene clustering done" << std::endl;
-    std::cerr << gene.size() << " gene clusters found" << std::endl;
-    const std::string out_path = outdir + "/clusters.out";
-    if (!a.has("iso")) {                                                         // main.cpp:264-277
+    }
+    void gene_level() {
+        rattle_cluster_set *raw = nullptr;
+        {
+            cli_timer t("library: load + cluster");
+            P.t_s = a.d("t_s", P.t_s); P.t_v = a.d("t_v", P.t_v); P.bv_threshold = a.d("bv_threshold", P.bv_threshold);
+            P.min_bv_threshold = a.d("bv_min_threshold", P.min_bv_threshold); P.bv_falloff = a.d("bv_falloff", P.bv_falloff);
+            P.min_reads_cluster = a.i("min_reads_cluster", 0); P.repr_percentile = a.d("repr_percentile", P.repr_percentile);
+            P.is_rna = is_rna ? 1 : 0;
+            team.run([&](int r, rattle_ctx *ctx) {                                      // every rank ends up with the same clusters
+                if (want_report) chk(rattle_hip_set_cluster_report(ctx, 1));
+                chk(rattle_hip_load_reads(ctx, cat.data(), off.data(), (uint32_t)order.size(), k, is_rna ? 0 : 1));
+                rattle_cluster_set *mine = nullptr;
+                chk(rattle_hip_cluster_reads(ctx, &P, &mine));
+                if (r == 0) raw = mine; else rattle_hip_cluster_set_free(mine);
+            });
+        }
+        t_out.reset(new cli_timer("to clusters.out"));
+        if (want_report) report_rows(raw, 0, nullptr);
+        clusters = to_set(raw);
+        std::cerr << "Gene clustering done" << std::endl;
+        std::cerr << clusters.size() << " gene clusters found" << std::endl;
+    }
+    // main.cpp:281-323: second level per gene cluster with the iso parameters.  All gene clusters at once: the subsets are
+    // independent (rattle_hip_cluster_subsets runs them concurrently, and over the ranks when there are several)
+    void iso_level() {
+        P.t_s = a.d("iso_t_s", 0.3); P.t_v = a.d("iso_t_v", 25);
+        cluster_set_t gene = std::move(clusters), iso;
+        std::vector<uint32_t> ids;
+        std::vector<uint64_t> sub_off(1, 0);
         for (auto &c : gene) {
+            std::stable_sort(c.seqs.begin(), c.seqs.end(), [](const cseq_t &x, const cseq_t &y) { return x.seq_id > y.seq_id; });
+            std::stable_sort(c.seqs.begin(), c.seqs.end(), [&](const cseq_t &x, const cseq_t &y) { return off[x.seq_id + 1] - off[x.seq_id] > off[y.seq_id + 1] - off[y.seq_id]; });
+            for (auto &s : c.seqs) ids.push_back((uint32_t)s.seq_id);
+            sub_off.push_back(ids.size());
+        }
+        std::vector<rattle_cluster_set *> subs(gene.size() ? gene.size() : 1, nullptr);
+        team.run([&](int r, rattle_ctx *ctx) {
+            chk(rattle_hip_load_reads(ctx, cat.data(), off.data(), (uint32_t)order.size(), iso_k, is_rna ? 0 : 1));
+            std::vector<rattle_cluster_set *> mine(gene.size() ? gene.size() : 1, nullptr);
+            chk(rattle_hip_cluster_subsets(ctx, &P, ids.data(), sub_off.data(), (uint32_t)gene.size(), mine.data(), 0));
+            if (r == 0) subs = mine; else for (auto *x : mine) rattle_hip_cluster_set_free(x);
+        });
+        int gi = 0;
+        for (auto &c : gene) {
+            if (want_report) report_rows(subs[gi], 1, c.seqs.data());
+            for (auto &ic : to_set(subs[gi])) {
+                cluster_t o;
+                o.main_seq = cseq_t{c.seqs[ic.main_seq.seq_id].seq_id, ic.main_seq.rev, gi};
+                for (auto &s : ic.seqs) o.seqs.push_back(cseq_t{c.seqs[s.seq_id].seq_id, s.rev, gi});
+                iso.push_back(o);
+            }
+            ++gi;
+        }
+        std::cerr << "Isoform clustering done" << std::endl;
+        std::cerr << iso.size() << " isoform clusters found" << std::endl;
+        clusters = std::move(iso);
+    }
+    void write() {                                                                   // clusters.out holds record indices (main.cpp:264-277)
+        for (auto &c : clusters) {
             c.main_seq.seq_id = (int)order[c.main_seq.seq_id];
             for (auto &s : c.seqs) s.seq_id = (int)order[s.seq_id];
         }
-        write_clusters(gene, out_path);
-        if (want_report) write_report();
+        write_clusters(clusters, outdir + "/clusters.out");
+        if (want_report) write_text(outdir + "/cluster_report.tsv", report_text);
         team.close();
-        return EXIT_SUCCESS;
+        t_out.reset();
     }
-    // main.cpp:281-323: second level per gene cluster with the iso parameters
-    P.t_s = a.d("iso_t_s", 0.3); P.t_v = a.d("iso_t_v", 25);
-    cluster_set_t iso;
-    // all gene clusters at once: the subsets are independent (rattle_hip_cluster_subsets runs them concurrently, and
-    // over the ranks when there are several)
-    std::vector<uint32_t> ids;
-    std::vector<uint64_t> sub_off(1, 0);
-    for (auto &c : gene) {
-        std::stable_sort(c.seqs.begin(), c.seqs.end(), [](const cseq_t &x, const cseq_t &y) { return x.seq_id > y.seq_id; });
-        std::stable_sort(c.seqs.begin(), c.seqs.end(), [&](const cseq_t &x, const cseq_t &y) { return off[x.seq_id + 1] - off[x.seq_id] > off[y.seq_id + 1] - off[y.seq_id]; });
-        for (auto &s : c.seqs) ids.push_back((uint32_t)s.seq_id);
-        sub_off.push_back(ids.size());
-    }
-    std::vector<rattle_cluster_set *> subs(gene.size() ? gene.size() : 1, nullptr);
-    team.run([&](int r, rattle_ctx *ctx) {
-        chk(rattle_hip_load_reads(ctx, cat.data(), off.data(), n_reads, iso_k, is_rna ? 0 : 1));
-        std::vector<rattle_cluster_set *> mine(gene.size() ? gene.size() : 1, nullptr);
-        chk(rattle_hip_cluster_subsets(ctx, &P, ids.data(), sub_off.data(), (uint32_t)gene.size(), mine.data(), 0));
-        if (r == 0) subs = mine; else for (auto *x : mine) rattle_hip_cluster_set_free(x);
-    });
-    int gi = 0;
-    for (auto &c : gene) {
-        if (want_report) report_rows(subs[gi], 1, c.seqs.data());
-        for (auto &ic : to_set(subs[gi])) {
-            cluster_t o;
-            o.main_seq = cseq_t{(int)order[c.seqs[ic.main_seq.seq_id].seq_id], ic.main_seq.rev, gi};
-            for (auto &s : ic.seqs) o.seqs.push_back(cseq_t{(int)order[c.seqs[s.seq_id].seq_id], s.rev, gi});
-            iso.push_back(o);
-        }
-        ++gi;
-    }
-    std::cerr << "Isoform clustering done" << std::endl;
-    std::cerr << iso.size() << " isoform clusters found" << std::endl;
-    write_clusters(iso, out_path);
-    if (want_report) write_report();
-    team.close();
+};
+
+int mode_cluster(int argc, char **argv) {
+    cluster_job J;
+    J.options(argc, argv);
+    J.read_input();
+    J.gene_level();
+    if (J.a.has("iso")) J.iso_level();
+    J.write();
     return EXIT_SUCCESS;
 }
 
-// `rattle assign`: the reads of -i placed on the transcripts of -x by their best cluster_together score (include/rattle_hip.h, "assign").
+// ---- `rattle assign` -----------------------------------------------------------------------------------------------------
+// The reads of -i placed on the transcripts of -x by their best cluster_together score (include/rattle_hip.h, "assign").
 // Every record of both files takes part, in file order: there is no length filter and no sort.  A read with a base other than A, C,
 // G, T, U is not compared and comes out unassigned (`cluster` skips such reads).
-int mode_assign(int argc, char **argv) {
-    std::vector<opt_def> defs = {
-        {"help", {"-h", "--help"}, false}, {"input", {"-i", "--input"}, true}, {"targets", {"-x", "--transcripts"}, true},
-        {"output", {"-o", "--output"}, true}, {"kmer_size", {"-k", "--kmer-size"}, true}, {"t_s", {"-s", "--score-threshold"}, true},
-        {"t_v", {"-v", "--max-variance"}, true}, {"bv_threshold", {"-B", "--bv-start-threshold"}, true}, {"rna", {"--rna"}, false},
-        {"count-pass", {"--count-pass"}, true}, {"device", {"--device"}, true}, {"devices", {"--devices"}, true},
-        {"target-batch", {"--target-batch"}, true}, {"read-chunk", {"--read-chunk"}, true}};
-    args_t a = parse(argc, argv, defs);
-    const char *usage = "rattle assign -i reads.fq -x transcripts.fq [-o dir] [-k 10] [-s 0.2] [-v 1000000] [-B 0.4] [--rna] [--device n]\n"
-                        "  places every read of -i on the transcript of -x that accepts it with the best score (the comparison `cluster` joins\n"
-                        "  reads by, the transcript in the seed's role) and writes assignments.tsv (one line per read: target, strand, score,\n"
-                        "  second_score, n_accepted, bases, hc_bases, min_len, variance) and target_counts.tsv (reads per transcript)\n"
-                        "  --count-pass auto|seed|search|index   form of the count pass (default auto)\n"
-                        "  --target-batch n / --read-chunk n     transcripts per evaluation / reads indexed at a time (the result does not depend on them)\n";
-    if (a.has("help")) { std::cerr << usage; return EXIT_SUCCESS; }
-    if (!a.has("input")) die("ERROR: No input file provided (-i reads)");
-    if (!a.has("targets")) die("ERROR: No transcript file provided (-x transcripts)");
-    if (a.has("devices")) die("\nError: assign runs on one device: --devices is not available, use --device\n");
+struct assign_job {
+    args_t a;
+    int k = 10;
+    std::string outdir;
     rattle_assign_params P;
-    memset(&P, 0, sizeof P);
-    const std::string form = a.str("count-pass", "auto");
-    if (form == "auto") P.count_pass = 0; else if (form == "seed") P.count_pass = 1; else if (form == "search") P.count_pass = 2;
-    else if (form == "index") P.count_pass = 3;
-    else { std::cerr << "ERROR: --count-pass takes auto, seed, search or index (got '" << form << "')\nusage: " << usage; return EXIT_FAILURE; }
-    const int k = a.i("kmer_size", 10);
-    if (k > 16) die("\nError: maximum kmer size = 16 \n");
-    const std::string outdir = a.str("output", ".");
-    if (a.has("output") && access(outdir.c_str(), F_OK)) die("\nOutput folder doesn't exit. Please create it first. \n");
-    P.t_s = a.d("t_s", 0.2); P.t_v = a.d("t_v", 1000000); P.bv_threshold = a.d("bv_threshold", 0.4);
-    P.is_rna = a.has("rna") ? 1 : 0;
-    P.target_batch = (uint32_t)std::max(0, a.i("target-batch", 0)); P.read_chunk = (uint32_t)std::max(0, a.i("read-chunk", 0));
-    std::cerr << "RNA mode: " << std::boolalpha << (P.is_rna != 0) << std::endl;
     device_team team;
-    team_opener opener(team, a, 0);
-    read_table R, X;
-    { cli_timer t("read input"); read_table_inputs(R, split_string(a.str("input", ""), ','), {}, false); read_table_inputs(X, split_string(a.str("targets", ""), ','), {}, false); }
-    auto clean = [](const span &s) { for (uint32_t i = 0; i < s.n; ++i) if (!strchr("ACGTU", s.p[i]) || !s.p[i]) return false; return true; };
-    std::vector<uint32_t> rid, xid(X.n());
-    for (size_t i = 0; i < X.n(); ++i) {
-        if (!clean(X.seq[i])) die("\nError: transcript " + X.head(i) + " has a base other than A, C, G, T, U\n");
-        xid[i] = (uint32_t)i;
-    }
-    for (size_t i = 0; i < R.n(); ++i) if (clean(R.seq[i])) rid.push_back((uint32_t)i);
-    if (rid.size() != R.n()) std::cerr << "\n" << R.n() - rid.size() << "  reads with a base other than A, C, G, T, U are left unassigned" << std::endl;
-    std::cout << "Reads: " << R.n() << ", transcripts: " << X.n() << std::endl;
+    team_opener opener;                           // opens `team` behind the reading of the input
+    read_table R, X;                              // the reads and the transcripts
+    std::vector<uint32_t> rid, xid;               // the records that are submitted: the clean reads, every transcript
     byte_buf rcat, xcat;
     std::vector<uint64_t> roff, xoff;
-    gather_reads(R, rid, rcat, nullptr, roff);
-    gather_reads(X, xid, xcat, nullptr, xoff);
-    opener.wait();
     rattle_assignment *A = nullptr;
-    { cli_timer t("library: assign"); chk(rattle_hip_assign_reads(team.ctx[0], xcat.data(), xoff.data(), (uint32_t)xid.size(), rcat.data(), roff.data(), (uint32_t)rid.size(), k, &P, &A)); }
-    auto name = [](const span &h) {                                               // the id: the header's first token, without its '@' / '>'
-        const char *b = h.p, *e = h.p + h.n;
-        if (b < e && (*b == '@' || *b == '>')) ++b;
-        while (b < e && (*b == ' ' || *b == '\t')) ++b;
-        const char *t = b;
-        while (t < e && *t != ' ' && *t != '\t') ++t;
-        return std::string(b, t - b);
-    };
-    std::vector<uint64_t> n_best(X.n(), 0), n_unique(X.n(), 0);
-    std::string text = "read\ttarget\tstrand\tscore\tsecond_score\tn_accepted\tbases\thc_bases\tmin_len\tvariance\n";
-    char num[3][40];
-    size_t at = 0;                                                                // next submitted read
-    for (size_t i = 0; i < R.n(); ++i) {
-        const bool sent = at < rid.size() && rid[at] == i;
-        const int32_t t = sent ? A->target[at] : -1;
-        snprintf(num[0], sizeof num[0], "%.17g", sent ? A->score[at] : -1.0);
-        snprintf(num[1], sizeof num[1], "%.17g", sent ? A->second_score[at] : -1.0);
-        snprintf(num[2], sizeof num[2], "%.17g", sent ? A->variance[at] : 0.0);
-        text += name(R.header[i]) + "\t" + (t >= 0 ? name(X.header[t]) : std::string("*")) + "\t" + (t < 0 ? "*" : A->rev[at] ? "-" : "+") + "\t" +
-                num[0] + "\t" + num[1] + "\t" + std::to_string(sent ? A->n_accepted[at] : 0u) + "\t" + std::to_string(sent ? A->bases[at] : 0) + "\t" +
-                std::to_string(sent ? A->hc_bases[at] : 0) + "\t" + std::to_string(sent ? A->min_len[at] : 0u) + "\t" + num[2] + "\n";
-        if (t >= 0) { ++n_best[t]; if (A->second_score[at] < 0) ++n_unique[t]; }
-        if (sent) ++at;
+    std::string text, counts;                     // assignments.tsv, target_counts.tsv
+    void options(int argc, char **argv) {
+        a = parse(argc, argv, {
+            {"help", {"-h", "--help"}, false}, {"input", {"-i", "--input"}, true}, {"targets", {"-x", "--transcripts"}, true},
+            {"output", {"-o", "--output"}, true}, {"kmer_size", {"-k", "--kmer-size"}, true}, {"t_s", {"-s", "--score-threshold"}, true},
+            {"t_v", {"-v", "--max-variance"}, true}, {"bv_threshold", {"-B", "--bv-start-threshold"}, true}, {"rna", {"--rna"}, false},
+            {"count-pass", {"--count-pass"}, true}, {"device", {"--device"}, true}, {"devices", {"--devices"}, true},
+            {"target-batch", {"--target-batch"}, true}, {"read-chunk", {"--read-chunk"}, true}});
+        const char *usage = "rattle assign -i reads.fq -x transcripts.fq [-o dir] [-k 10] [-s 0.2] [-v 1000000] [-B 0.4] [--rna] [--device n]\n"
+                            "  places every read of -i on the transcript of -x that accepts it with the best score (the comparison `cluster` joins\n"
+                            "  reads by, the transcript in the seed's role) and writes assignments.tsv (one line per read: target, strand, score,\n"
+                            "  second_score, n_accepted, bases, hc_bases, min_len, variance) and target_counts.tsv (reads per transcript)\n"
+                            "  --count-pass auto|seed|search|index   form of the count pass (default auto)\n"
+                            "  --target-batch n / --read-chunk n     transcripts per evaluation / reads indexed at a time (the result does not depend on them)\n";
+        if (a.has("help")) { std::cerr << usage; exit(EXIT_SUCCESS); }
+        if (!a.has("input")) die("ERROR: No input file provided (-i reads)");
+        if (!a.has("targets")) die("ERROR: No transcript file provided (-x transcripts)");
+        if (a.has("devices")) die("\nError: assign runs on one device: --devices is not available, use --device\n");
+        memset(&P, 0, sizeof P);
+        P.count_pass = count_pass_of(a.str("count-pass", "auto"), usage);
+        k = a.i("kmer_size", 10);
+        if (k > 16) die("\nError: maximum kmer size = 16 \n");
+        outdir = output_dir(a);
+        P.t_s = a.d("t_s", 0.2); P.t_v = a.d("t_v", 1000000); P.bv_threshold = a.d("bv_threshold", 0.4);
+        P.is_rna = a.has("rna") ? 1 : 0;
+        P.target_batch = (uint32_t)std::max(0, a.i("target-batch", 0)); P.read_chunk = (uint32_t)std::max(0, a.i("read-chunk", 0));
+        std::cerr << "RNA mode: " << std::boolalpha << (P.is_rna != 0) << std::endl;
     }
-    rattle_hip_assignment_free(A);
-    std::string counts = "target\tlength\treads\tunique_reads\n";
-    for (size_t t = 0; t < X.n(); ++t)
-        counts += name(X.header[t]) + "\t" + std::to_string(X.seq[t].n) + "\t" + std::to_string(n_best[t]) + "\t" + std::to_string(n_unique[t]) + "\n";
-    for (auto &f : {std::make_pair(std::string("assignments.tsv"), &text), std::make_pair(std::string("target_counts.tsv"), &counts)}) {
-        const std::string path = outdir + "/" + f.first;
-        std::ofstream o(path);
-        o << *f.second;
-        o.close();
-        if (!o) die("Error: cannot write " + path);
+    // both files, the alphabet screen and the gather, while the device opens
+    void read_input() {
+        opener.start(team, a, 0);
+        { cli_timer t("read input"); read_table_inputs(R, split_string(a.str("input", ""), ','), {}, false); read_table_inputs(X, split_string(a.str("targets", ""), ','), {}, false); }
+        auto clean = [](const span &s) { for (uint32_t i = 0; i < s.n; ++i) if (!strchr("ACGTU", s.p[i]) || !s.p[i]) return false; return true; };
+        xid.resize(X.n());
+        for (size_t i = 0; i < X.n(); ++i) {
+            if (!clean(X.seq[i])) die("\nError: transcript " + X.head(i) + " has a base other than A, C, G, T, U\n");
+            xid[i] = (uint32_t)i;
+        }
+        for (size_t i = 0; i < R.n(); ++i) if (clean(R.seq[i])) rid.push_back((uint32_t)i);
+        if (rid.size() != R.n()) std::cerr << "\n" << R.n() - rid.size() << "  reads with a base other than A, C, G, T, U are left unassigned" << std::endl;
+        std::cout << "Reads: " << R.n() << ", transcripts: " << X.n() << std::endl;
+        gather_reads(R, rid, rcat, nullptr, roff);
+        gather_reads(X, xid, xcat, nullptr, xoff);
+        opener.wait();
     }
-    team.close();
-    std::cerr << "Done" << std::endl;
+    void run() {
+        cli_timer t("library: assign");
+        chk(rattle_hip_assign_reads(team.ctx[0], xcat.data(), xoff.data(), (uint32_t)xid.size(), rcat.data(), roff.data(), (uint32_t)rid.size(), k, &P, &A));
+    }
+    // one line per read of -i, the reads that were not submitted included; then one line per transcript
+    void format() {
+        std::vector<uint64_t> n_best(X.n(), 0), n_unique(X.n(), 0);
+        text = "read\ttarget\tstrand\tscore\tsecond_score\tn_accepted\tbases\thc_bases\tmin_len\tvariance\n";
+        size_t at = 0;                                                                // next submitted read
+        for (size_t i = 0; i < R.n(); ++i) {
+            const bool sent = at < rid.size() && rid[at] == i;
+            const int32_t t = sent ? A->target[at] : -1;
+            text += record_name(R.header[i]) + "\t" + (t >= 0 ? record_name(X.header[t]) : std::string("*")) + "\t" + (t < 0 ? "*" : A->rev[at] ? "-" : "+") + "\t" +
+                    g17(sent ? A->score[at] : -1.0) + "\t" + g17(sent ? A->second_score[at] : -1.0) + "\t" + std::to_string(sent ? A->n_accepted[at] : 0u) + "\t" +
+                    std::to_string(sent ? A->bases[at] : 0) + "\t" + std::to_string(sent ? A->hc_bases[at] : 0) + "\t" + std::to_string(sent ? A->min_len[at] : 0u) + "\t" +
+                    g17(sent ? A->variance[at] : 0.0) + "\n";
+            if (t >= 0) { ++n_best[t]; if (A->second_score[at] < 0) ++n_unique[t]; }
+            if (sent) ++at;
+        }
+        rattle_hip_assignment_free(A);
+        counts = "target\tlength\treads\tunique_reads\n";
+        for (size_t t = 0; t < X.n(); ++t)
+            counts += record_name(X.header[t]) + "\t" + std::to_string(X.seq[t].n) + "\t" + std::to_string(n_best[t]) + "\t" + std::to_string(n_unique[t]) + "\n";
+    }
+    void write() {
+        write_text(outdir + "/assignments.tsv", text);
+        write_text(outdir + "/target_counts.tsv", counts);
+        team.close();
+        std::cerr << "Done" << std::endl;
+    }
+};
+
+int mode_assign(int argc, char **argv) {
+    assign_job J;
+    J.options(argc, argv);
+    J.read_input();
+    J.run();
+    J.format();
+    J.write();
     return EXIT_SUCCESS;
 }
 
-int mode_correct(int argc, char **argv) {
-    std::vector<opt_def> defs = {
-        {"help", {"-h", "--help"}, false}, {"input", {"-i", "--input"}, true}, {"label", {"-l", "--label"}, true},
-        {"clusters", {"-c", "--clusters"}, true}, {"output", {"-o", "--output"}, true}, {"gap-occ", {"-g", "--gap-occ"}, true},
-        {"min-occ", {"-m", "--min-occ"}, true}, {"split", {"-s", "--split"}, true}, {"min-reads", {"-r", "--min-reads"}, true},
-        {"threads", {"-t", "--threads"}, true}, {"verbose", {"--verbose"}, false}, {"device", {"--device"}, true},
-        {"vote-order", {"--vote-order"}, true}, {"max-pack-cells", {"--max-pack-cells"}, true}, {"devices", {"--devices"}, true},
-        {"host-exchange", {"--host-exchange"}, false}, {"write-unzipped", {"--write-unzipped"}, false}, {"report", {"--report"}, false},
-        {"support", {"--support"}, false}};
-    args_t a = parse(argc, argv, defs);
-    if (a.has("help")) {
-        std::cerr << "rattle correct -i reads.fq -c clusters.out [-o dir] ... (flags of RATTLE's correct mode)\n"
-                     "  --report             also write correction_report.tsv: per record of corrected.fq its lengths before and after, the bases\n"
-                     "                       trimmed at either end, and how many columns matched, were substituted, kept against the\n"
-                     "                       winner, inserted, deleted or kept against a gap winner\n"
-                     "  --support            also write consensus_support.tsv: per record of consensi.fq how many reads stand behind every\n"
-                     "                       base (support: reads that voted for it, depth: reads that voted in its column, composed through\n"
-                     "                       the pack consensi for a cluster of several packs), the smallest ratio and the number of bases\n"
-                     "                       with no majority; one device only.  consensi.fq itself keeps its qualities\n"
-                     "  --max-pack-cells N   leave packs whose largest alignment needs more than N DP cells uncorrected (default: only\n"
-                     "                       packs that do not fit the device are skipped); skipped packs are listed in skipped_packs.tsv\n"
-                     "  --devices 0,1,..     one job over several GPUs (RCCL; --host-exchange: in-process exchange on host buffers)\n";
-        return EXIT_SUCCESS;
-    }
-    if (!a.has("input")) die("ERROR: No input file provided");
-    if (!a.has("clusters")) die("ERROR: No clusters file provided");
-    const bool want_support = a.has("support");
-    if (want_support && a.has("devices") && split_string(a.str("devices", ""), ',').size() > 1)
-        die("\nError: --support cannot be combined with --devices naming more than one device: the consensus support is made on one device\n");
-    std::cerr << "Reading fasta file... ";
-    std::vector<std::string> labels = split_string(a.str("label", ""), ',');
-    const std::vector<std::string> files = split_string(a.str("input", ""), ',');
+// ---- `rattle correct` ----------------------------------------------------------------------------------------------------
+struct correct_job {
+    args_t a;
+    bool want_report = false, want_support = false, gene_mode = true;
+    std::vector<std::string> labels, files;
+    std::string outdir, corrected_path, corrected_tmp;
     device_team team;
-    // arena hint: ~440 kB of FASTQ per pack of 200 one-kb reads, at most a device full of resident packs in each of two
-    // column classes (1792 places x 18.4 MB + 2048 x 34.5 MB = 104 GB at 1e6 one-kb reads, round 4; a hint that falls short
-    // costs a second allocation -- 2.7 s in the first end-to-end run of round 4, when the hint was 89 GB -- not the result).  The
-    // driver clears what it hands out at ~20 ms per GB, so a generous hint is seconds of start-up.
-    const uint64_t packs_hint = std::min<uint64_t>(input_bytes(files) / 440000 + 1, 3840);
-    team_opener opener(team, a, packs_hint * (30ull << 20));
+    team_opener opener;                           // opens `team` behind the reading of the input
     read_table T;
-    { cli_timer t("read input"); read_table_inputs(T, files, labels, a.has("write-unzipped")); }
-    std::cerr << "Done" << std::endl;
-    std::unique_ptr<cli_timer> t_cl(new cli_timer("read clusters + gather"));
-    cluster_set_t clusters = read_clusters(a.str("clusters", ""));
-    if (clusters.empty()) die("\nError: empty clusters file\n");
-    const bool gene_mode = clusters[0].main_seq.gene_id == -1;                   // correct.cpp:322
-    const uint32_t n_reads = (uint32_t)T.n();
-
-    byte_buf cat, qcat;
+    cluster_set_t clusters;
+    byte_buf cat, qcat;                           // bases and qualities of every record, in file order, and their offsets
     std::vector<uint64_t> off;
-    {
-        std::vector<uint32_t> all(n_reads);
-        for (uint32_t i = 0; i < n_reads; ++i) all[i] = i;
-        gather_reads(T, all, cat, &qcat, off);
-    }
-    std::vector<uint32_t> coff(1, 0);
+    std::vector<uint32_t> coff;                   // the clusters' members, flattened
     std::vector<int32_t> mid;
     std::vector<uint8_t> mrev;
-    for (auto &c : clusters) {
-        for (auto &s : c.seqs) { mid.push_back(s.seq_id); mrev.push_back(s.rev ? 1 : 0); }
-        coff.push_back((uint32_t)mid.size());
+    rattle_correct_params P = default_correct_params();
+    std::atomic<bool> early_done{false}, early_failed{false};   // corrected.fq.tmp, written from the library's callback
+    rattle_correction *R = nullptr;
+    read_set_t consensi;
+    std::unique_ptr<cli_timer> t_out;
+    void options(int argc, char **argv) {
+        a = parse(argc, argv, {
+            {"help", {"-h", "--help"}, false}, {"input", {"-i", "--input"}, true}, {"label", {"-l", "--label"}, true},
+            {"clusters", {"-c", "--clusters"}, true}, {"output", {"-o", "--output"}, true}, {"gap-occ", {"-g", "--gap-occ"}, true},
+            {"min-occ", {"-m", "--min-occ"}, true}, {"split", {"-s", "--split"}, true}, {"min-reads", {"-r", "--min-reads"}, true},
+            {"threads", {"-t", "--threads"}, true}, {"verbose", {"--verbose"}, false}, {"device", {"--device"}, true},
+            {"vote-order", {"--vote-order"}, true}, {"max-pack-cells", {"--max-pack-cells"}, true}, {"devices", {"--devices"}, true},
+            {"host-exchange", {"--host-exchange"}, false}, {"write-unzipped", {"--write-unzipped"}, false}, {"report", {"--report"}, false},
+            {"support", {"--support"}, false}});
+        if (a.has("help")) {
+            std::cerr << "rattle correct -i reads.fq -c clusters.out [-o dir] ... (flags of RATTLE's correct mode)\n"
+                         "  --report             also write correction_report.tsv: per record of corrected.fq its lengths before and after, the bases\n"
+                         "                       trimmed at either end, and how many columns matched, were substituted, kept against the\n"
+                         "                       winner, inserted, deleted or kept against a gap winner\n"
+                         "  --support            also write consensus_support.tsv: per record of consensi.fq how many reads stand behind every\n"
+                         "                       base (support: reads that voted for it, depth: reads that voted in its column, composed through\n"
+                         "                       the pack consensi for a cluster of several packs), the smallest ratio and the number of bases\n"
+                         "                       with no majority; one device only.  consensi.fq itself keeps its qualities\n"
+                         "  --max-pack-cells N   leave packs whose largest alignment needs more than N DP cells uncorrected (default: only\n"
+                         "                       packs that do not fit the device are skipped); skipped packs are listed in skipped_packs.tsv\n"
+                         "  --devices 0,1,..     one job over several GPUs (RCCL; --host-exchange: in-process exchange on host buffers)\n";
+            exit(EXIT_SUCCESS);
+        }
+        if (!a.has("input")) die("ERROR: No input file provided");
+        if (!a.has("clusters")) die("ERROR: No clusters file provided");
+        want_report = a.has("report"); want_support = a.has("support");
+        one_device_only(a, "support", "consensus support");
+        labels = split_string(a.str("label", ""), ','); files = split_string(a.str("input", ""), ',');
+        outdir = a.str("output", ".");
+        corrected_path = outdir + "/corrected.fq"; corrected_tmp = corrected_path + ".tmp";
     }
-    rattle_correct_params P;
-    memset(&P, 0, sizeof(P));
-    P.min_occ = a.d("min-occ", 0.3); P.gap_occ = a.d("gap-occ", 0.3); P.err_ratio = 30.0;
-    P.split = a.i("split", 200); P.min_reads = a.i("min-reads", 5); P.n_threads = 0;
-    std::string vo = a.str("vote-order", "");
-    if (vo.size() == 6) memcpy(P.vote_order, vo.data(), 6);
-    if (a.has("max-pack-cells")) P.max_pack_cells = std::stoull(a.str("max-pack-cells", "0"));
-    t_cl.reset();
-    { cli_timer t("wait for device + arena"); opener.wait(); }
-    auto tag = [&](int cid) {                                                    // correct.cpp:348-353
-        int gid = clusters[cid].main_seq.gene_id;
+    // the reads, the clusters and the gather, while the devices open and reserve their arenas
+    void read_input() {
+        std::cerr << "Reading fasta file... ";
+        // arena hint: ~440 kB of FASTQ per pack of 200 one-kb reads, at most a device full of resident packs in each of two
+        // column classes (1792 places x 18.4 MB + 2048 x 34.5 MB = 104 GB at 1e6 one-kb reads, round 4; a hint that falls short
+        // costs a second allocation -- 2.7 s in the first end-to-end run of round 4, when the hint was 89 GB -- not the result).  The
+        // driver clears what it hands out at ~20 ms per GB, so a generous hint is seconds of start-up.
+        const uint64_t packs_hint = std::min<uint64_t>(input_bytes(files) / 440000 + 1, 3840);
+        opener.start(team, a, packs_hint * (30ull << 20));
+        { cli_timer t("read input"); read_table_inputs(T, files, labels, a.has("write-unzipped")); }
+        std::cerr << "Done" << std::endl;
+        {
+            cli_timer t("read clusters + gather");
+            clusters = read_clusters(a.str("clusters", ""));
+            if (clusters.empty()) die("\nError: empty clusters file\n");
+            gene_mode = clusters[0].main_seq.gene_id == -1;                          // correct.cpp:322
+            std::vector<uint32_t> all(T.n());
+            for (uint32_t i = 0; i < all.size(); ++i) all[i] = i;
+            gather_reads(T, all, cat, &qcat, off);
+            flatten_members(clusters, coff, mid, mrev);
+            P.min_occ = a.d("min-occ", P.min_occ); P.gap_occ = a.d("gap-occ", P.gap_occ);
+            P.split = a.i("split", P.split); P.min_reads = a.i("min-reads", P.min_reads);
+            const std::string vo = a.str("vote-order", "");
+            if (vo.size() == 6) memcpy(P.vote_order, vo.data(), 6);
+            if (a.has("max-pack-cells")) P.max_pack_cells = std::stoull(a.str("max-pack-cells", "0"));
+        }
+        cli_timer t("wait for device + arena");
+        opener.wait();
+    }
+    std::string tag(int cid) const {                                                 // correct.cpp:348-353
+        const int gid = clusters[cid].main_seq.gene_id;
         if (gid == -1) return ",gene_cluster_" + std::to_string(cid);
         return ",gene_cluster_" + std::to_string(gid) + ",transcript_cluster_" + std::to_string(cid);
-    };
+    }
     // corrected.fq / uncorrected.fq (fasta.cpp:436-445 record layout) straight from the library's buffers: the text of each
     // file is laid out by record offsets and filled in parallel
-    auto write_set = [&](const rattle_read_set &S, bool corrected, const std::string &path) -> bool {
+    bool write_set(const rattle_read_set &S, bool corrected, const std::string &path) const {
         std::vector<std::string> tags(clusters.size());
         std::vector<uint64_t> at((size_t)S.n + 1, 0);
         for (uint32_t i = 0; i < S.n; ++i) {
@@ -982,49 +981,43 @@ int mode_correct(int argc, char **argv) {
             }
         });
         return text.finish();
-    };
-    const std::string outdir = a.str("output", ".");
-    // corrected.fq is formatted and written from the library's corrected_ready callback, while POA #2 / #3 still run on the
-    // device (one device: the sharded job reassembles its reads at the end).  The callback runs on a library thread with kernels
-    // in flight, so it never exits the process: it writes corrected.fq.tmp and records the outcome; the main thread renames the
-    // file once correct_reads has returned 0 (the reference writes its three files only after correct_reads, main.cpp:405-411: a
-    // failed run must not leave a complete-looking corrected.fq) or removes it and reports the failure.
-    struct early_out { std::function<bool(const rattle_read_set &)> write; std::atomic<bool> done{false}, failed{false}; } early;
-    const std::string corrected_path = outdir + "/corrected.fq", corrected_tmp = corrected_path + ".tmp";
-    early.write = [&](const rattle_read_set &S) { cli_timer t("corrected.fq (behind the consensus stages)"); return write_set(S, true, corrected_tmp); };
-    rattle_correction *R = nullptr;
-    std::unique_ptr<cli_timer> t_lib(new cli_timer("library: correct_reads"));
-    if (team.n() == 1) {
-        P.corrected_ready = [](void *u, const rattle_read_set_s *S, const uint32_t *) {
-            early_out *E = (early_out *)u;
-            if (E->write(*S)) E->done = true; else E->failed = true;
-        };
-        P.corrected_ready_user = &early;
     }
-    const bool want_report = a.has("report");
-    team.run([&](int r, rattle_ctx *ctx) {                                      // packs sharded over the ranks, result reassembled on rank 0
-        rattle_correction *mine = nullptr, *merged = nullptr;
-        if (want_report) chk(rattle_hip_set_correction_report(ctx, 1));
-        if (want_support) chk(rattle_hip_set_consensus_support(ctx, 1));
-        const int rc = rattle_hip_correct_reads(ctx, cat.data(), qcat.data(), off.data(), n_reads, (uint32_t)clusters.size(), coff.data(), mid.data(),
-                                                mrev.data(), &P, &mine);
-        if (rc != 0 && team.n() == 1) unlink(corrected_tmp.c_str());           // no half of a result stays behind
-        chk(rc);
-        if (team.n() == 1) { R = mine; return; }
-        chk(rattle_hip_correction_gather(ctx, mine, 0, &merged));
-        rattle_hip_correction_free(mine);
-        if (r == 0) R = merged;
-    });
-    if (early.failed) { unlink(corrected_tmp.c_str()); die("Error: cannot write " + corrected_path); }
-    if (early.done && rename(corrected_tmp.c_str(), corrected_path.c_str()) != 0) die("Error: cannot write " + corrected_path);
-    t_lib.reset();
-    std::unique_ptr<cli_timer> t_out(new cli_timer("format + write outputs"));
-    read_set_t consensi;
-    // consensus headers, correct.cpp:453-469,495-549: labels counted over the reads of the cluster's packs
-    std::vector<std::vector<int>> label_counts(clusters.size(), std::vector<int>(labels.size(), 0));
-    if (!labels.empty()) {
-        // only packs that produced a pack consensus count (as `reads=` does): packs the library skipped (budget rule: listed by
-        // their index among ALL packs of the cluster; POA #1 / #2 beyond the device: by their index among the QUEUED packs) do not
+    // rattle_correct_params::corrected_ready.  It runs on a library thread with kernels in flight, so it never exits the process: it
+    // writes corrected.fq.tmp and records the outcome
+    static void corrected_ready(void *user, const rattle_read_set_s *S, const uint32_t *) {
+        correct_job *J = (correct_job *)user;
+        cli_timer t("corrected.fq (behind the consensus stages)");
+        if (J->write_set(*S, true, J->corrected_tmp)) J->early_done = true; else J->early_failed = true;
+    }
+    // corrected.fq is formatted and written from the library's corrected_ready callback, while POA #2 / #3 still run on the
+    // device (one device: the sharded job reassembles its reads at the end).  The main thread renames corrected.fq.tmp once
+    // correct_reads has returned 0 (the reference writes its three files only after correct_reads, main.cpp:405-411: a failed run
+    // must not leave a complete-looking corrected.fq) or removes it and reports the failure.
+    void run_library() {
+        cli_timer t("library: correct_reads");
+        if (team.n() == 1) { P.corrected_ready = corrected_ready; P.corrected_ready_user = this; }
+        team.run([&](int r, rattle_ctx *ctx) {                                      // packs sharded over the ranks, result reassembled on rank 0
+            rattle_correction *mine = nullptr, *merged = nullptr;
+            if (want_report) chk(rattle_hip_set_correction_report(ctx, 1));
+            if (want_support) chk(rattle_hip_set_consensus_support(ctx, 1));
+            const int rc = rattle_hip_correct_reads(ctx, cat.data(), qcat.data(), off.data(), (uint32_t)T.n(), (uint32_t)clusters.size(), coff.data(), mid.data(),
+                                                    mrev.data(), &P, &mine);
+            if (rc != 0 && team.n() == 1) unlink(corrected_tmp.c_str());           // no half of a result stays behind
+            chk(rc);
+            if (team.n() == 1) { R = mine; return; }
+            chk(rattle_hip_correction_gather(ctx, mine, 0, &merged));
+            rattle_hip_correction_free(mine);
+            if (r == 0) R = merged;
+        });
+        if (early_failed) { unlink(corrected_tmp.c_str()); die("Error: cannot write " + corrected_path); }
+        if (early_done && rename(corrected_tmp.c_str(), corrected_path.c_str()) != 0) die("Error: cannot write " + corrected_path);
+    }
+    // correct.cpp:453-469: per cluster, how many reads of its packs carry each label.  Only packs that produced a pack consensus
+    // count (as `reads=` does): packs the library skipped (budget rule: listed by their index among ALL packs of the cluster;
+    // POA #1 / #2 beyond the device: by their index among the QUEUED packs) do not
+    std::vector<std::vector<int>> count_labels() const {
+        std::vector<std::vector<int>> counts(clusters.size(), std::vector<int>(labels.size(), 0));
+        if (labels.empty()) return counts;
         std::set<std::pair<int, uint32_t>> skip_all, skip_queued;
         for (uint32_t i = 0; i < R->skipped.n; ++i) {
             if (R->skipped.stage[i] == 0) skip_all.insert({R->skipped.cluster_id[i], R->skipped.pack[i]});
@@ -1045,60 +1038,45 @@ int mode_correct(int argc, char **argv) {
                     size_t p = h.find_first_of(",");
                     std::string rest = p == std::string::npos ? "" : h.substr(p + 1);
                     std::string lab = rest.substr(0, rest.find_first_of(","));
-                    for (size_t l = 0; l < labels.size(); ++l) if (labels[l] == lab) label_counts[c][l]++;
+                    for (size_t l = 0; l < labels.size(); ++l) if (labels[l] == lab) counts[c][l]++;
                 }
             }
         }
+        return counts;
     }
-    for (uint32_t i = 0; i < R->consensi.n; ++i) {
-        int cid = R->consensi.cluster_id[i];
-        std::string lr;
-        for (size_t l = 0; l < labels.size(); ++l) lr += labels[l] + ":" + std::to_string(label_counts[cid][l]) + ",";
-        read_t r;
-        if (gene_mode) r.header = "@gene_cluster_" + std::to_string(cid) + " reads=" + std::to_string(R->consensi.n_reads[i]) + " labels=" + lr;
-        else r.header = "@transcript_cluster_" + std::to_string(cid) + " gene_cluster_" + std::to_string(clusters[cid].main_seq.gene_id) +
-                        " reads=" + std::to_string(R->consensi.n_reads[i]) + " labels=" + lr;
-        r.seq.assign(R->consensi.seq + R->consensi.off[i], R->consensi.seq + R->consensi.off[i + 1]);
-        r.quality.assign(R->consensi.qual + R->consensi.off[i], R->consensi.qual + R->consensi.off[i + 1]);
-        r.ann = "+";
-        consensi.push_back(r);
+    void consensus_headers() {                                                       // correct.cpp:495-549
+        t_out.reset(new cli_timer("format + write outputs"));
+        const std::vector<std::vector<int>> label_counts = count_labels();
+        for (uint32_t i = 0; i < R->consensi.n; ++i) {
+            const int cid = R->consensi.cluster_id[i];
+            std::string lr;
+            for (size_t l = 0; l < labels.size(); ++l) lr += labels[l] + ":" + std::to_string(label_counts[cid][l]) + ",";
+            const std::string name = gene_mode ? "@gene_cluster_" + std::to_string(cid)
+                                               : "@transcript_cluster_" + std::to_string(cid) + " gene_cluster_" + std::to_string(clusters[cid].main_seq.gene_id);
+            consensi.push_back(consensus_record(R->consensi, i, name + " reads=" + std::to_string(R->consensi.n_reads[i]) + " labels=" + lr));
+        }
     }
-    std::cerr << std::endl << "Generating consensi..." << std::endl;
-    if (!early.done && !write_set(R->corrected, true, corrected_path)) die("Error: cannot write " + corrected_path);
-    if (!write_set(R->uncorrected, false, outdir + "/uncorrected.fq")) die("Error: cannot write " + outdir + "/uncorrected.fq");
-    write_fastq_file(consensi, outdir + "/consensi.fq");
-    if (want_report) {
-        // correction_report.tsv: one line per record of corrected.fq, in that file's order
+    // correction_report.tsv: one line per record of corrected.fq, in that file's order
+    std::string correction_report_text() const {
         rattle_correction_report *rp = nullptr;
         chk(rattle_hip_correction_report(R, &rp));
-        const std::string path = outdir + "/correction_report.tsv";
-        std::ofstream f(path);
-        f << "read\tcluster\tin_len\tout_len\ttrim_front\ttrim_back\tmatch\tsubstituted\tmismatch_kept\tinserted\tdeleted\tgap_kept\n";
+        std::string text = "read\tcluster\tin_len\tout_len\ttrim_front\ttrim_back\tmatch\tsubstituted\tmismatch_kept\tinserted\tdeleted\tgap_kept\n";
         for (uint32_t i = 0; i < rp->n; ++i) {
-            const span &h = T.header[(uint32_t)R->corrected.read_id[i]];             // the id: the header's first token, without its '@' / '>'
-            const char *b = h.p, *e = h.p + h.n;
-            if (b < e && (*b == '@' || *b == '>')) ++b;
-            const char *t = b;
-            while (t < e && *t != ' ' && *t != '\t') ++t;
-            f.write(b, t - b);
-            f << "\t" << R->corrected.cluster_id[i] << "\t" << rp->in_len[i] << "\t" << rp->out_len[i] << "\t" << rp->trim_front[i] << "\t" << rp->trim_back[i]
-              << "\t" << rp->match[i] << "\t" << rp->substituted[i] << "\t" << rp->mismatch_kept[i] << "\t" << rp->inserted[i] << "\t" << rp->deleted[i]
-              << "\t" << rp->gap_kept[i] << "\n";
+            text += record_name(T.header[(uint32_t)R->corrected.read_id[i]]) + "\t" + std::to_string(R->corrected.cluster_id[i]);
+            for (const uint32_t *v : {rp->in_len, rp->out_len, rp->trim_front, rp->trim_back, rp->match, rp->substituted, rp->mismatch_kept, rp->inserted,
+                                      rp->deleted, rp->gap_kept})
+                text += "\t" + std::to_string(v[i]);
+            text += "\n";
         }
         rattle_hip_correction_report_free(rp);
-        f.close();
-        if (!f) die("Error: cannot write " + path);
+        return text;
     }
-    if (want_support) {
-        // consensus_support.tsv: one line per record of consensi.fq, in that file's order
+    // consensus_support.tsv: one line per record of consensi.fq, in that file's order
+    std::string consensus_support_text() const {
         rattle_consensus_support *sp = nullptr;
         chk(rattle_hip_consensus_support(R, &sp));
-        const std::string path = outdir + "/consensus_support.tsv";
-        std::ofstream f(path);
-        f << "consensus\tlength\tlevel\treads\tmin_ratio\tweak\tsupport\tdepth\n";
+        std::string text = "consensus\tlength\tlevel\treads\tmin_ratio\tweak\tsupport\tdepth\n";
         for (uint32_t i = 0; i < sp->n; ++i) {
-            const std::string &h = consensi[i].header;                                  // the name: the header's first token, without its '@'
-            const size_t b = !h.empty() && h[0] == '@' ? 1 : 0;
             const uint64_t p0 = sp->off[i], p1 = sp->off[i + 1];
             double min_ratio = 0.0;
             uint64_t weak = 0;
@@ -1107,33 +1085,50 @@ int mode_correct(int argc, char **argv) {
                 if (p == p0 || ratio < min_ratio) min_ratio = ratio;
                 weak += 2ull * sp->support[p] <= sp->depth[p];
             }
-            char num[64];
-            snprintf(num, sizeof(num), "%.17g", min_ratio);
-            f << h.substr(b, h.find_first_of(" \t") - b) << "\t" << (p1 - p0) << "\t" << (int)sp->level[i] << "\t" << R->consensi.n_reads[i] << "\t" << num << "\t" << weak;
-            for (int which = 0; which < 2; ++which) {
-                const uint32_t *v = which ? sp->depth : sp->support;
-                f << "\t";
-                for (uint64_t p = p0; p < p1; ++p) { if (p > p0) f << ","; f << v[p]; }
+            text += record_name(consensi[i].header) + "\t" + std::to_string(p1 - p0) + "\t" + std::to_string((int)sp->level[i]) + "\t" +
+                    std::to_string(R->consensi.n_reads[i]) + "\t" + g17(min_ratio) + "\t" + std::to_string(weak);
+            for (const uint32_t *v : {sp->support, sp->depth}) {
+                text += "\t";
+                for (uint64_t p = p0; p < p1; ++p) { if (p > p0) text += ","; text += std::to_string(v[p]); }
             }
-            f << "\n";
+            text += "\n";
         }
         rattle_hip_consensus_support_free(sp);
-        f.close();
-        if (!f) die("Error: cannot write " + path);
+        return text;
     }
-    if (R->skipped.n) {
-        // packs whose POA did not fit the device (or the --max-pack-cells budget): their reads are in uncorrected.fq
-        std::ofstream f(outdir + "/skipped_packs.tsv");
-        f << "cluster\tpack\tstage\treads\n";
+    // skipped_packs.tsv: packs whose POA did not fit the device (or the --max-pack-cells budget): their reads are in uncorrected.fq
+    std::string skipped_packs_text() const {
+        std::string text = "cluster\tpack\tstage\treads\n";
         for (uint32_t i = 0; i < R->skipped.n; ++i)
-            f << R->skipped.cluster_id[i] << "\t" << R->skipped.pack[i] << "\t" << R->skipped.stage[i] << "\t"
-              << (R->skipped.read_off[i + 1] - R->skipped.read_off[i]) << "\n";
-        std::cerr << R->skipped.n << " pack(s) with " << R->counters[4] << " reads were not corrected (DP beyond the device or the budget): skipped_packs.tsv" << std::endl;
+            text += std::to_string(R->skipped.cluster_id[i]) + "\t" + std::to_string(R->skipped.pack[i]) + "\t" + std::to_string(R->skipped.stage[i]) + "\t" +
+                    std::to_string(R->skipped.read_off[i + 1] - R->skipped.read_off[i]) + "\n";
+        return text;
     }
-    t_out.reset();
-    std::cerr << "Done" << std::endl;
-    rattle_hip_correction_free(R);
-    team.close();
+    void write_outputs() {
+        std::cerr << std::endl << "Generating consensi..." << std::endl;
+        if (!early_done && !write_set(R->corrected, true, corrected_path)) die("Error: cannot write " + corrected_path);
+        if (!write_set(R->uncorrected, false, outdir + "/uncorrected.fq")) die("Error: cannot write " + outdir + "/uncorrected.fq");
+        write_fastq_file(consensi, outdir + "/consensi.fq");
+        if (want_report) write_text(outdir + "/correction_report.tsv", correction_report_text());
+        if (want_support) write_text(outdir + "/consensus_support.tsv", consensus_support_text());
+        if (R->skipped.n) {
+            write_text(outdir + "/skipped_packs.tsv", skipped_packs_text());
+            std::cerr << R->skipped.n << " pack(s) with " << R->counters[4] << " reads were not corrected (DP beyond the device or the budget): skipped_packs.tsv" << std::endl;
+        }
+        t_out.reset();
+        std::cerr << "Done" << std::endl;
+        rattle_hip_correction_free(R);
+        team.close();
+    }
+};
+
+int mode_correct(int argc, char **argv) {
+    correct_job J;
+    J.options(argc, argv);
+    J.read_input();
+    J.run_library();
+    J.consensus_headers();
+    J.write_outputs();
     return EXIT_SUCCESS;
 }
 
@@ -1205,114 +1200,121 @@ int mode_extract_clusters(int argc, char **argv) {
     return EXIT_SUCCESS;
 }
 
-// `rattle polish`, /root/reference/main.cpp:612-762: cluster the consensi (k=6, 0.5, 25, bv 0.4/0.4 so
-// no merge pass), correct with min_reads=0, rewrite the consensus headers.
-int mode_polish(int argc, char **argv) {
-    std::vector<opt_def> defs = {
-        {"help", {"-h", "--help"}, false}, {"input", {"-i", "--input"}, true}, {"output", {"-o", "--output-folder"}, true},
-        {"label", {"-l", "--label"}, true}, {"threads", {"-t", "--threads"}, true}, {"rna", {"--rna"}, false},
-        {"verbose", {"--verbose"}, false}, {"summary", {"--summary"}, false}, {"device", {"--device"}, true}};
-    args_t a = parse(argc, argv, defs);
-    if (a.has("help")) { std::cerr << "rattle polish -i consensi.fq [-o dir] [--rna] [--summary]\n"; return EXIT_SUCCESS; }
-    if (!a.has("input")) die("ERROR: No input file provided");
-    std::cerr << "Reading fasta file... ";
-    std::string in = a.str("input", "");
-    if (access(in.c_str(), F_OK)) die("\nError: Input file not found! \n");
-    read_set_t reads;
-    for_each_record(in, true, [&](const std::string &h, const std::string &s, const std::string &an, const std::string &q) {
-        reads.push_back(read_t{h, s, an, q});
-    });
-    std::stable_sort(reads.begin(), reads.end(), [](const read_t &x, const read_t &y) { return x.seq.size() > y.seq.size(); });
-    std::cerr << "Done" << std::endl;
-    const bool is_rna = a.has("rna"), summary = a.has("summary");
-    std::vector<std::string> labels = split_string(a.str("label", ""), ',');
-    std::cerr << "Clustering consensus sequences..." << std::endl;
+// ---- `rattle polish`, main.cpp:612-762 ----------------------------------------------------------------------------------------
+// Cluster the consensi (k=6, 0.5, 25, bv 0.4/0.4 so no merge pass), correct with min_reads=0, rewrite the consensus headers.
+struct polish_job {
+    args_t a;
+    bool is_rna = false, summary = false;
+    std::vector<std::string> labels;
+    read_set_t reads, out;                        // the input consensi, longest first; the records of transcriptome.fq
+    std::string cat, qcat;                        // their bases and qualities (padded with '!' / cut to the sequence length)
+    std::vector<uint64_t> off{0};
     rattle_ctx *ctx = nullptr;
-    chk(rattle_hip_ctx_create(a.i("device", 0), &ctx));
-    rattle_cluster_params P;
-    P.t_s = 0.5; P.t_v = 25; P.bv_threshold = 0.4; P.min_bv_threshold = 0.4; P.bv_falloff = 0.05;
-    P.min_reads_cluster = 0; P.use_hc = 0; P.repr_percentile = 0.15; P.is_rna = is_rna ? 1 : 0;
-    load(ctx, reads, 6, !is_rna);
-    rattle_cluster_set *raw = nullptr;
-    chk(rattle_hip_cluster_reads(ctx, &P, &raw));
-    cluster_set_t clusters = to_set(raw);
-
-    std::string cat, qcat;
-    std::vector<uint64_t> off(1, 0);
-    for (auto &r : reads) {
-        cat += r.seq;
-        std::string q = r.quality;
-        q.resize(r.seq.size(), '!');
-        qcat += q;
-        off.push_back(cat.size());
-    }
-    std::vector<uint32_t> coff(1, 0);
-    std::vector<int32_t> mid;
-    std::vector<uint8_t> mrev;
-    for (auto &c : clusters) {
-        for (auto &s : c.seqs) { mid.push_back(s.seq_id); mrev.push_back(s.rev ? 1 : 0); }
-        coff.push_back((uint32_t)mid.size());
-    }
-    rattle_correct_params CP;
-    memset(&CP, 0, sizeof(CP));
-    CP.min_occ = 0.3; CP.gap_occ = 0.3; CP.err_ratio = 30.0; CP.split = 200; CP.min_reads = 0; CP.n_threads = 0;
+    cluster_set_t clusters;
     rattle_correction *R = nullptr;
-    chk(rattle_hip_correct_reads(ctx, (const uint8_t *)cat.data(), (const uint8_t *)qcat.data(), off.data(), (uint32_t)reads.size(),
-                                 (uint32_t)clusters.size(), coff.data(), mid.data(), mrev.data(), &CP, &R));
-    read_set_t out;
-    std::vector<std::string> summary_results;
-    std::map<int, int> gene_map;
-    int gid = -1;
-    for (uint32_t i = 0; i < R->consensi.n; ++i) {
-        const int cid = R->consensi.cluster_id[i];           // == i: every cluster has a pack with min_reads = 0
-        int total_reads = 0;
-        std::vector<int> label_counts(labels.size(), 0);
-        for (auto &m : clusters[cid].seqs) {
-            const std::string &h = reads[m.seq_id].header;
-            auto info = split_string(h, '=');
-            total_reads += std::stoi(info.at(1));
-            for (size_t l = 0; l < labels.size(); ++l) {
-                size_t idx = h.find(labels[l]);
-                if (idx != std::string::npos) {
-                    std::string sub = h.substr(idx + 1);
-                    label_counts[l] += std::stoi(sub.substr(sub.find_first_of(":") + 1));
+    std::string summary_text;                     // polish_summary.tsv: one line per input consensus
+    void options(int argc, char **argv) {
+        a = parse(argc, argv, {
+            {"help", {"-h", "--help"}, false}, {"input", {"-i", "--input"}, true}, {"output", {"-o", "--output-folder"}, true},
+            {"label", {"-l", "--label"}, true}, {"threads", {"-t", "--threads"}, true}, {"rna", {"--rna"}, false},
+            {"verbose", {"--verbose"}, false}, {"summary", {"--summary"}, false}, {"device", {"--device"}, true}});
+        if (a.has("help")) { std::cerr << "rattle polish -i consensi.fq [-o dir] [--rna] [--summary]\n"; exit(EXIT_SUCCESS); }
+        if (!a.has("input")) die("ERROR: No input file provided");
+        is_rna = a.has("rna"); summary = a.has("summary");
+        labels = split_string(a.str("label", ""), ',');
+    }
+    void read_input() {
+        std::cerr << "Reading fasta file... ";
+        const std::string in = a.str("input", "");
+        if (access(in.c_str(), F_OK)) die("\nError: Input file not found! \n");
+        for_each_fastq_record(in, [&](const std::string &h, const std::string &s, const std::string &an, const std::string &q) {
+            reads.push_back(read_t{h, s, an, q});
+        });
+        std::stable_sort(reads.begin(), reads.end(), [](const read_t &x, const read_t &y) { return x.seq.size() > y.seq.size(); });
+        for (auto &r : reads) {
+            cat += r.seq;
+            std::string q = r.quality; q.resize(r.seq.size(), '!'); qcat += q;
+            off.push_back(cat.size());
+        }
+        std::cerr << "Done" << std::endl;
+    }
+    void cluster() {
+        std::cerr << "Clustering consensus sequences..." << std::endl;
+        chk(rattle_hip_ctx_create(a.i("device", 0), &ctx));
+        rattle_cluster_params P = default_cluster_params();
+        P.t_s = 0.5; P.t_v = 25; P.min_bv_threshold = 0.4; P.is_rna = is_rna ? 1 : 0;
+        chk(rattle_hip_load_reads(ctx, (const uint8_t *)cat.data(), off.data(), (uint32_t)reads.size(), 6, is_rna ? 0 : 1));
+        rattle_cluster_set *raw = nullptr;
+        chk(rattle_hip_cluster_reads(ctx, &P, &raw));
+        clusters = to_set(raw);
+    }
+    void correct() {
+        std::vector<uint32_t> coff;
+        std::vector<int32_t> mid;
+        std::vector<uint8_t> mrev;
+        flatten_members(clusters, coff, mid, mrev);
+        rattle_correct_params P = default_correct_params();
+        P.min_reads = 0;
+        chk(rattle_hip_correct_reads(ctx, (const uint8_t *)cat.data(), (const uint8_t *)qcat.data(), off.data(), (uint32_t)reads.size(),
+                                     (uint32_t)clusters.size(), coff.data(), mid.data(), mrev.data(), &P, &R));
+    }
+    // main.cpp:690-755: a new consensus sums `reads=` and the label counts of the inputs it was made from.  Made from transcript-level
+    // inputs it is one itself, and its gene follows the reference's gene_map: a member whose gene cluster is new maps that gene cluster
+    // to the gene the record has so far (its own, if it has none), a member whose gene cluster was met before gives the record the
+    // gene it maps to
+    void rewrite_headers() {
+        std::map<int, int> gene_map;
+        for (uint32_t i = 0; i < R->consensi.n; ++i) {
+            const int cid = R->consensi.cluster_id[i];           // == i: every cluster has a pack with min_reads = 0
+            int gid = -1, total_reads = 0;
+            std::vector<int> label_counts(labels.size(), 0);
+            for (auto &m : clusters[cid].seqs) {
+                const std::string &h = reads[m.seq_id].header;
+                total_reads += std::stoi(split_string(h, '=').at(1));
+                for (size_t l = 0; l < labels.size(); ++l) {
+                    size_t idx = h.find(labels[l]);
+                    if (idx != std::string::npos) {
+                        std::string sub = h.substr(idx + 1);
+                        label_counts[l] += std::stoi(sub.substr(sub.find_first_of(":") + 1));
+                    }
+                }
+                auto info_c = split_string(h, '_');
+                if (h.find("transcript_cluster") != std::string::npos) {
+                    const int id = std::stoi(info_c.at(4));
+                    if (gene_map.find(id) == gene_map.end()) { if (gid == -1) gid = id; gene_map.insert({id, gid}); }
+                    else gid = gene_map.find(id)->second;
+                    if (summary) summary_text += "transcript_cluster_" + std::to_string(std::stoi(info_c.at(2))) + ", gene_cluster_" + std::to_string(id) +
+                                                 ", new_cluster_" + std::to_string(cid) + "\n";
+                } else if (summary) {
+                    summary_text += "gene_cluster_" + std::to_string(std::stoi(info_c.at(2))) + ", new_cluster_" + std::to_string(cid) + "\n";
                 }
             }
-            auto info_c = split_string(h, '_');
-            if (h.find("transcript_cluster") != std::string::npos) {
-                int id = std::stoi(info_c.at(4));
-                if (gene_map.find(id) == gene_map.end()) { if (gid == -1) gid = id; gene_map.insert({id, gid}); }
-                else gid = gene_map.find(id)->second;
-                if (summary) summary_results.push_back("transcript_cluster_" + std::to_string(std::stoi(info_c.at(2))) + ", gene_cluster_" +
-                                                       std::to_string(id) + ", new_cluster_" + std::to_string(cid));
-            } else if (summary) {
-                summary_results.push_back("gene_cluster_" + std::to_string(std::stoi(info_c.at(2))) + ", new_cluster_" + std::to_string(cid));
-            }
+            const std::string rcount = std::to_string(R->consensi.n_reads[i]);       // the "reads=" field correct_reads writes (correct.cpp:542)
+            std::string header = gid != -1 ? "@transcript_cluster_" + std::to_string(cid) + " gene_cluster_" + std::to_string(gid) + " generated_from_transcript_clusters=" + rcount
+                                           : "@cluster_" + std::to_string(cid) + " generated_from_consensi_clusters=" + rcount;
+            header += " total_reads=" + std::to_string(total_reads) + " labels=";
+            for (size_t l = 0; l < labels.size(); ++l) header += labels[l] + ":" + std::to_string(label_counts[l]) + ",";
+            out.push_back(consensus_record(R->consensi, i, header));
         }
-        const int rcount = R->consensi.n_reads[i];           // the "reads=" field correct_reads writes (correct.cpp:542)
-        read_t r;
-        if (gid != -1)
-            r.header = "@transcript_cluster_" + std::to_string(cid) + " gene_cluster_" + std::to_string(gid) + " generated_from_transcript_clusters=" +
-                       std::to_string(rcount) + " total_reads=" + std::to_string(total_reads) + " labels=";
-        else
-            r.header = "@cluster_" + std::to_string(cid) + " generated_from_consensi_clusters=" + std::to_string(rcount) + " total_reads=" +
-                       std::to_string(total_reads) + " labels=";
-        for (size_t l = 0; l < labels.size(); ++l) r.header += labels[l] + ":" + std::to_string(label_counts[l]) + ",";
-        r.seq.assign(R->consensi.seq + R->consensi.off[i], R->consensi.seq + R->consensi.off[i + 1]);
-        r.quality.assign(R->consensi.qual + R->consensi.off[i], R->consensi.qual + R->consensi.off[i + 1]);
-        r.ann = "+";
-        out.push_back(r);
-        gid = -1;
     }
-    const std::string outdir = a.str("output", ".");
-    if (summary) {
-        std::ofstream f(outdir + "/polish_summary.tsv");
-        for (auto &l : summary_results) f << l << "\n";
+    void write() {
+        const std::string outdir = a.str("output", ".");
+        if (summary) write_text(outdir + "/polish_summary.tsv", summary_text);
+        write_fastq_file(out, outdir + "/transcriptome.fq");
+        rattle_hip_correction_free(R);
+        rattle_hip_ctx_destroy(ctx);
+        std::cerr << "Done" << std::endl;
     }
-    write_fastq_file(out, outdir + "/transcriptome.fq");
-    rattle_hip_correction_free(R);
-    rattle_hip_ctx_destroy(ctx);
-    std::cerr << "Done" << std::endl;
+};
+
+int mode_polish(int argc, char **argv) {
+    polish_job J;
+    J.options(argc, argv);
+    J.read_input();
+    J.cluster();
+    J.correct();
+    J.rewrite_headers();
+    J.write();
     return EXIT_SUCCESS;
 }
 
@@ -1320,17 +1322,14 @@ int mode_polish(int argc, char **argv) {
 
 int main(int argc, char **argv) {
     setenv("GPU_MAX_HW_QUEUES", "12", 0);      // before the HIP runtime starts: the POA column classes of a pass run concurrently, one hardware queue each (poa.hip)
-    if (argc < 2) {
-        std::cout << "Run with mode: ./rattle <cluster|cluster_summary|extract_clusters|correct|polish|assign>" << std::endl;
-        return EXIT_FAILURE;
-    }
+    const char *mode = argc < 2 ? "" : argv[1];
     try {
-        if (!strcmp(argv[1], "cluster")) return mode_cluster(argc, argv);
-        if (!strcmp(argv[1], "correct")) return mode_correct(argc, argv);
-        if (!strcmp(argv[1], "polish")) return mode_polish(argc, argv);
-        if (!strcmp(argv[1], "assign")) return mode_assign(argc, argv);
-        if (!strcmp(argv[1], "cluster_summary")) return mode_cluster_summary(argc, argv);
-        if (!strcmp(argv[1], "extract_clusters")) return mode_extract_clusters(argc, argv);
+        if (!strcmp(mode, "cluster")) return mode_cluster(argc, argv);
+        if (!strcmp(mode, "correct")) return mode_correct(argc, argv);
+        if (!strcmp(mode, "polish")) return mode_polish(argc, argv);
+        if (!strcmp(mode, "assign")) return mode_assign(argc, argv);
+        if (!strcmp(mode, "cluster_summary")) return mode_cluster_summary(argc, argv);
+        if (!strcmp(mode, "extract_clusters")) return mode_extract_clusters(argc, argv);
     } catch (const std::exception &e) {
         std::cerr << e.what() << std::endl;
         return EXIT_FAILURE;
