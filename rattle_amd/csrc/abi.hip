@@ -324,73 +324,8 @@ int rattle_hip_cluster_subsets(rattle_ctx *c, const rattle_cluster_params *P, co
     // cluster.cpp:42: `if (is_rna) return {-1,false}` comes before the reverse test, so a both-strand index would over-cluster
     if (P->is_rna && c->idx.both) { set_error("--rna mode needs the reads loaded with both_strands=0"); return RATTLE_ERR_STATE; }
     RT_HIP(hipStreamSynchronize(c->stream));
-    // several ranks: the subsets (gene clusters, main.cpp:281-318) are independent -> LPT over ranks by the
-    // pair count proxy n^2, every rank clusters its own and the results are all-gathered at the end
-    const int R = c->xchg.nranks, rk = c->xchg.rank;
-    std::vector<uint32_t> owner(n_subsets, 0);
-    if (R > 1) {
-        std::vector<uint64_t> cost(n_subsets);
-        for (uint32_t i = 0; i < n_subsets; ++i) { const uint64_t n = sub_off[i + 1] - sub_off[i]; cost[i] = n * n; }
-        lpt_assign(cost, R, owner);
-    }
-    std::vector<uint32_t> order;                                  // my subsets, largest first
-    for (uint32_t i = 0; i < n_subsets; ++i) if ((int)owner[i] == rk) order.push_back(i);
-    std::sort(order.begin(), order.end(), [&](uint32_t a, uint32_t b) {
-        const uint64_t la = sub_off[a + 1] - sub_off[a], lb = sub_off[b + 1] - sub_off[b];
-        return la != lb ? la > lb : a < b;
-    });
     (void)n_workers;                                              // round 1 ran one host thread per worker; the subsets now advance in lockstep
-    int rc = cluster_driver_many(c, P, ids, sub_off, order.data(), (uint32_t)order.size(), outs);
-    std::string err_msg = rc != 0 ? rattle_hip_last_error() : "";
-    if (rc != 0) for (uint32_t i : order) { rattle_hip_cluster_set_free(outs[i]); outs[i] = nullptr; }
-    if (R > 1) {
-        // all ranks take part in the exchange even after a local failure (an empty payload marks it)
-        std::vector<uint8_t> mine;
-        auto put = [&mine](const void *p, size_t n) { const size_t at = mine.size(); mine.resize(at + n); if (n) memcpy(mine.data() + at, p, n); };
-        if (rc == 0)
-            for (uint32_t i : order) {
-                const rattle_cluster_set *cs = outs[i];
-                const uint32_t hdr[3] = {i, cs->n_clusters, cs->offsets[cs->n_clusters]};
-                put(hdr, 12); put(cs->counters, 64);
-                put(cs->main_id, (size_t)hdr[1] * 4); put(cs->offsets, ((size_t)hdr[1] + 1) * 4); put(cs->member_id, (size_t)hdr[2] * 4);
-                put(cs->main_rev, hdr[1]); put(cs->member_rev, hdr[2]);
-                const uint8_t z[4] = {0, 0, 0, 0};
-                put(z, (4 - (hdr[1] + hdr[2]) % 4) % 4);
-            }
-        else { const uint32_t bad = 0xFFFFFFFFu; put(&bad, 4); }
-        std::vector<std::vector<uint8_t>> all;
-        int xrc = xchg_allgatherv(c, mine, all);
-        if (rc == 0) rc = xrc;
-        for (int r = 0; r < R && rc == 0; ++r) {
-            if (r == rk) continue;
-            const std::vector<uint8_t> &b = all[r];
-            if (b.size() == 4) { set_error("cluster_subsets failed on rank " + std::to_string(r)); rc = RATTLE_ERR_HIP; break; }
-            size_t at = 0;
-            while (at + 12 <= b.size()) {
-                uint32_t hdr[3];
-                memcpy(hdr, b.data() + at, 12); at += 12;
-                if (hdr[0] >= n_subsets || outs[hdr[0]]) { set_error("cluster_subsets exchange: malformed record"); rc = RATTLE_ERR_HIP; break; }
-                rattle_cluster_set *cs = new_cluster_set();
-                cs->n_clusters = hdr[1];
-                memcpy(cs->counters, b.data() + at, 64); at += 64;
-                cs->main_id = (int32_t *)malloc(std::max<size_t>(1, hdr[1]) * 4); cs->offsets = (uint32_t *)malloc(((size_t)hdr[1] + 1) * 4);
-                cs->member_id = (int32_t *)malloc(std::max<size_t>(1, hdr[2]) * 4);
-                cs->main_rev = (uint8_t *)malloc(std::max<size_t>(1, hdr[1])); cs->member_rev = (uint8_t *)malloc(std::max<size_t>(1, hdr[2]));
-                memcpy(cs->main_id, b.data() + at, (size_t)hdr[1] * 4); at += (size_t)hdr[1] * 4;
-                memcpy(cs->offsets, b.data() + at, ((size_t)hdr[1] + 1) * 4); at += ((size_t)hdr[1] + 1) * 4;
-                memcpy(cs->member_id, b.data() + at, (size_t)hdr[2] * 4); at += (size_t)hdr[2] * 4;
-                memcpy(cs->main_rev, b.data() + at, hdr[1]); at += hdr[1];
-                memcpy(cs->member_rev, b.data() + at, hdr[2]); at += hdr[2];
-                at += (4 - (hdr[1] + hdr[2]) % 4) % 4;
-                outs[hdr[0]] = cs;
-            }
-        }
-    }
-    if (rc != 0) {
-        for (uint32_t i = 0; i < n_subsets; ++i) { rattle_hip_cluster_set_free(outs[i]); outs[i] = nullptr; }
-        return rc;
-    }
-    return 0;
+    return cluster_subsets_ranked(c, P, ids, sub_off, n_subsets, outs);
 }
 
 int rattle_hip_stage_reads(rattle_ctx *c, const uint8_t *seq, const uint8_t *qual, const uint64_t *off, uint32_t n) {

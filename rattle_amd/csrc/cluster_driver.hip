@@ -27,6 +27,7 @@
 #include <cstring>
 
 #include "common.h"
+#include "wire.h"
 
 namespace rattle {
 
@@ -283,25 +284,25 @@ struct evaluator {
     // (seed, candidate position, strand) triples.  A rank that scored the candidates at positions r, r + R, ... gives its stride and
     // offset, so that the positions are the whole request's; the whole request itself takes (1, 0).
     static std::vector<uint8_t> pack_piece(const uint64_t *counters, const uint64_t *before, const std::vector<hit_t> &hits, uint32_t R, uint32_t r) {
-        std::vector<uint8_t> pay(24 + hits.size() * 12);
-        for (int i = 0; i < 3; ++i) { const uint64_t d = counters[i] - before[i]; memcpy(pay.data() + 8 * i, &d, 8); }
-        for (size_t i = 0; i < hits.size(); ++i) {
-            const uint32_t t[3] = {hits[i].seed, hits[i].cand * R + r, hits[i].rev};
-            memcpy(pay.data() + 24 + 12 * i, t, 12);
-        }
+        const uint64_t deltas[3] = {counters[0] - before[0], counters[1] - before[1], counters[2] - before[2]};
+        std::vector<wire_hit> t(hits.size());
+        for (size_t i = 0; i < hits.size(); ++i) t[i] = wire_hit{hits[i].seed, hits[i].cand * R + r, hits[i].rev};
+        std::vector<uint8_t> pay;
+        write_hit_list(pay, deltas, t.data(), t.size());
         return pay;
     }
 
-    // ... and a piece read back: its deltas added to counters (unless nullptr), its hits appended, except those at the candidate
-    // positions drop, drop + R, ... (drop < 0: none)
-    static int unpack_piece(const std::vector<uint8_t> &b, uint64_t *counters, std::vector<hit_t> &hits, uint32_t R, int drop) {
-        if (b.size() < 24 || (b.size() - 24) % 12) { set_error("cluster exchange: malformed hit list"); return RATTLE_ERR_HIP; }
-        if (counters) for (int i = 0; i < 3; ++i) { uint64_t d; memcpy(&d, b.data() + 8 * i, 8); counters[i] += d; }
-        for (size_t at = 24; at < b.size(); at += 12) {
-            uint32_t t[3];
-            memcpy(t, b.data() + at, 12);
-            if (drop >= 0 && t[1] % R == (uint32_t)drop) continue;
-            hits.push_back(hit_t{t[0], t[1], (uint8_t)t[2]});
+    // ... and the piece of rank `from` read back and checked against the request it answers: its deltas added to counters (unless
+    // nullptr), its hits appended, except those at the candidate positions drop, drop + R, ... (drop < 0: none)
+    static int unpack_piece(const std::vector<uint8_t> &b, int from, const request &q, uint64_t *counters, std::vector<hit_t> &hits, uint32_t R, int drop) {
+        wire_reader W(b.data(), b.size());
+        hit_list_view V;
+        if (!parse_hit_list(W, q.seeds.size(), q.cands.size(), V)) { set_error(wire_error("cluster hit exchange", from, W)); return RATTLE_ERR_HIP; }
+        if (counters) for (int i = 0; i < 3; ++i) counters[i] += V.deltas[i];
+        for (size_t i = 0; i < V.n; ++i) {
+            const wire_hit &t = V.hits[i];
+            if (drop >= 0 && t.cand % R == (uint32_t)drop) continue;
+            hits.push_back(hit_t{t.seed, t.cand, (uint8_t)t.rev});
         }
         return 0;
     }
@@ -335,7 +336,7 @@ struct evaluator {
             const std::vector<uint8_t> &b = all[(size_t)p];
             if (replay && b.empty()) continue;
             // replaying: this rank's own counters and hits arrived in its own piece
-            RT_TRY(unpack_piece(b, replay && p == r ? nullptr : q.counters, q.hits, (uint32_t)R, replay && p != r ? r : -1));
+            RT_TRY(unpack_piece(b, p, q, replay && p == r ? nullptr : q.counters, q.hits, (uint32_t)R, replay && p != r ? r : -1));
         }
         return 0;
     }
@@ -1019,6 +1020,67 @@ int cluster_driver_many(rattle_ctx *ctx, const rattle_cluster_params *P, const u
     }
     RT_TRY(run_jobs(ctx, P, jobs, false));
     for (uint32_t i = 0; i < n_which; ++i) outs[which[i]] = jobs[i].flatten();
+    return 0;
+}
+
+// cluster_driver_many as one job over the ranks of the context: the subsets (gene clusters, main.cpp:281-318) are independent -> LPT
+// over ranks by the pair count proxy n^2, every rank clusters its own, largest first, and the sets are all-gathered at the end
+// (wire.h: the cluster sets).  All ranks take part in the exchange even after a local failure, which their piece then announces.
+// Every outs[i] is a set on return, or on error none is.
+int cluster_subsets_ranked(rattle_ctx *ctx, const rattle_cluster_params *P, const uint32_t *ids, const uint64_t *sub_off, uint32_t n_subsets,
+                           rattle_cluster_set **outs) {
+    const int R = ctx->xchg.nranks, rk = ctx->xchg.rank;
+    std::vector<uint32_t> owner(n_subsets, 0);
+    if (R > 1) {
+        std::vector<uint64_t> cost(n_subsets);
+        for (uint32_t i = 0; i < n_subsets; ++i) { const uint64_t n = sub_off[i + 1] - sub_off[i]; cost[i] = n * n; }
+        lpt_assign(cost, R, owner);
+    }
+    std::vector<uint32_t> order;                                  // my subsets, largest first
+    for (uint32_t i = 0; i < n_subsets; ++i) if ((int)owner[i] == rk) order.push_back(i);
+    std::sort(order.begin(), order.end(), [&](uint32_t a, uint32_t b) {
+        const uint64_t la = sub_off[a + 1] - sub_off[a], lb = sub_off[b + 1] - sub_off[b];
+        return la != lb ? la > lb : a < b;
+    });
+    auto give_up = [&](int rc) {
+        for (uint32_t i = 0; i < n_subsets; ++i) { rattle_hip_cluster_set_free(outs[i]); outs[i] = nullptr; }
+        return rc;
+    };
+    int rc = cluster_driver_many(ctx, P, ids, sub_off, order.data(), (uint32_t)order.size(), outs);
+    if (R == 1) return rc ? give_up(rc) : 0;
+    const std::string local_msg = rc ? rattle_hip_last_error() : "";
+    std::vector<uint8_t> mine;
+    if (rc == 0) for (uint32_t i : order) write_cluster_set(mine, i, *outs[i]);
+    else write_cluster_sets_failure(mine);
+    std::vector<std::vector<uint8_t>> all;
+    const int xrc = xchg_allgatherv(ctx, mine, all);
+    if (rc) { set_error(local_msg); return give_up(rc); }
+    if (xrc) return give_up(xrc);
+    std::vector<uint8_t> seen(n_subsets, 0);
+    std::vector<cluster_set_view> sets;
+    for (int r = 0; r < R; ++r) {
+        if (r == rk) continue;
+        const std::vector<uint8_t> &b = all[(size_t)r];
+        if (is_cluster_sets_failure(b.data(), b.size())) { set_error("cluster_subsets failed on rank " + std::to_string(r)); return give_up(RATTLE_ERR_HIP); }
+        wire_reader W(b.data(), b.size());
+        sets.clear();
+        if (!parse_cluster_sets(W, n_subsets, sub_off, owner.data(), (uint32_t)r, seen, sets)) { set_error(wire_error("cluster_subsets exchange", r, W)); return give_up(RATTLE_ERR_HIP); }
+        for (const cluster_set_view &V : sets) {
+            rattle_cluster_set *cs = new_cluster_set();
+            const size_t nc = V.n_clusters, nm = V.n_members;
+            cs->n_clusters = V.n_clusters;
+            memcpy(cs->counters, V.counters, sizeof(V.counters));
+            cs->main_id = (int32_t *)malloc(std::max<size_t>(1, nc) * 4); cs->offsets = (uint32_t *)malloc((nc + 1) * 4);
+            cs->member_id = (int32_t *)malloc(std::max<size_t>(1, nm) * 4);
+            cs->main_rev = (uint8_t *)malloc(std::max<size_t>(1, nc)); cs->member_rev = (uint8_t *)malloc(std::max<size_t>(1, nm));
+            memcpy(cs->offsets, V.offsets, (nc + 1) * 4);
+            if (nc) { memcpy(cs->main_id, V.main_id, nc * 4); memcpy(cs->main_rev, V.main_rev, nc); }
+            if (nm) { memcpy(cs->member_id, V.member_id, nm * 4); memcpy(cs->member_rev, V.member_rev, nm); }
+            outs[V.subset] = cs;
+        }
+    }
+    // (every piece held exactly its rank's subsets, so with this rank's own every subset is here once)
+    for (uint32_t i = 0; i < n_subsets; ++i) if (!outs[i]) { set_error("cluster_subsets exchange: subset " + std::to_string(i) + " never arrived"); return give_up(RATTLE_ERR_HIP); }
     return 0;
 }
 

@@ -493,6 +493,9 @@ int launch_post_msa(rattle_ctx *ctx, const post_args &A, uint32_t n_packs, int m
 // cluster_driver.cpp
 int cluster_driver_many(rattle_ctx *ctx, const rattle_cluster_params *P, const uint32_t *ids, const uint64_t *sub_off,
                         const uint32_t *which, uint32_t n_which, rattle_cluster_set **outs);
+// ... all n_subsets of them, shared out over the ranks of the context and their sets exchanged: outs[i] for every subset, or none on error
+int cluster_subsets_ranked(rattle_ctx *ctx, const rattle_cluster_params *P, const uint32_t *ids, const uint64_t *sub_off, uint32_t n_subsets,
+                           rattle_cluster_set **outs);
 int cluster_driver(rattle_ctx *ctx, const rattle_cluster_params *P, const uint32_t *subset, uint32_t n_subset,
                    rattle_cluster_set **out);
 int debug_evaluate(rattle_ctx *ctx, const rattle_cluster_params *P, int count_mode, const rattle_debug_rect *R, uint32_t n_rects,

@@ -37,6 +37,7 @@
 #include <thread>
 
 #include "common.h"
+#include "wire.h"
 
 namespace rattle {
 
@@ -352,14 +353,6 @@ int fetch_consensi(rattle_ctx *ctx, cons_stage &C) {
     return 0;
 }
 
-// byte-string records of the exchange: [u32 id][u32 flag][u32 len][bytes]
-void put_rec(std::vector<uint8_t> &b, uint32_t id, uint32_t flag, const char *s, uint32_t len) {
-    const size_t at = b.size();
-    b.resize(at + 12 + len);
-    memcpy(b.data() + at, &id, 4); memcpy(b.data() + at + 4, &flag, 4); memcpy(b.data() + at + 8, &len, 4);
-    if (len) memcpy(b.data() + at + 12, s, len);
-}
-
 struct skip_t { int32_t cid; uint32_t pack, stage; std::vector<int32_t> rids; };
 
 // One `correct` call: what its steps share, and the steps in the order correct_driver() runs them.
@@ -667,27 +660,21 @@ struct correct_job {
     int exchange_stage(std::vector<uint8_t> &mine_bytes) {
         std::vector<std::vector<uint8_t>> all;
         if (nranks > 1) {
-            if (local_rc) { mine_bytes.clear(); put_rec(mine_bytes, 0xFFFFFFFFu, 0xFFFFFFFFu, nullptr, 0); }      // failure record
+            if (local_rc) { mine_bytes.clear(); write_stage_failure(mine_bytes); }
             RT_TRY(xchg_allgatherv(ctx, mine_bytes, all));
             if (local_rc) { set_error(local_msg); return local_rc; }
-            for (int rk = 0; rk < nranks; ++rk) {
-                uint32_t id = 0, flag = 0;
-                if (all[rk].size() >= 12) { memcpy(&id, all[rk].data(), 4); memcpy(&flag, all[rk].data() + 4, 4); }
-                if (id == 0xFFFFFFFFu && flag == 0xFFFFFFFFu) { set_error("correct_reads failed on rank " + std::to_string(rk)); return RATTLE_ERR_HIP; }
-            }
+            for (int rk = 0; rk < nranks; ++rk)
+                if (is_stage_failure(all[rk].data(), all[rk].size())) { set_error("correct_reads failed on rank " + std::to_string(rk)); return RATTLE_ERR_HIP; }
         } else if (xchg_recording(ctx)) RT_TRY(xchg_allgatherv(ctx, mine_bytes, all));      // (measurement aid, common.h)
         else { all.resize(1); all[0].swap(mine_bytes); }
-        for (const std::vector<uint8_t> &b : all) {
-            size_t at = 0;
-            while (at + 12 <= b.size()) {
-                uint32_t id, flag, len;
-                memcpy(&id, b.data() + at, 4); memcpy(&flag, b.data() + at + 4, 4); memcpy(&len, b.data() + at + 8, 4);
-                const char *s = (const char *)b.data() + at + 12;
-                at += 12 + len;
-                const uint32_t kind = flag & 1u, dead = flag >> 1;
-                if (kind == 0) { if (dead) pk_dead[id] = (uint8_t)dead; else { pk_cons[id].assign(s, len); pk_has[id] = 1; } }
-                else if (!dead) { cl_cons[id].assign(s, len); cl_has[id] = 1; }
+        for (size_t rk = 0; rk < all.size(); ++rk) {
+            wire_reader W(all[rk].data(), all[rk].size());
+            stage_rec rec;
+            while (next_stage_rec(W, n_packs, n_clusters, rec)) {
+                if (rec.kind() == 0) { if (rec.dead()) pk_dead[rec.id] = (uint8_t)rec.dead(); else { pk_cons[rec.id].assign(rec.s, rec.len); pk_has[rec.id] = 1; } }
+                else if (!rec.dead()) { cl_cons[rec.id].assign(rec.s, rec.len); cl_has[rec.id] = 1; }
             }
+            if (!W.ok()) { set_error(wire_error("correct stage exchange", (int)rk, W)); return RATTLE_ERR_HIP; }
         }
         return 0;
     }
@@ -740,9 +727,9 @@ struct correct_job {
         for (uint32_t c : clusters3) {
             if (S.skipped[slot]) {
                 skips.push_back(skip_t{(int32_t)c, 0u, 3u, {}});
-                put_rec(bytes, c, 1u | (3u << 1), nullptr, 0);
+                write_stage_rec(bytes, c, 1u | (3u << 1), nullptr, 0);
             } else {
-                put_rec(bytes, c, 1u, (const char *)C.cons.data() + S.coff[slot], C.len[slot]);
+                write_stage_rec(bytes, c, 1u, (const char *)C.cons.data() + S.coff[slot], C.len[slot]);
                 if (support) { for (int f = 0; f < SUP_FIELDS; ++f) cl_sup[f][c] = counts(slot, f); cl_level[c] = 3; }
             }
             ++slot;
@@ -752,9 +739,9 @@ struct correct_job {
             if (S.skipped[slot]) {
                 skips.push_back(skip_t{PL.pk_cid[p], PL.pk_local[p], 2u, {}});
                 for (uint32_t q = S1.first[k]; q < S1.first[k + 1]; ++q) skips.back().rids.push_back(r[q].rid);
-                put_rec(bytes, p, 2u << 1, nullptr, 0);
+                write_stage_rec(bytes, p, 2u << 1, nullptr, 0);
             } else {
-                put_rec(bytes, p, 0u, (const char *)C.cons.data() + S.coff[slot], C.len[slot]);
+                write_stage_rec(bytes, p, 0u, (const char *)C.cons.data() + S.coff[slot], C.len[slot]);
                 if (support) { pk_sup[p] = counts(slot, SUP_SUPPORT); pk_dep[p] = counts(slot, SUP_DEPTH); }
             }
             ++slot;
@@ -968,7 +955,7 @@ int correct_driver(rattle_ctx *ctx, const uint8_t *seq, const uint8_t *qual, con
     std::vector<uint32_t> s2a, s2b;                  // my live packs of the big clusters / of all others
     for (uint32_t k = 0; k < J.nm; ++k) {
         const uint32_t p = J.mine[k];
-        if (J.pk_dead[p]) put_rec(bytes, p, 1u << 1, nullptr, 0);      // given up in stage 1: announced with the first exchange
+        if (J.pk_dead[p]) write_stage_rec(bytes, p, 1u << 1, nullptr, 0);      // given up in stage 1: announced with the first exchange
         else (J.big[J.PL.pk_cid[p]] ? s2a : s2b).push_back(k);
     }
     // stage 2a: my packs of the big clusters

@@ -17,6 +17,7 @@
 #include <mutex>
 
 #include "common.h"
+#include "wire.h"
 
 namespace rattle {
 
@@ -262,62 +263,13 @@ static int xchg_gatherv(rattle_ctx *ctx, const std::vector<uint8_t> &mine, int r
     return 0;
 }
 
-// ---- (de)serialisation of a correction for the gather -------------------------------------------------
+// ---- the root's merge of a gathered correction (the pieces' format: wire.h) ----------------------------------
 namespace {
 
-template <typename T>
-void put(std::vector<uint8_t> &b, const T *p, size_t n) {
-    // (insert, not resize + memcpy: a resize zero-fills what the copy then overwrites -- 0.16 s of a rank's 250 MB piece at eight ranks)
-    if (n) b.insert(b.end(), (const uint8_t *)p, (const uint8_t *)p + n * sizeof(T));
-}
-template <typename T>
-const T *take(const uint8_t *b, size_t &at, size_t n) {
-    const T *p = (const T *)(b + at);
-    at += n * sizeof(T);
-    return p;
-}
+static_assert((int)WIRE_REP_FIELDS == (int)REP_FIELDS, "the gather piece carries every field of the correction report");
 
 // reads of a set as (key, piece index) so the root can order them; sequences are copied by the merge
 struct rec_ref { uint64_t key; uint32_t piece, idx; };
-
-struct piece_view {                      // one rank's serialised set
-    uint32_t n = 0;
-    const int32_t *read_id = nullptr, *cluster_id = nullptr, *n_reads = nullptr;
-    const uint32_t *pack = nullptr;
-    const uint64_t *off = nullptr;
-    const char *seq = nullptr, *qual = nullptr;
-    const uint32_t *rep[REP_FIELDS] = {};      // the correction report of the records (corrected set), if the rank made one
-    bool has_rep = false;
-};
-
-void put_set(std::vector<uint8_t> &b, const rattle_read_set &S, const uint32_t *pack) {
-    const uint64_t n = S.n;
-    b.reserve(b.size() + 16 + (n + 1) * 8 + n * 16 + 2 * S.off[n] + 8);      // one growth, not a doubling per array
-    put(b, &n, 1);
-    put(b, S.off, n + 1);                // 8-byte fields first: every array stays naturally aligned
-    put(b, S.read_id, n); put(b, S.cluster_id, n); put(b, S.n_reads, n);
-    std::vector<uint32_t> none;
-    if (!pack) { none.assign(n, 0); pack = none.data(); }
-    put(b, pack, n);                     // 4 x 4n bytes: still 8-byte aligned
-    const uint64_t tot = S.off[n];
-    put(b, S.seq, tot); put(b, S.qual, tot);
-    const uint64_t pad = (8 - (2 * tot) % 8) % 8;
-    const char z[8] = {0};
-    put(b, z, pad);
-}
-
-piece_view take_set(const uint8_t *b, size_t &at) {
-    piece_view V;
-    const uint64_t n = *take<uint64_t>(b, at, 1);
-    V.n = (uint32_t)n;
-    V.off = take<uint64_t>(b, at, n + 1);
-    V.read_id = take<int32_t>(b, at, n); V.cluster_id = take<int32_t>(b, at, n); V.n_reads = take<int32_t>(b, at, n);
-    V.pack = take<uint32_t>(b, at, n);
-    const uint64_t tot = V.off[n];
-    V.seq = take<char>(b, at, tot); V.qual = take<char>(b, at, tot);
-    at += (8 - (2 * tot) % 8) % 8;
-    return V;
-}
 
 // merge the pieces' records in key order (stable: equal keys keep piece order, then record order)
 // rep_out: where the records' correction report goes, field by field ([REP_FIELDS] arrays of S.n entries), or null
@@ -391,23 +343,8 @@ int correction_gather(rattle_ctx *ctx, const rattle_correction *L, int root, rat
     // (the root's own share never travels: it is merged from where it lies -- serialising it was 0.15 s of the root's time at eight ranks,
     // 0.6 s at two -- and an empty piece goes into the transport in its place)
     if (X.rank != root) {
-    put_set(mine, L->corrected, L->corrected_pack);
-    put_set(mine, L->uncorrected, L->uncorrected_pack);
-    {
-        const rattle_skip_list &K = L->skipped;
-        const uint64_t n = K.n, tot = K.read_off[K.n];
-        put(mine, &n, 1); put(mine, K.read_off, n + 1);
-        put(mine, K.cluster_id, n); put(mine, K.pack, n); put(mine, K.stage, n); put(mine, K.read_id, tot);
-        if ((3 * n + tot) & 1) { const uint32_t z = 0; put(mine, &z, 1); }
-        put(mine, L->counters, 8);
-    }
-    {
-        // the correction report of the corrected records, if this rank made one (ten arrays of 4-byte entries: 8-byte aligned as a whole)
         const correction_box *B = box_of(L);
-        const uint64_t has = B && B->has_report ? 1 : 0;
-        put(mine, &has, 1);
-        if (has) for (int f = 0; f < REP_FIELDS; ++f) put(mine, B->rep[f], L->corrected.n);
-    }
+        write_gather_piece(mine, *L, B && B->has_report ? B->rep : nullptr);
     }
     T_ser.stop();
     gathered G;
@@ -417,7 +354,6 @@ int correction_gather(rattle_ctx *ctx, const rattle_correction *L, int root, rat
     }
     if (X.rank != root) return 0;
     phase_timer T_merge("gather: merge on the root");
-    rattle_correction *R = new_correction();
     std::vector<piece_view> cor, unc;
     struct skip_ref { int32_t cid; uint32_t pack, stage; const int32_t *rid; uint64_t n; };
     std::vector<skip_ref> sk;
@@ -444,30 +380,23 @@ int correction_gather(rattle_ctx *ctx, const rattle_correction *L, int root, rat
             cnt[5] += L->counters[5]; cnt[6] += L->counters[6]; cnt[7] += L->counters[7];
             continue;
         }
-        size_t at = 0;
-        const uint8_t *b = G.p[r];
-        cor.push_back(take_set(b, at));
-        unc.push_back(take_set(b, at));
-        const uint64_t n = *take<uint64_t>(b, at, 1);
-        const uint64_t *ro = take<uint64_t>(b, at, n + 1);
-        const int32_t *cid = take<int32_t>(b, at, n);
-        const uint32_t *pk = take<uint32_t>(b, at, n), *stg = take<uint32_t>(b, at, n);
-        const uint64_t tot = ro[n];
-        const int32_t *rid = take<int32_t>(b, at, tot);
-        if ((3 * n + tot) & 1) take<uint32_t>(b, at, 1);
-        const uint64_t *c8 = take<uint64_t>(b, at, 8);
-        for (uint64_t i = 0; i < n; ++i) sk.push_back(skip_ref{cid[i], pk[i], stg[i], rid + ro[i], ro[i + 1] - ro[i]});
+        wire_reader W(G.p[r], G.n[r]);
+        gather_view V;
+        if (!parse_gather_piece(W, V)) { set_error(wire_error("correction gather", r, W)); return RATTLE_ERR_HIP; }
+        cor.push_back(V.corrected);
+        unc.push_back(V.uncorrected);
+        const skip_view &K = V.skipped;
+        for (uint64_t i = 0; i < K.n; ++i) sk.push_back(skip_ref{K.cluster_id[i], K.pack[i], K.stage[i], K.read_id + K.read_off[i], K.read_off[i + 1] - K.read_off[i]});
+        const uint64_t *c8 = V.counters;
         cnt[0] += c8[0]; cnt[1] += c8[1];                 // DP cells and alignments add up; the pack count is global already
         cnt[2] = c8[2];
         cnt[3] += c8[3]; cnt[4] += c8[4];
         cnt[5] += c8[5]; cnt[6] += c8[6]; cnt[7] += c8[7];      // cells computed, certified bands, failed certificates add up as well
-        piece_view &C = cor[cor.size() - 1];
-        C.has_rep = *take<uint64_t>(b, at, 1) != 0;
-        if (C.has_rep) for (int f = 0; f < REP_FIELDS; ++f) C.rep[f] = take<uint32_t>(b, at, C.n);
     }
     // the merged result has a correction report if every rank made one
     bool all_rep = true;
     for (const piece_view &C : cor) all_rep = all_rep && C.has_rep;
+    rattle_correction *R = new_correction();
     correction_box *RB = box_of(R);
     if (all_rep) {
         size_t n_cor = 0;
