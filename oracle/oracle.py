@@ -125,6 +125,31 @@ class Oracle(_Lib):
             out.append((deg_a[a:b], eoff[a:b + 1] - eoff[a], dst_a[eoff[a]:eoff[b]]))
         return out
 
+    def poa_band(self, seqs):
+        """What kernel C's exact band is planned from, on the oracle's own graph and matrices.  A list with one dict per
+        alignment k = 1 .. n-1 of poa_msa's loop (the graph after sequences 0 .. k-1): n (rows), C (MSA columns), L (len(seqs[k])), S (the
+        best score of the full matrices), ordered (every in-edge comes from a strictly earlier column) and cols (the column, 1-based, of
+        every rank = DP row - 1)."""
+        n = len(seqs)
+        off = np.zeros(n + 1, np.uint64)
+        off[1:] = np.cumsum([len(s) for s in seqs], dtype=np.uint64)
+        cat = b"".join(seqs)
+        facts = np.zeros(5 * max(n - 1, 1), np.int64)
+        cols = _P(C.c_uint32)()
+        self.lib.orc_poa_band_facts.restype = C.c_uint64
+        tot = self.lib.orc_poa_band_facts(C.c_char_p(cat), _ptr(off, C.c_uint64), C.c_uint32(n), _ptr(facts, C.c_int64), C.byref(cols))
+        try:
+            cols_a = np.ctypeslib.as_array(cols, (tot,)).astype(np.int64) if tot else np.zeros(0, np.int64)
+        finally:
+            self.lib.orc_free(cols)
+        out, at = [], 0
+        for k in range(1, n):
+            rows, cc, ll, ss, od = (int(x) for x in facts[5 * (k - 1):5 * k])
+            out.append({"n": rows, "C": cc, "L": ll, "S": ss, "ordered": bool(od), "cols": cols_a[at:at + rows]})
+            at += rows
+        assert at == tot
+        return out
+
     def poa_msa_blind(self, seqs, kind, value=0):
         """poa_msa with a deliberately wrong row loop (orc_poa_msa_blind), for proving that a pack would notice one.  kind "from": a row's
         in-edges from index `value` on are not seen; "at": in-edges exactly `value` rows back; "beyond": `value` or more rows back;

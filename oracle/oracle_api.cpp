@@ -230,6 +230,47 @@ uint64_t orc_poa_graph(const char *seqs, const uint64_t *off, uint32_t n, uint64
     return dst.size();
 }
 
+// The facts kernel C's exact band is planned from, restated on the oracle's own graph and matrices (tests: on which side of
+// the plan's comparisons a constructed pack sits).  For k = 1 .. n-1 of orc_poa_msa's loop, the graph after sequences 0 .. k-1:
+// facts[5 (k-1) ..] = rows of the graph, its MSA columns C (ranks in topological order; a rank opens a column iff none of its node's
+// aligned group has a smaller rank), L = |seqs[k]|, S = the best score of the full matrices (the scalar fill's), ordered = 1 iff every
+// in-edge comes from a strictly earlier column.  cols (malloc'd, orc_free): the column (1-based) of every rank, graph after graph;
+// returns its length (the sum of the graphs' rows).
+uint64_t orc_poa_band_facts(const char *seqs, const uint64_t *off, uint32_t n, int64_t *facts, uint32_t **cols) {
+    poa_graph_t G;
+    poa_engine_t eng;                              // (scalar rows: their H is read below)
+    std::vector<uint32_t> all;
+    for (uint32_t k = 0; k < n; ++k) {
+        const std::string s(seqs + off[k], seqs + off[k + 1]);
+        poa_alignment_t a = eng.align(s, G);
+        if (k > 0) {
+            const size_t nv = G.nodes.size();
+            std::vector<uint32_t> rank(nv), col(nv);
+            for (size_t r = 0; r < nv; ++r) rank[G.rank_to_node[r]] = (uint32_t)r;
+            uint32_t C = 0;
+            for (size_t r = 0; r < nv; ++r) {
+                const uint32_t v = G.rank_to_node[r];
+                bool first = true;
+                for (uint32_t m : G.nodes[v].aligned) if (rank[m] < r) first = false;
+                if (first) ++C;
+                col[v] = C;
+                all.push_back(C);
+            }
+            bool ordered = true;
+            for (const poa_edge_t &e : G.edges) if (col[e.begin] >= col[e.end]) ordered = false;
+            int32_t S = 0;
+            if (!s.empty()) for (int32_t h : eng.H) S = std::max(S, h);
+            int64_t *f = facts + 5 * (size_t)(k - 1);
+            f[0] = (int64_t)nv; f[1] = C; f[2] = (int64_t)s.size(); f[3] = S; f[4] = ordered ? 1 : 0;
+        }
+        G.add_alignment(a, s);
+    }
+    uint32_t *p = (uint32_t *)malloc((all.size() + 1) * sizeof(uint32_t));
+    memcpy(p, all.data(), all.size() * sizeof(uint32_t));
+    *cols = p;
+    return all.size();
+}
+
 // poa_msa's loop with a deliberately WRONG row loop (tests: a constructed pack must notice).  Every alignment is computed against a
 // copy of the graph in which the row loop's view of the in-edges is spoilt; the alignment is then added to the true graph.
 // kind 1: a row's in-edges from the value-th on (0-based, in in-edge order) are not seen; 2: in-edges exactly `value` rows back are not
