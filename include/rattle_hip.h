@@ -234,6 +234,39 @@ int rattle_hip_assign_reads(rattle_ctx *ctx, const uint8_t *target_concat, const
 void rattle_hip_assignment_free(rattle_assignment *a);
 
 /* ------------------------------------------------------------------------------------
+ * align_pairs: WHERE on its transcript every placed read lies (kernel E, csrc/pair_align.hip); the reference has no counterpart.
+ * target_of_read and rev are exactly rattle_assignment::target and ::rev: read r is aligned to target target_of_read[r] (-1: not
+ * submitted), reverse-complemented first when rev[r] == 1 (A<->T, C<->G, U complements to A).  Only A, C, G, T, U occur; two letters
+ * match iff they are equal after U is read as T.  The alignment is a Smith-Waterman local alignment with match +5, mismatch -4 and
+ * gap -8 PER GAPPED COLUMN: the match, mismatch and gap-open values of `correct`'s engine (a15), but with LINEAR gaps, deliberately not
+ * affine -- that is what makes the record below derivable without a traceback (the device writes no traceback matrix):
+ *   H[i][j] = max(0, H[i-1][j-1] + s(q_i, t_j), H[i-1][j] - 8, H[i][j-1] - 8),  H[0][*] = H[*][0] = 0,  i over the read, j over the target
+ * and it is fully determined: a cell with H == 0 begins a new alignment (a path never runs through a zero); predecessors that tie are
+ * taken diagonal, then up (a read base against a gap), then left (a target base against a gap); the end cell is the largest H, ties to
+ * the smallest i, then the smallest j; no positive cell: no alignment.  Per read:
+ *   status      0 aligned; 1 no positive cell, or one of the two sequences empty; 2 skipped: len(q) * len(t) > max_cells; 3 not submitted
+ *   score       H of the end cell
+ *   q_start, q_end, t_start, t_end   0-based, end-exclusive; q_* on the read AS GIVEN (PAF): for rev == 1 they are Lq - e and Lq - s of
+ *               the reverse-complemented coordinates
+ *   matches, mismatches, q_gap (read bases against a gap), t_gap (target bases against a gap)
+ * (zeros where status != 0).  Every cell carries (start_i, start_j, matches) of its path, taken from the predecessor the rule picks;
+ * with the spans sq, st:  mismatches = (8 (sq + st) - 21 matches + score) / 12,  q_gap = sq - matches - mismatches,  t_gap = st - matches
+ * - mismatches.  One 40-byte record per submitted read is all that returns to the host.
+ * RATTLE_ERR_ARG, before the device is looked at: a NULL pointer, a target index >= n_targets, a rev other than 0 or 1, a byte outside
+ * ACGTU in a submitted read or in a target a submitted read names, a sequence of 2^31 bases or more.  RATTLE_ERR_STATE: a context
+ * without a device, and, before anything is exchanged, a context that is one rank of several (sharded jobs are not built).
+ */
+typedef struct { uint64_t max_cells;   /* 0 = no limit */
+                 uint32_t pair_chunk;  /* pairs in flight; 0 = default; the result does not depend on it */ } rattle_align_params;
+typedef struct { uint32_t n; uint8_t *status; int32_t *score;
+                 uint32_t *q_start, *q_end, *t_start, *t_end, *matches, *mismatches, *q_gap, *t_gap; } rattle_alignment;
+int  rattle_hip_align_pairs(rattle_ctx *ctx, const uint8_t *target_concat, const uint64_t *target_offsets, uint32_t n_targets,
+                            const uint8_t *read_concat, const uint64_t *read_offsets, uint32_t n_reads,
+                            const int32_t *target_of_read /* -1: not submitted */, const uint8_t *rev,
+                            const rattle_align_params *params, rattle_alignment **out);
+void rattle_hip_alignment_free(rattle_alignment *a);
+
+/* ------------------------------------------------------------------------------------
  * a15  spoa engine + graph as called from /root/reference/correct.cpp:395-405,428-436,520-532
  * (createAlignmentEngine(kSW,5,-4,-8,-6); align + add_alignment per sequence;
  * generate_multiple_sequence_alignment).  Packs are independent; pack p holds sequences
@@ -585,7 +618,8 @@ void rattle_hip_debug_consensus_support_free(rattle_debug_support *d);
 /* ------------------------------------------------------------------------------------
  * Per-kernel timing measured with HIP events on the stream the kernels run on.
  * kernel: 0 kmer_extract, 1 bv_filter, 2 pair_score, 3 poa_align, 4 post_msa, 5 the per-read reduction of
- * assign (alg_bytes: the bytes of its records copied to the host).  Accumulated since
+ * assign (alg_bytes: the bytes of its records copied to the host), 6 pair_align (kernel E; alg_bytes: the sequence bytes read plus
+ * the record bytes written).  Accumulated since
  * the last reset: total milliseconds, number of launches, algorithmic bytes moved.
  */
 int rattle_hip_kernel_stats(rattle_ctx *ctx, int kernel, double *total_ms, uint64_t *launches, uint64_t *alg_bytes);

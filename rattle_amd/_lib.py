@@ -145,6 +145,19 @@ class Assignment(C.Structure):
     _fields_ = [("n", C.c_uint32)] + [(f, C.POINTER(t)) for f, t in ASSIGN_FIELDS]
 
 
+class AlignParams(C.Structure):
+    _fields_ = [("max_cells", C.c_uint64), ("pair_chunk", C.c_uint32)]
+
+
+# the per-read record of align_pairs (rattle_alignment): one entry per read
+ALIGN_FIELDS = (("status", C.c_uint8), ("score", C.c_int32), ("q_start", C.c_uint32), ("q_end", C.c_uint32), ("t_start", C.c_uint32),
+                ("t_end", C.c_uint32), ("matches", C.c_uint32), ("mismatches", C.c_uint32), ("q_gap", C.c_uint32), ("t_gap", C.c_uint32))
+
+
+class Alignment(C.Structure):
+    _fields_ = [("n", C.c_uint32)] + [(f, C.POINTER(t)) for f, t in ALIGN_FIELDS]
+
+
 # int fn(void *user, const void *send, uint64 send_bytes, void *recv, const uint64 *recv_bytes)
 ALLGATHERV_FN = C.CFUNCTYPE(C.c_int, C.c_void_p, C.c_void_p, C.c_uint64, C.c_void_p, C.POINTER(C.c_uint64))
 
@@ -191,6 +204,9 @@ SIGNATURES = {
     "rattle_hip_assign_reads": (C.c_int, [C.c_void_p, _u8p, _u64p, C.c_uint32, _u8p, _u64p, C.c_uint32, C.c_int, _P(AssignParams),
                                           _P(_P(Assignment))]),
     "rattle_hip_assignment_free": (None, [_P(Assignment)]),
+    "rattle_hip_align_pairs": (C.c_int, [C.c_void_p, _u8p, _u64p, C.c_uint32, _u8p, _u64p, C.c_uint32, _i32p, _u8p, _P(AlignParams),
+                                         _P(_P(Alignment))]),
+    "rattle_hip_alignment_free": (None, [_P(Alignment)]),
     "rattle_hip_poa_msa": (C.c_int, [C.c_void_p, _u8p, _u64p, C.c_uint32, _u32p, C.c_uint32, _P(_P(MsaSet))]),
     "rattle_hip_msa_set_free": (None, [_P(MsaSet)]),
     "rattle_hip_correct_reads": (C.c_int, [C.c_void_p, _u8p, _u8p, _u64p, C.c_uint32, C.c_uint32, _u32p, _i32p, _u8p,

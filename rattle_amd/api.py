@@ -18,7 +18,7 @@ import numpy as np
 from . import _lib
 from ._lib import ClusterParams, ClusterSet, Correction, CorrectParams, MsaSet, check
 
-K_KMER, K_FILTER, K_SCORE, K_POA, K_POST, K_ASSIGN = 0, 1, 2, 3, 4, 5
+K_KMER, K_FILTER, K_SCORE, K_POA, K_POST, K_ASSIGN, K_ALIGN = 0, 1, 2, 3, 4, 5, 6
 
 
 def _ptr(a: np.ndarray, t):
@@ -611,6 +611,33 @@ class Context:
         self.n = self.k = 0               # the loaded read set was replaced by the last chunk's
         return self._take_assignment(out)
 
+    def align_pairs(self, targets: Sequence[bytes], reads: Sequence[bytes], target_of_read, rev, max_cells=0, pair_chunk=0) -> dict:
+        """Every read r with target_of_read[r] >= 0 aligned locally to that target, reverse-complemented first where rev[r] == 1
+        (rattle_hip_align_pairs, kernel E): the two arrays are `target` and `rev` of an assignment.  Returns a dict of arrays with one
+        entry per read (_lib.ALIGN_FIELDS): status (0 aligned, 1 nothing aligns, 2 skipped by max_cells, 3 not submitted), score,
+        q_start, q_end (on the read as given), t_start, t_end, matches, mismatches, q_gap, t_gap."""
+        tcat, toff = pack_reads(targets)
+        rcat, roff = pack_reads(reads)
+        return self.align_pairs_packed(tcat, toff, rcat, roff, target_of_read, rev, max_cells, pair_chunk)
+
+    def align_pairs_packed(self, tcat: np.ndarray, toff: np.ndarray, rcat: np.ndarray, roff: np.ndarray, target_of_read, rev,
+                           max_cells=0, pair_chunk=0) -> dict:
+        """align_pairs() on packed arrays (pack_reads)"""
+        P = _lib.AlignParams(int(max_cells), int(pair_chunk))
+        n = len(roff) - 1
+        t = np.ascontiguousarray(target_of_read, np.int32)
+        r = np.ascontiguousarray(rev, np.uint8)
+        if len(t) != n or len(r) != n:
+            raise ValueError("target_of_read and rev need one entry per read")
+        out = C.POINTER(_lib.Alignment)()
+        check(self.lib.rattle_hip_align_pairs(self.h, _ptr(tcat, C.c_uint8) if len(tcat) else None, _ptr(toff, C.c_uint64), len(toff) - 1,
+                                              _ptr(rcat, C.c_uint8) if len(rcat) else None, _ptr(roff, C.c_uint64), n,
+                                              _ptr(t, C.c_int32) if n else None, _ptr(r, C.c_uint8) if n else None, C.byref(P), C.byref(out)))
+        m = int(out.contents.n)
+        res = {f: np.ctypeslib.as_array(getattr(out.contents, f), (max(m, 1),))[:m].copy() for f, _ in _lib.ALIGN_FIELDS}
+        self.lib.rattle_hip_alignment_free(out)
+        return res
+
     def debug_evaluate(self, rects, t_s=0.2, t_v=1000000.0, use_hc=False, is_rna=False, count_pass="auto"):
         """One evaluation of the greedy clustering on the loaded reads (rattle_hip_debug_evaluate, a test hook).
         rects: list of (seed_ids, cand_ids, thr); cand_ids None = triangular (the seeds against each other, pairs s < c).
@@ -936,3 +963,36 @@ def assign_command(ctx: Context, read_headers: Sequence[bytes], reads: Sequence[
         rec[f][sent] = got[f]
     tn = [_first_token(h) for h in target_headers]
     return (assignments_tsv([_first_token(h) for h in read_headers], tn, rec), target_counts_tsv(tn, [len(s) for s in targets], rec))
+
+
+def paf_text(read_names: Sequence[bytes], read_lengths: Sequence[int], target_names: Sequence[bytes], target_lengths: Sequence[int],
+             assignment: dict, alignment: dict) -> bytes:
+    """alignments.paf as `rattle assign --paf` writes it: one line per read with status 0, in file order (none for unassigned, unaligned
+    or skipped reads): read, Lq, q_start, q_end, + / -, target, Lt, t_start, t_end, matches, columns (matches + mismatches + q_gap +
+    t_gap), 255, AS:i:score, NM:i:mismatches + q_gap + t_gap, nx:i:mismatches, ni:i:q_gap, nd:i:t_gap."""
+    lines = []
+    for i in np.nonzero(np.asarray(alignment["status"]) == 0)[0]:
+        t = int(assignment["target"][i])
+        M, X, qg, tg = (int(alignment[f][i]) for f in ("matches", "mismatches", "q_gap", "t_gap"))
+        lines.append(b"%s\t%d\t%d\t%d\t%s\t%s\t%d\t%d\t%d\t%d\t%d\t255\tAS:i:%d\tNM:i:%d\tnx:i:%d\tni:i:%d\tnd:i:%d\n" % (
+            read_names[i], int(read_lengths[i]), int(alignment["q_start"][i]), int(alignment["q_end"][i]),
+            b"-" if assignment["rev"][i] else b"+", target_names[t], int(target_lengths[t]), int(alignment["t_start"][i]),
+            int(alignment["t_end"][i]), M, M + X + qg + tg, int(alignment["score"][i]), X + qg + tg, X, qg, tg))
+    return b"".join(lines)
+
+
+def assign_paf_command(ctx: Context, read_headers: Sequence[bytes], reads: Sequence[bytes], target_headers: Sequence[bytes],
+                       targets: Sequence[bytes], *, k=10, t_s=0.2, t_v=1000000.0, bv_threshold=0.4, is_rna=False, count_pass="auto",
+                       target_batch=0, read_chunk=0, max_cells=0, pair_chunk=0):
+    """`rattle assign --paf`: assign_command, then every placed read aligned to its transcript (Context.align_pairs).  Returns the bytes
+    of assignments.tsv, target_counts.tsv and alignments.paf; the first two are what assign_command returns."""
+    sent = [i for i, s in enumerate(reads) if not s.translate(None, b"ACGTU")]
+    got = ctx.assign(targets, [reads[i] for i in sent], k, t_s, t_v, bv_threshold, False, is_rna, target_batch, read_chunk, count_pass)
+    rec = unassigned_records(len(reads))
+    for f in rec:
+        rec[f][sent] = got[f]
+    aln = ctx.align_pairs(targets, reads, rec["target"], rec["rev"], max_cells, pair_chunk)
+    tn = [_first_token(h) for h in target_headers]
+    rn = [_first_token(h) for h in read_headers]
+    tl = [len(s) for s in targets]
+    return (assignments_tsv(rn, tn, rec), target_counts_tsv(tn, tl, rec), paf_text(rn, [len(s) for s in reads], tn, tl, rec, aln))

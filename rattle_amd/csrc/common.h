@@ -129,7 +129,7 @@ struct hbuf {
     }
 };
 
-enum { K_KMER = 0, K_FILTER = 1, K_SCORE = 2, K_POA = 3, K_POST = 4, K_ASSIGN = 5, K_COUNT = 6 };
+enum { K_KMER = 0, K_FILTER = 1, K_SCORE = 2, K_POA = 3, K_POST = 4, K_ASSIGN = 5, K_ALIGN = 6, K_COUNT = 7 };
 
 struct kstat {
     double ms = 0;
@@ -503,6 +503,9 @@ int debug_evaluate(rattle_ctx *ctx, const rattle_cluster_params *P, int count_mo
 // records [out_base, out_base + n_reads) of A: the loaded reads read_ids placed on the loaded reads target_ids
 int assign_driver(rattle_ctx *ctx, const rattle_assign_params *P, const uint32_t *target_ids, uint32_t n_targets, const uint32_t *read_ids,
                   uint32_t n_reads, rattle_assignment *A, uint32_t out_base);
+// pair_align.hip : kernel E, the local alignment of every submitted read on its target; fills every array of A (arguments checked by the caller)
+int align_pairs_run(rattle_ctx *ctx, const uint8_t *tseq, const uint64_t *toff, uint32_t n_targets, const uint8_t *rseq, const uint64_t *roff,
+                    uint32_t n_reads, const int32_t *target, const uint8_t *rev, const rattle_align_params *P, rattle_alignment *A);
 
 // correct_driver.hip
 int debug_post_msa(rattle_ctx *ctx, const rattle_correct_params *P, int mode, const rattle_debug_msa *in, rattle_debug_post **out);

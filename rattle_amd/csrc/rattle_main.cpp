@@ -767,7 +767,8 @@ int mode_cluster(int argc, char **argv) {
 // ---- `rattle assign` -----------------------------------------------------------------------------------------------------
 // The reads of -i placed on the transcripts of -x by their best cluster_together score (include/rattle_hip.h, "assign").
 // Every record of both files takes part, in file order: there is no length filter and no sort.  A read with a base other than A, C,
-// G, T, U is not compared and comes out unassigned (`cluster` skips such reads).
+// G, T, U is not compared and comes out unassigned (`cluster` skips such reads).  --paf: every placed read is then aligned to its transcript
+// (include/rattle_hip.h, "align_pairs") and alignments.paf appears beside the two tables.
 struct assign_job {
     args_t a;
     int k = 10;
@@ -780,20 +781,26 @@ struct assign_job {
     byte_buf rcat, xcat;
     std::vector<uint64_t> roff, xoff;
     rattle_assignment *A = nullptr;
-    std::string text, counts;                     // assignments.tsv, target_counts.tsv
+    bool want_paf = false;
+    rattle_align_params AP;
+    std::string text, counts, paf;                // assignments.tsv, target_counts.tsv, alignments.paf (--paf)
     void options(int argc, char **argv) {
         a = parse(argc, argv, {
             {"help", {"-h", "--help"}, false}, {"input", {"-i", "--input"}, true}, {"targets", {"-x", "--transcripts"}, true},
             {"output", {"-o", "--output"}, true}, {"kmer_size", {"-k", "--kmer-size"}, true}, {"t_s", {"-s", "--score-threshold"}, true},
             {"t_v", {"-v", "--max-variance"}, true}, {"bv_threshold", {"-B", "--bv-start-threshold"}, true}, {"rna", {"--rna"}, false},
             {"count-pass", {"--count-pass"}, true}, {"device", {"--device"}, true}, {"devices", {"--devices"}, true},
-            {"target-batch", {"--target-batch"}, true}, {"read-chunk", {"--read-chunk"}, true}});
-        const char *usage = "rattle assign -i reads.fq -x transcripts.fq [-o dir] [-k 10] [-s 0.2] [-v 1000000] [-B 0.4] [--rna] [--device n]\n"
+            {"target-batch", {"--target-batch"}, true}, {"read-chunk", {"--read-chunk"}, true}, {"paf", {"--paf"}, false},
+            {"paf-max-cells", {"--paf-max-cells"}, true}});
+        const char *usage = "rattle assign -i reads.fq -x transcripts.fq [-o dir] [-k 10] [-s 0.2] [-v 1000000] [-B 0.4] [--rna] [--device n] [--paf]\n"
                             "  places every read of -i on the transcript of -x that accepts it with the best score (the comparison `cluster` joins\n"
                             "  reads by, the transcript in the seed's role) and writes assignments.tsv (one line per read: target, strand, score,\n"
                             "  second_score, n_accepted, bases, hc_bases, min_len, variance) and target_counts.tsv (reads per transcript)\n"
                             "  --count-pass auto|seed|search|index   form of the count pass (default auto)\n"
-                            "  --target-batch n / --read-chunk n     transcripts per evaluation / reads indexed at a time (the result does not depend on them)\n";
+                            "  --target-batch n / --read-chunk n     transcripts per evaluation / reads indexed at a time (the result does not depend on them)\n"
+                            "  --paf                                 also align every placed read to its transcript (local, match 5, mismatch -4, gap -8 per\n"
+                            "                                        column) and write alignments.paf: one PAF line per aligned read, in file order\n"
+                            "  --paf-max-cells n                     with --paf: skip a read whose length x its transcript's length exceeds n (default 0: no limit)\n";
         if (a.has("help")) { std::cerr << usage; exit(EXIT_SUCCESS); }
         if (!a.has("input")) die("ERROR: No input file provided (-i reads)");
         if (!a.has("targets")) die("ERROR: No transcript file provided (-x transcripts)");
@@ -805,6 +812,10 @@ struct assign_job {
         outdir = output_dir(a);
         P.t_s = a.d("t_s", 0.2); P.t_v = a.d("t_v", 1000000); P.bv_threshold = a.d("bv_threshold", 0.4);
         P.is_rna = a.has("rna") ? 1 : 0;
+        want_paf = a.has("paf");
+        if (a.has("paf-max-cells") && !want_paf) die("\nError: --paf-max-cells needs --paf\n");
+        memset(&AP, 0, sizeof AP);
+        AP.max_cells = std::stoull(a.str("paf-max-cells", "0"));
         P.target_batch = (uint32_t)std::max(0, a.i("target-batch", 0)); P.read_chunk = (uint32_t)std::max(0, a.i("read-chunk", 0));
         std::cerr << "RNA mode: " << std::boolalpha << (P.is_rna != 0) << std::endl;
     }
@@ -829,6 +840,26 @@ struct assign_job {
         cli_timer t("library: assign");
         chk(rattle_hip_assign_reads(team.ctx[0], xcat.data(), xoff.data(), (uint32_t)xid.size(), rcat.data(), roff.data(), (uint32_t)rid.size(), k, &P, &A));
     }
+    // --paf: the submitted reads on the transcripts `run` placed them on; one PAF line per read that aligns, in file order
+    void align() {
+        cli_timer t("library: align_pairs");
+        rattle_alignment *L = nullptr;
+        chk(rattle_hip_align_pairs(team.ctx[0], xcat.data(), xoff.data(), (uint32_t)xid.size(), rcat.data(), roff.data(), (uint32_t)rid.size(), A->target, A->rev, &AP, &L));
+        uint64_t skipped = 0;
+        for (uint32_t at = 0; at < L->n; ++at) {
+            skipped += L->status[at] == 2;
+            if (L->status[at] != 0) continue;
+            const uint32_t x = (uint32_t)A->target[at];
+            const uint64_t gaps = (uint64_t)L->q_gap[at] + L->t_gap[at], cols = (uint64_t)L->matches[at] + L->mismatches[at] + gaps;
+            paf += record_name(R.header[rid[at]]) + "\t" + std::to_string(R.seq[rid[at]].n) + "\t" + std::to_string(L->q_start[at]) + "\t" + std::to_string(L->q_end[at]) + "\t" +
+                   (A->rev[at] ? "-" : "+") + "\t" + record_name(X.header[x]) + "\t" + std::to_string(X.seq[x].n) + "\t" + std::to_string(L->t_start[at]) + "\t" +
+                   std::to_string(L->t_end[at]) + "\t" + std::to_string(L->matches[at]) + "\t" + std::to_string(cols) + "\t255\tAS:i:" + std::to_string(L->score[at]) +
+                   "\tNM:i:" + std::to_string(L->mismatches[at] + gaps) + "\tnx:i:" + std::to_string(L->mismatches[at]) + "\tni:i:" + std::to_string(L->q_gap[at]) +
+                   "\tnd:i:" + std::to_string(L->t_gap[at]) + "\n";
+        }
+        rattle_hip_alignment_free(L);
+        if (skipped) std::cerr << "\n" << skipped << "  reads over --paf-max-cells are left out of alignments.paf" << std::endl;
+    }
     // one line per read of -i, the reads that were not submitted included; then one line per transcript
     void format() {
         std::vector<uint64_t> n_best(X.n(), 0), n_unique(X.n(), 0);
@@ -852,6 +883,7 @@ struct assign_job {
     void write() {
         write_text(outdir + "/assignments.tsv", text);
         write_text(outdir + "/target_counts.tsv", counts);
+        if (want_paf) write_text(outdir + "/alignments.paf", paf);
         team.close();
         std::cerr << "Done" << std::endl;
     }
@@ -862,6 +894,7 @@ int mode_assign(int argc, char **argv) {
     J.options(argc, argv);
     J.read_input();
     J.run();
+    if (J.want_paf) J.align();
     J.format();
     J.write();
     return EXIT_SUCCESS;
