@@ -718,13 +718,27 @@ __device__ __forceinline__ s16x2 pk_left(uint32_t cur, uint32_t prev) { return a
 #define POA_SHIFT_ONCE 0          // 1: maxima over the predecessors on the unshifted H words, ONE shift per row (1.18 x (NP + 1) fewer instructions
                                   // per row, but the shift then sits on the row's critical path: -1.3 % in an interleaved A/B, three rounds on one box)
 #endif
+#ifndef POA_FAR_BY_DISTANCE
+#define POA_FAR_BY_DISTANCE 1     // 1: the row of a predecessor beyond the ring is row - distance byte; the full plan only answers for a saturated byte
+                                  // (0: always the full plan, a scalar-cache round trip per far fetch.  1536-column class alone, interleaved, three
+                                  // rounds: 979 against 938 GCUPS at 2048 packs, 803 against 785 at 1536; profiles/round7_ring_front.txt)
+#endif
 typedef unsigned short u16x2 __attribute__((ext_vector_type(2)));
 typedef uint32_t u32x4 __attribute__((ext_vector_type(4)));
 typedef const __attribute__((address_space(4))) u32x4 *cplan_t;      // wave-uniform loads from it are s_load_dwordx4
 
-template <int CPL, int RING, int NW>
+// FRONT > 0 (the 1536-column instance, poa_front_rows): the row loop keeps RING + FRONT rows, in the SAME LDS.  The extra rows lie over
+// what stands in front of the ring -- the sequence, the graph walks' bitmaps and their stack -- none of which is live while the rows
+// run: this function has the sequence in registers once its prologue is through (a barrier there, before the first ring write), the
+// bitmaps are zeroed by each of their users, the stack is empty between two walks, and the caller copies the sequence in again behind
+// the rows.  A slot of that ring is the threads' words with the row's four left-column words right behind them, so ONE offset, carried
+// from row to row, addresses both (RING + FRONT is no power of two: no mask, and no division either).  The ring ends where the ring of
+// RING rows ends (poa_ring_bytes) and so begins poa_front_need bytes in front of S.ring.
+template <int CPL, int RING, int NW, int FRONT = 0>
 __device__ void dp_rows_v3(poa_ws &S, dp_xchg &X, uint32_t n, uint32_t L, uint32_t Lp, int32_t &best, uint32_t &best_row, bool &multi) {
     constexpr int NT = 64 * NW, NP = CPL / 2;
+    constexpr uint32_t RSLOTS = RING + FRONT;                         // rows the ring serves
+    constexpr uint32_t ROWW = NT * NP + 4;                            // FRONT > 0: words from one slot to the next
     static_assert(RING > 0, "the rows of the last RING rows live in LDS");
     static_assert(NT * CPL <= 2560 && NW <= 4, "packed rows: u = Hn + g - (j+1)e must fit 16 bits");
     const int tid = threadIdx.x, lane = tid & 63, wave = __builtin_amdgcn_readfirstlane(tid >> 6);
@@ -751,6 +765,7 @@ __device__ void dp_rows_v3(poa_ws &S, dp_xchg &X, uint32_t n, uint32_t L, uint32
         SEL[u] = sa | (sb << 16);
     }
     const bool plain = S.plain != 0;
+    if constexpr (FRONT > 0) __syncthreads();    // every thread has its sequence bytes (sw, SEL): from here on the ring may overwrite S.sq
     s16x2 JE[NP], UC[NP];                        // per column: j*e and g - (j+1)*e
 #pragma unroll
     for (int u = 0; u < NP; ++u) {
@@ -761,13 +776,16 @@ __device__ void dp_rows_v3(poa_ws &S, dp_xchg &X, uint32_t n, uint32_t L, uint32
     }
     s16x2 MXA = pk_splat(0);                    // running maximum of this thread's columns over all rows (pairs)
     const bool wave_act = (uint32_t)wave * 64u * CPL < Lp;
-    uint32_t *const ring_thr = S.ring + (size_t)tid * NP;              // slot s of this thread: ring_thr + s * NT * NP
-    // slot s of this wavefront: lhr[4 * s].  The LDS offset is made opaque in a VECTOR register: as a uniform value its address
+    uint32_t *const ring0 = FRONT > 0 ? S.ring + (RING * NT * NP + RING * 4) - RSLOTS * ROWW : S.ring;
+    uint32_t *const ring_thr = ring0 + (size_t)tid * NP;               // slot s of this thread: ring_thr + s * NT * NP (FRONT > 0: + s * ROWW)
+    uint32_t own_off = ROWW;                                           // FRONT > 0: word offset of the slot of the row in hand, (row % RSLOTS) * ROWW
+    // slot s of this wavefront: lhr[4 * s] (FRONT > 0: lhr[s * ROWW], right behind the slot's own words).
+    // The LDS offset is made opaque in a VECTOR register: as a uniform value its address
     // arithmetic went through the scalar unit (shift, add, v_mov per predecessor) -- the scalar unit issues as many instructions per
     // cell as the vector unit in this kernel, one v_lshl_add does the same
     uint32_t lhr_off = (uint32_t)wave;
     asm volatile("" : "+v"(lhr_off));
-    uint32_t *const lhr = (uint32_t *)S.lh_ring + lhr_off;
+    uint32_t *const lhr = (FRONT > 0 ? ring0 + NT * NP : (uint32_t *)S.lh_ring) + lhr_off;
     uint32_t *const Hrec = (uint32_t *)S.H;                            // the record, a dword per column pair
 
     // the plan through the scalar cache: invalidate it first (the plan was just rewritten by vector stores, which are in L2
@@ -793,23 +811,30 @@ __device__ void dp_rows_v3(poa_ws &S, dp_xchg &X, uint32_t n, uint32_t L, uint32
         uint32_t raw[4][NP], rawl[4];
         // k: which of the four fetch slots; kp: which in-edge (0..7: the plan holds its row; 8: `far_row` is given)
         auto fetch = [&](const int k, const int kp, const uint32_t d, const uint32_t far_row) __attribute__((always_inline)) {
-            if (d <= (uint32_t)RING) {
-                const uint32_t slot = (row - d) % (uint32_t)RING;
-                const uint32_t *rp = ring_thr + slot * (uint32_t)(NT * NP);
+            if (d <= RSLOTS) {
+                // FRONT > 0: d slots back from the row's own, around the ring's end (a subtraction and its borrow)
+                const uint32_t back = d * ROWW;
+                const uint32_t slot = FRONT > 0 ? 0u : (row - d) % (uint32_t)RING;
+                const uint32_t soff = FRONT > 0 ? (own_off < back ? own_off + RSLOTS * ROWW - back : own_off - back) : slot * (uint32_t)(NT * NP);
+                const uint32_t *rp = ring_thr + soff;
                 if constexpr (NP == 2) { const uint2 a2 = *(const uint2 *)rp; raw[k][0] = a2.x; raw[k][1] = a2.y; }
                 else if constexpr (NP == 4) { const uint4 a4 = *(const uint4 *)rp; raw[k][0] = a4.x; raw[k][1] = a4.y; raw[k][2] = a4.z; raw[k][3] = a4.w; }
                 else {
 #pragma unroll
                     for (int u = 0; u < NP; ++u) raw[k][u] = rp[u];
                 }
-                rawl[k] = lhr[4 * slot];
+                rawl[k] = lhr[FRONT > 0 ? soff : 4 * slot];
             } else {
-                // beyond the ring (a few per cent of the fetches): the row itself from the full plan (the byte may be saturated)
-                uint32_t prow = kp >= 8 ? far_row : kp >= 4 ? cpc[row - 1][kp - 4] : cpb[row - 1][kp];
-                // the scalar load lands HERE: left pending to the end of this (rare) branch, the compiler waits lgkmcnt(0) before the
-                // next predecessor's ring address on the common path too (same scalar register) -- which serialised the LDS reads of
-                // a row's predecessors
-                asm volatile("s_waitcnt lgkmcnt(0)" : "+s"(prow));
+                // beyond the ring: the distance byte gives the row unless it is saturated; only then the row itself comes from the full
+                // plan, a scalar-cache round trip (the walk beyond the eighth in-edge brings its row along)
+                uint32_t prow = kp >= 8 ? far_row : row - d;
+                if (kp < 8 && (!POA_FAR_BY_DISTANCE || d >= 255u)) {
+                    prow = kp >= 4 ? cpc[row - 1][kp - 4] : cpb[row - 1][kp];
+                    // the scalar load lands HERE: left pending to the end of this (rare) branch, the compiler waits lgkmcnt(0) before the
+                    // next predecessor's ring address on the common path too (same scalar register) -- which serialised the LDS reads of
+                    // a row's predecessors
+                    asm volatile("s_waitcnt lgkmcnt(0)" : "+s"(prow));
+                }
                 // No divergent control flow in here (threads beyond the row and the lanes that need no left neighbour load from a valid
                 // address and drop the value): with exec-mask regions inside, the compiler gave the COMMON path a flag, a second test
                 // and a second branch per predecessor.
@@ -950,9 +975,13 @@ __device__ void dp_rows_v3(poa_ws &S, dp_xchg &X, uint32_t n, uint32_t L, uint32
         base = max(base, texcl);
         const s16x2 BASE = as_pk(pack16(base, base));
         uint32_t W[NP];
+        // (FRONT > 0: j*e of the further pairs from the first pair's, a packed add with an inline constant each, instead of a register each
+        // across the loop -- the allocator, held to 64 registers, otherwise keeps one in scratch and reloads it every row)
+        s16x2 je0 = JE[0];
+        if constexpr (FRONT > 0) asm volatile("" : "+v"(je0));
 #pragma unroll
         for (int u = 0; u < NP; ++u) {
-            const s16x2 EV = pk_max(BASE, EX[u]) + JE[u];
+            const s16x2 EV = pk_max(BASE, EX[u]) + (FRONT > 0 && u > 0 ? je0 + pk_splat(2 * u * POA_E) : JE[u]);
             const s16x2 HN = pk_max(HNp[u], EV);
             MXA = pk_max(MXA, HN);
             // One word per pair serves the ring, later rows and the traceback: H (14 bits) and min(H - F, 3).  The traceback's tests
@@ -962,15 +991,16 @@ __device__ void dp_rows_v3(poa_ws &S, dp_xchg &X, uint32_t n, uint32_t L, uint32
             W[u] = as_u(HN) | (as_u(pk_min(HN - FN[u], pk_splat(3))) << 14);
         }
         {
-            const uint32_t slot = row % (uint32_t)RING;
-            uint32_t *rp = ring_thr + slot * (uint32_t)(NT * NP);
+            const uint32_t slot = FRONT > 0 ? 0u : row % (uint32_t)RING;
+            const uint32_t soff = FRONT > 0 ? own_off : slot * (uint32_t)(NT * NP);
+            uint32_t *rp = ring_thr + soff;
             if constexpr (NP == 2) *(uint2 *)rp = make_uint2(W[0], W[1]);
             else if constexpr (NP == 4) *(uint4 *)rp = make_uint4(W[0], W[1], W[2], W[3]);
             else {
 #pragma unroll
                 for (int u = 0; u < NP; ++u) rp[u] = W[u];
             }
-            if (lane_o == 0) lhr[4 * slot] = (uint32_t)hl_new << 16;
+            if (lane_o == 0) lhr[FRONT > 0 ? soff : 4 * slot] = (uint32_t)hl_new << 16;
             if (act) {
                 uint32_t *hq = Hrec + ((uint64_t)row * Lp >> 1) + (c0 >> 1);
                 if (NP % 2 == 0) {
@@ -993,9 +1023,11 @@ __device__ void dp_rows_v3(poa_ws &S, dp_xchg &X, uint32_t n, uint32_t L, uint32
         for (uint32_t row = 1; row <= n; row += 2) {
             if (row < n) p1 = cpd[row];
             step(std::integral_constant<uint32_t, 1>{}, row, p0);
+            if constexpr (FRONT > 0) own_off = own_off == (RSLOTS - 1) * ROWW ? 0u : own_off + ROWW;
             if (row + 1 <= n) {
                 if (row + 1 < n) p0 = cpd[row + 1];
                 step(std::integral_constant<uint32_t, 0>{}, row + 1, p1);
+                if constexpr (FRONT > 0) own_off = own_off == (RSLOTS - 1) * ROWW ? 0u : own_off + ROWW;
             }
         }
     }
@@ -2421,6 +2453,22 @@ __host__ __device__ constexpr uint32_t poa_ring_bytes(int CPL, int RING, int NW,
 __host__ __device__ constexpr uint32_t poa_region_bytes(uint32_t node_cap, int CPL, int RING, int NW, int PK) {
     return (2u * poa_bit_words(node_cap) + POA_STACK) * 4u + poa_ring_bytes(CPL, RING, NW, PK);      // bitmaps, stack, ring: back to back
 }
+// The barrier form's 1536-column instance runs its rows on a ring of POA_FRONT_ROWS rows more than its RING says, at no LDS of its own:
+// the extra rows lie over the sequence, the bitmaps and the stack in front of the ring, which are idle while the rows run (dp_rows_v3,
+// FRONT).  29 % of that class's in-edges lie further back than four rows and came from HBM one after the other; the LDS for a longer
+// ring costs a workgroup per CU (profiles/round5_ring_1536.txt), this one does not.  poa_front_need: the bytes the ring (a slot = the
+// threads' words + four left-column words) reaches in front of S.ring; the host pads the sequence's LDS copy up to it (poa_run::lds_plan).
+#ifndef POA_FRONT_ROWS
+#define POA_FRONT_ROWS 2
+#endif
+__host__ __device__ constexpr int poa_front_rows(int CPL, int RING, int NW, int PK) { return PK == 1 && CPL == 6 && RING == 4 && NW == 4 ? POA_FRONT_ROWS : 0; }
+__host__ __device__ constexpr uint32_t poa_front_need(int CPL, int RING, int NW, int PK) {
+    return poa_front_rows(CPL, RING, NW, PK) == 0 ? 0u
+         : (uint32_t)(RING + poa_front_rows(CPL, RING, NW, PK)) * (64u * NW * (CPL / 2) + 4u) * 4u - poa_ring_bytes(CPL, RING, NW, PK);
+}
+static_assert(poa_front_need(6, POA_RING_4x6, 4, 1) % 16u == 0, "the ring in front of S.ring starts 16-byte aligned, like S.ring");
+// (a full 1536-column group of a first pass -- 1536 bytes of sequence, 7 x 1536 nodes -- has a front of 6272 bytes: nothing to pad, eight workgroups per CU as before)
+static_assert(poa_front_need(6, POA_RING_4x6, 4, 1) <= 1536u + (2u * poa_bit_words(7u * 1536u) + POA_STACK) * 4u || POA_RING_4x6 != 4 || POA_FRONT_ROWS != 2, "the two extra rows fit the front of the 1536-column class");
 
 // minimum wavefronts per SIMD the register allocation is held to (the kernel is bound by the latency of a row's dependent
 // instruction chain, hidden only by other resident wavefronts: occupancy first)
@@ -2508,6 +2556,8 @@ __global__ __launch_bounds__(64 * NW * pk_teams(RING, PK), poa_min_waves(CPL, NW
                 const uint32_t n = S.n_nodes;
                 const uint32_t Lp = (L + CPL - 1) / CPL * CPL;
                 if (PK == 8 ? ((uint64_t)(n + 1) * 512u > A.cell_cap || L > 2560u) : ((uint64_t)(n + 1) * Lp > A.cell_cap || (PK != 2 && Lp > NTC * CPL))) { S.err = POA_ERR_CELLS; break; }
+                // (the host pads the sequence's LDS copy so that the rows' ring fits in front of S.ring, poa_run::lds_plan: a launch without that fails here, not in LDS)
+                if (poa_front_rows(CPL, RING, NW, PK) > 0 && A.seq_cap + (2u * poa_bit_words(A.node_cap) + POA_STACK) * 4u < poa_front_need(CPL, RING, NW, PK)) { S.err = POA_ERR_GRAPH; break; }
                 // ---- 1. rows are taken in the incrementally maintained block order (merge_order) ----
                 unsigned long long t0 = PT_NOW();
                 // ---- 2. plan + sequence to LDS (all threads) ----
@@ -2532,7 +2582,7 @@ __global__ __launch_bounds__(64 * NW * pk_teams(RING, PK), poa_min_waves(CPL, NW
                             if (k < 4) dy |= d << (8 * k); else dz |= d << (8 * (k - 4));
                         }
 #ifdef POA_PREDSTAT
-                        { const uint32_t d = r + 1 - ((uint32_t)S.rank[b] + 1); ++ps_in; if (d > (uint32_t)(RING > 0 ? RING : 1)) ++ps_far; if (d == 1) ++ps_prev; }
+                        { const uint32_t d = r + 1 - ((uint32_t)S.rank[b] + 1); ++ps_in; if (d > (uint32_t)(RING > 0 ? RING + poa_front_rows(CPL, RING, NW, PK) : 1)) ++ps_far; if (d == 1) ++ps_prev; }
 #endif
                     }
 #ifdef POA_PREDSTAT
@@ -2800,7 +2850,16 @@ __global__ __launch_bounds__(64 * NW * pk_teams(RING, PK), poa_min_waves(CPL, NW
                 else if constexpr (PK == 2) dp_rows_long<CPL, NW>(S, X, s, n, L, Lp, best, best_row, multi);
                 else if constexpr (PK == 3) dp_rows_wide<CPL, RING, NW>(S, X, n, L, Lp, best, best_row, multi);
                 else if constexpr (PK == 7) dp_rows_mt<CPL, NW, RING>(S, X, A, n, L, Lp, best, best_row, multi);
-                else if constexpr (PK == 1) dp_rows_v3<CPL, RING, NW>(S, X, n, L, Lp, best, best_row, multi);
+                else if constexpr (PK == 1) {
+                    constexpr int FR = poa_front_rows(CPL, RING, NW, PK);
+                    dp_rows_v3<CPL, RING, NW, FR>(S, X, n, L, Lp, best, best_row, multi);
+                    if constexpr (FR > 0) {
+                        // the ring lay over the sequence's LDS copy (every wavefront is behind its last ring access: dp_rows_v3 ends with
+                        // barriers): in again, as in step 2, before the traceback tests its letters
+                        for (uint32_t t = tid; t < Lp; t += NT) S.sq[t] = t < L ? s[t] : 0;
+                        __syncthreads();
+                    }
+                }
                 else dp_rows<CPL, RING, NW>(S, X, n, L, Lp, best, best_row, multi);
                 cells += (unsigned long long)n * L;
                 if (PK != 8) cells_done += (unsigned long long)n * L;
@@ -3826,6 +3885,10 @@ struct poa_run {
         if (gc < 4 && P.V->pk != 1 && P.V->pk != 8 && (lds_bytes(g, P.V) > 158u * 1024 || !mt_ring_ok)) { P.V = &k_dense[gc]; A.ring_slots = A.ring_reach = A.ring_slack = 0; A.o_planm = P.per_slot; A.band = 0; }      // (o_planm: empty, at the end of the slot)
         if ((gc == 4 || gc == 5 || gc == 6) && (lds_bytes(g, P.V) > 158u * 1024 || ENV.noring)) P.V = &k_noring[gc - 4];
         if (gc == POA_CLASSES - 1 && (lds_bytes(g, P.V) > 158u * 1024 || ENV.noring)) P.V = &k_long_noring;
+        // the instance whose rows keep a longer ring over the front of the workgroup's LDS (poa_front_rows): the front holds it.  A full
+        // 1536-column group of a first pass has that much anyway; a smaller front is padded up to it and still takes less LDS than that group
+        const uint32_t need = poa_front_need((int)P.V->cpl, (int)P.V->ring, (int)P.V->nw, (int)P.V->pk), front = poa_lds_front(A.seq_cap, ncap);
+        if (front < need) A.seq_cap += (need - front + 15u) & ~15u;
         P.shm = lds_bytes(g, P.V);
     }
     uint64_t plan_group(int g, uint64_t tb, uint32_t tl) { slot_layout(g, tb, tl); lds_plan(g); return C[g].per_slot; }
