@@ -267,6 +267,33 @@ int  rattle_hip_align_pairs(rattle_ctx *ctx, const uint8_t *target_concat, const
 void rattle_hip_alignment_free(rattle_alignment *a);
 
 /* ------------------------------------------------------------------------------------
+ * align_cigars: align_pairs, and WHICH columns of every alignment disagree (kernel F, csrc/pair_cigar.hip, after kernel E on the same
+ * uploaded sequences).  *out is field for field what rattle_hip_align_pairs returns for the same arguments.  The CIGAR of read r is
+ * ops[offset[r] .. offset[r + 1]), each op  length << 4 | code  with BAM's codes, in the extended set:
+ *   7 '='  a read base on an equal target base (after U is read as T)     8 'X'  a read base on an unequal target base
+ *   1 'I'  a read base against a gap (counted in q_gap)                   2 'D'  a target base against a gap (counted in t_gap)
+ * It is the path the rule of align_pairs picks (diagonal, then up, then left; it begins behind a zero cell), read from its start to its
+ * end on the strand that was aligned: the read reverse-complemented first when rev[r] == 1, the target always forward -- PAF's order on
+ * both strands.  Runs are merged; there is no clipping op (q_start and q_end say what is clipped).  So the summed lengths of '=', 'X',
+ * 'I', 'D' are matches, mismatches, q_gap, t_gap of the record, '=' + 'X' + 'I' = q_end - q_start and '=' + 'X' + 'D' = t_end - t_start.
+ * A read whose status is not 0 has no ops: offset[r + 1] == offset[r].  (A run of 2^28 columns or more would come in pieces.)
+ * Kernel F works on the rectangle (q_start, q_end] x (t_start, t_end] of kernel E's record alone: it records 2 bits per cell there
+ * (16 bytes per 64 cells), walks them back on the device, and only the ops and one count per pair return to the host.  The code bytes
+ * of the pairs in flight are capped at 4 GiB (pair_chunk bounds their number as it does for kernel E); a pair that alone needs more
+ * runs alone, and if its allocation fails the call ends with RATTLE_ERR_HIP and nothing is returned.  The result depends on neither.
+ * Errors: those of rattle_hip_align_pairs, checked in the same order before the context is looked at; cigars == NULL is RATTLE_ERR_ARG.
+ * rattle_hip_kernel_stats: kernel F is id 7, one launch per sub-chunk (the gather of the ops is not counted); kernel E's launches of the
+ * call count under id 6 as before.  alg_bytes of id 7, per aligned pair with R = q_end - q_start rows and C = t_end - t_start columns:
+ *   R + C  (the rectangle's sequence bytes)  +  16 * (ceil(R / 64) * (C - 1) + R)  (code records written)  +  4 * ops  +  4  (the count)
+ */
+typedef struct { uint32_t n; uint64_t *offset /* n + 1 */; uint32_t *ops /* len << 4 | op */; } rattle_cigars;
+int  rattle_hip_align_cigars(rattle_ctx *ctx, const uint8_t *target_concat, const uint64_t *target_offsets, uint32_t n_targets,
+                             const uint8_t *read_concat, const uint64_t *read_offsets, uint32_t n_reads,
+                             const int32_t *target_of_read /* -1: not submitted */, const uint8_t *rev,
+                             const rattle_align_params *params, rattle_alignment **out, rattle_cigars **cigars);
+void rattle_hip_cigars_free(rattle_cigars *c);
+
+/* ------------------------------------------------------------------------------------
  * a15  spoa engine + graph as called from /root/reference/correct.cpp:395-405,428-436,520-532
  * (createAlignmentEngine(kSW,5,-4,-8,-6); align + add_alignment per sequence;
  * generate_multiple_sequence_alignment).  Packs are independent; pack p holds sequences
@@ -619,7 +646,7 @@ void rattle_hip_debug_consensus_support_free(rattle_debug_support *d);
  * Per-kernel timing measured with HIP events on the stream the kernels run on.
  * kernel: 0 kmer_extract, 1 bv_filter, 2 pair_score, 3 poa_align, 4 post_msa, 5 the per-read reduction of
  * assign (alg_bytes: the bytes of its records copied to the host), 6 pair_align (kernel E; alg_bytes: the sequence bytes read plus
- * the record bytes written).  Accumulated since
+ * the record bytes written), 7 pair_cigar (kernel F; alg_bytes: see align_cigars).  Accumulated since
  * the last reset: total milliseconds, number of launches, algorithmic bytes moved.
  */
 int rattle_hip_kernel_stats(rattle_ctx *ctx, int kernel, double *total_ms, uint64_t *launches, uint64_t *alg_bytes);

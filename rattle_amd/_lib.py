@@ -158,6 +158,11 @@ class Alignment(C.Structure):
     _fields_ = [("n", C.c_uint32)] + [(f, C.POINTER(t)) for f, t in ALIGN_FIELDS]
 
 
+# the CIGARs of align_cigars (rattle_cigars): ops[offset[r] .. offset[r + 1]) of read r, each len << 4 | op
+class Cigars(C.Structure):
+    _fields_ = [("n", C.c_uint32), ("offset", C.POINTER(C.c_uint64)), ("ops", C.POINTER(C.c_uint32))]
+
+
 # int fn(void *user, const void *send, uint64 send_bytes, void *recv, const uint64 *recv_bytes)
 ALLGATHERV_FN = C.CFUNCTYPE(C.c_int, C.c_void_p, C.c_void_p, C.c_uint64, C.c_void_p, C.POINTER(C.c_uint64))
 
@@ -207,6 +212,9 @@ SIGNATURES = {
     "rattle_hip_align_pairs": (C.c_int, [C.c_void_p, _u8p, _u64p, C.c_uint32, _u8p, _u64p, C.c_uint32, _i32p, _u8p, _P(AlignParams),
                                          _P(_P(Alignment))]),
     "rattle_hip_alignment_free": (None, [_P(Alignment)]),
+    "rattle_hip_align_cigars": (C.c_int, [C.c_void_p, _u8p, _u64p, C.c_uint32, _u8p, _u64p, C.c_uint32, _i32p, _u8p, _P(AlignParams),
+                                          _P(_P(Alignment)), _P(_P(Cigars))]),
+    "rattle_hip_cigars_free": (None, [_P(Cigars)]),
     "rattle_hip_poa_msa": (C.c_int, [C.c_void_p, _u8p, _u64p, C.c_uint32, _u32p, C.c_uint32, _P(_P(MsaSet))]),
     "rattle_hip_msa_set_free": (None, [_P(MsaSet)]),
     "rattle_hip_correct_reads": (C.c_int, [C.c_void_p, _u8p, _u8p, _u64p, C.c_uint32, C.c_uint32, _u32p, _i32p, _u8p,

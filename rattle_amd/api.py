@@ -18,7 +18,7 @@ import numpy as np
 from . import _lib
 from ._lib import ClusterParams, ClusterSet, Correction, CorrectParams, MsaSet, check
 
-K_KMER, K_FILTER, K_SCORE, K_POA, K_POST, K_ASSIGN, K_ALIGN = 0, 1, 2, 3, 4, 5, 6
+K_KMER, K_FILTER, K_SCORE, K_POA, K_POST, K_ASSIGN, K_ALIGN, K_CIGAR = 0, 1, 2, 3, 4, 5, 6, 7
 
 
 def _ptr(a: np.ndarray, t):
@@ -638,6 +638,39 @@ class Context:
         self.lib.rattle_hip_alignment_free(out)
         return res
 
+    def align_cigars(self, targets: Sequence[bytes], reads: Sequence[bytes], target_of_read, rev, max_cells=0, pair_chunk=0):
+        """align_pairs(), and the CIGAR of every read that aligns (rattle_hip_align_cigars, kernels E and F).  Returns (records, offsets,
+        ops): the dict align_pairs returns for the same arguments, and the ops of read r as ops[offsets[r]:offsets[r + 1]], uint32
+        len << 4 | op with BAM's numbers (= 7, X 8, I 1, D 2), from the alignment's start to its end on the strand that was aligned
+        (cigar_bytes formats them).  A read whose status is not 0 has none."""
+        tcat, toff = pack_reads(targets)
+        rcat, roff = pack_reads(reads)
+        return self.align_cigars_packed(tcat, toff, rcat, roff, target_of_read, rev, max_cells, pair_chunk)
+
+    def align_cigars_packed(self, tcat: np.ndarray, toff: np.ndarray, rcat: np.ndarray, roff: np.ndarray, target_of_read, rev,
+                            max_cells=0, pair_chunk=0):
+        """align_cigars() on packed arrays (pack_reads)"""
+        P = _lib.AlignParams(int(max_cells), int(pair_chunk))
+        n = len(roff) - 1
+        t = np.ascontiguousarray(target_of_read, np.int32)
+        r = np.ascontiguousarray(rev, np.uint8)
+        if len(t) != n or len(r) != n:
+            raise ValueError("target_of_read and rev need one entry per read")
+        out = C.POINTER(_lib.Alignment)()
+        cg = C.POINTER(_lib.Cigars)()
+        check(self.lib.rattle_hip_align_cigars(self.h, _ptr(tcat, C.c_uint8) if len(tcat) else None, _ptr(toff, C.c_uint64), len(toff) - 1,
+                                               _ptr(rcat, C.c_uint8) if len(rcat) else None, _ptr(roff, C.c_uint64), n,
+                                               _ptr(t, C.c_int32) if n else None, _ptr(r, C.c_uint8) if n else None, C.byref(P), C.byref(out),
+                                               C.byref(cg)))
+        m = int(out.contents.n)
+        res = {f: np.ctypeslib.as_array(getattr(out.contents, f), (max(m, 1),))[:m].copy() for f, _ in _lib.ALIGN_FIELDS}
+        offsets = np.ctypeslib.as_array(cg.contents.offset, (m + 1,)).copy()
+        total = int(offsets[m])
+        ops = np.ctypeslib.as_array(cg.contents.ops, (max(total, 1),))[:total].copy()
+        self.lib.rattle_hip_alignment_free(out)
+        self.lib.rattle_hip_cigars_free(cg)
+        return res, offsets, ops
+
     def debug_evaluate(self, rects, t_s=0.2, t_v=1000000.0, use_hc=False, is_rna=False, count_pass="auto"):
         """One evaluation of the greedy clustering on the loaded reads (rattle_hip_debug_evaluate, a test hook).
         rects: list of (seed_ids, cand_ids, thr); cand_ids None = triangular (the seeds against each other, pairs s < c).
@@ -965,34 +998,50 @@ def assign_command(ctx: Context, read_headers: Sequence[bytes], reads: Sequence[
     return (assignments_tsv([_first_token(h) for h in read_headers], tn, rec), target_counts_tsv(tn, [len(s) for s in targets], rec))
 
 
+_CIGAR_LETTER = {1: b"I", 2: b"D", 7: b"=", 8: b"X"}
+
+
+def cigar_bytes(ops) -> bytes:
+    """the ops of one read (align_cigars: len << 4 | op) as a CIGAR string, b"12=1X3I...": the extended set, no clipping op"""
+    return b"".join(b"%d%s" % (int(o) >> 4, _CIGAR_LETTER[int(o) & 15]) for o in ops)
+
+
 def paf_text(read_names: Sequence[bytes], read_lengths: Sequence[int], target_names: Sequence[bytes], target_lengths: Sequence[int],
-             assignment: dict, alignment: dict) -> bytes:
+             assignment: dict, alignment: dict, cigars=None) -> bytes:
     """alignments.paf as `rattle assign --paf` writes it: one line per read with status 0, in file order (none for unassigned, unaligned
     or skipped reads): read, Lq, q_start, q_end, + / -, target, Lt, t_start, t_end, matches, columns (matches + mismatches + q_gap +
-    t_gap), 255, AS:i:score, NM:i:mismatches + q_gap + t_gap, nx:i:mismatches, ni:i:q_gap, nd:i:t_gap."""
+    t_gap), 255, AS:i:score, NM:i:mismatches + q_gap + t_gap, nx:i:mismatches, ni:i:q_gap, nd:i:t_gap.  cigars: (offsets, ops) of
+    align_cigars; with them every line ends in a further tag, cg:Z:<the read's CIGAR> (`--paf --cigar`)."""
     lines = []
+    tag = (lambda i: b"") if cigars is None else (lambda i: b"\tcg:Z:" + cigar_bytes(cigars[1][int(cigars[0][i]):int(cigars[0][i + 1])]))
     for i in np.nonzero(np.asarray(alignment["status"]) == 0)[0]:
         t = int(assignment["target"][i])
         M, X, qg, tg = (int(alignment[f][i]) for f in ("matches", "mismatches", "q_gap", "t_gap"))
-        lines.append(b"%s\t%d\t%d\t%d\t%s\t%s\t%d\t%d\t%d\t%d\t%d\t255\tAS:i:%d\tNM:i:%d\tnx:i:%d\tni:i:%d\tnd:i:%d\n" % (
+        lines.append(b"%s\t%d\t%d\t%d\t%s\t%s\t%d\t%d\t%d\t%d\t%d\t255\tAS:i:%d\tNM:i:%d\tnx:i:%d\tni:i:%d\tnd:i:%d%s\n" % (
             read_names[i], int(read_lengths[i]), int(alignment["q_start"][i]), int(alignment["q_end"][i]),
             b"-" if assignment["rev"][i] else b"+", target_names[t], int(target_lengths[t]), int(alignment["t_start"][i]),
-            int(alignment["t_end"][i]), M, M + X + qg + tg, int(alignment["score"][i]), X + qg + tg, X, qg, tg))
+            int(alignment["t_end"][i]), M, M + X + qg + tg, int(alignment["score"][i]), X + qg + tg, X, qg, tg, tag(i)))
     return b"".join(lines)
 
 
 def assign_paf_command(ctx: Context, read_headers: Sequence[bytes], reads: Sequence[bytes], target_headers: Sequence[bytes],
                        targets: Sequence[bytes], *, k=10, t_s=0.2, t_v=1000000.0, bv_threshold=0.4, is_rna=False, count_pass="auto",
-                       target_batch=0, read_chunk=0, max_cells=0, pair_chunk=0):
+                       target_batch=0, read_chunk=0, max_cells=0, pair_chunk=0, cigar=False):
     """`rattle assign --paf`: assign_command, then every placed read aligned to its transcript (Context.align_pairs).  Returns the bytes
-    of assignments.tsv, target_counts.tsv and alignments.paf; the first two are what assign_command returns."""
+    of assignments.tsv, target_counts.tsv and alignments.paf; the first two are what assign_command returns.  cigar=True is
+    `--paf --cigar`: Context.align_cigars, and a cg:Z: tag on every line."""
     sent = [i for i, s in enumerate(reads) if not s.translate(None, b"ACGTU")]
     got = ctx.assign(targets, [reads[i] for i in sent], k, t_s, t_v, bv_threshold, False, is_rna, target_batch, read_chunk, count_pass)
     rec = unassigned_records(len(reads))
     for f in rec:
         rec[f][sent] = got[f]
-    aln = ctx.align_pairs(targets, reads, rec["target"], rec["rev"], max_cells, pair_chunk)
+    cigars = None
+    if cigar:
+        aln, offsets, ops = ctx.align_cigars(targets, reads, rec["target"], rec["rev"], max_cells, pair_chunk)
+        cigars = (offsets, ops)
+    else:
+        aln = ctx.align_pairs(targets, reads, rec["target"], rec["rev"], max_cells, pair_chunk)
     tn = [_first_token(h) for h in target_headers]
     rn = [_first_token(h) for h in read_headers]
     tl = [len(s) for s in targets]
-    return (assignments_tsv(rn, tn, rec), target_counts_tsv(tn, tl, rec), paf_text(rn, [len(s) for s in reads], tn, tl, rec, aln))
+    return (assignments_tsv(rn, tn, rec), target_counts_tsv(tn, tl, rec), paf_text(rn, [len(s) for s in reads], tn, tl, rec, aln, cigars))

@@ -630,31 +630,28 @@ void rattle_hip_assignment_free(rattle_assignment *a) {
     free(a);
 }
 
-// ---- align_pairs (kernel E) -----------------------------------------------------------------------------------------------
-int rattle_hip_align_pairs(rattle_ctx *c, const uint8_t *tseq, const uint64_t *toff, uint32_t nt, const uint8_t *rseq, const uint64_t *roff,
-                           uint32_t nr, const int32_t *target, const uint8_t *rev, const rattle_align_params *P, rattle_alignment **out) {
-    if (out) *out = nullptr;
-    if (!c || !P || !out || !toff || !roff || (nr && (!target || !rev)) || (!tseq && toff[nt] != toff[0]) || (!rseq && roff[nr] != roff[0])) {
-        set_error("null argument");
-        return RATTLE_ERR_ARG;
-    }
+// ---- align_pairs (kernel E), align_cigars (kernels E and F) ---------------------------------------------------------------
+// the body of both entry points; `who` names the entry point in the messages, `run` (align_cigars) takes the ops of kernel F
+static int align_entry(const char *who, rattle_ctx *c, const uint8_t *tseq, const uint64_t *toff, uint32_t nt, const uint8_t *rseq, const uint64_t *roff,
+                       uint32_t nr, const int32_t *target, const uint8_t *rev, const rattle_align_params *P, rattle_alignment **out, cigar_run *run) {
+    const std::string w = std::string(who) + ": ";
     // the arguments, on the host: indices, strands, lengths, and the letters of every sequence that is submitted (a target once)
     auto clean = [](const uint8_t *s, uint64_t n) { for (uint64_t i = 0; i < n; ++i) if (!s[i] || !strchr("ACGTU", s[i])) return false; return true; };
     std::vector<uint8_t> seen(nt, 0);
     for (uint32_t r = 0; r < nr; ++r) {
         const int32_t t = target[r];
         if (t < 0) continue;
-        if ((uint32_t)t >= nt) { set_error("align_pairs: read " + std::to_string(r) + " names target " + std::to_string(t) + " of " + std::to_string(nt)); return RATTLE_ERR_ARG; }
-        if (rev[r] > 1) { set_error("align_pairs: rev of read " + std::to_string(r) + " is neither 0 nor 1"); return RATTLE_ERR_ARG; }
-        if (roff[r + 1] - roff[r] >= (1ull << 31) || toff[t + 1] - toff[t] >= (1ull << 31)) { set_error("align_pairs: a sequence of 2^31 bases or more"); return RATTLE_ERR_ARG; }
-        if (!clean(rseq + roff[r], roff[r + 1] - roff[r])) { set_error("align_pairs: read " + std::to_string(r) + " has a base other than A, C, G, T, U"); return RATTLE_ERR_ARG; }
+        if ((uint32_t)t >= nt) { set_error(w + "read " + std::to_string(r) + " names target " + std::to_string(t) + " of " + std::to_string(nt)); return RATTLE_ERR_ARG; }
+        if (rev[r] > 1) { set_error(w + "rev of read " + std::to_string(r) + " is neither 0 nor 1"); return RATTLE_ERR_ARG; }
+        if (roff[r + 1] - roff[r] >= (1ull << 31) || toff[t + 1] - toff[t] >= (1ull << 31)) { set_error(w + "a sequence of 2^31 bases or more"); return RATTLE_ERR_ARG; }
+        if (!clean(rseq + roff[r], roff[r + 1] - roff[r])) { set_error(w + "read " + std::to_string(r) + " has a base other than A, C, G, T, U"); return RATTLE_ERR_ARG; }
         if (!seen[t]) {
-            if (!clean(tseq + toff[t], toff[t + 1] - toff[t])) { set_error("align_pairs: target " + std::to_string(t) + " has a base other than A, C, G, T, U"); return RATTLE_ERR_ARG; }
+            if (!clean(tseq + toff[t], toff[t + 1] - toff[t])) { set_error(w + "target " + std::to_string(t) + " has a base other than A, C, G, T, U"); return RATTLE_ERR_ARG; }
             seen[t] = 1;
         }
     }
     if (c->xchg.nranks > 1) {
-        set_error("align_pairs is not available on a context that is one rank of several: sharded jobs are not built, align on one device");
+        set_error(std::string(who) + " is not available on a context that is one rank of several: sharded jobs are not built, align on one device");
         return RATTLE_ERR_STATE;
     }
     RT_TRY(use_device(c));
@@ -663,10 +660,48 @@ int rattle_hip_align_pairs(rattle_ctx *c, const uint8_t *tseq, const uint64_t *t
     A->n = nr;
     A->status = (uint8_t *)calloc(m, 1); A->score = (int32_t *)calloc(m, 4);
     for (uint32_t **f : {&A->q_start, &A->q_end, &A->t_start, &A->t_end, &A->matches, &A->mismatches, &A->q_gap, &A->t_gap}) *f = (uint32_t *)calloc(m, 4);
-    const int rc = align_pairs_run(c, tseq, toff, nt, rseq, roff, nr, target, rev, P, A);
+    if (run) { run->count.assign(nr, 0); run->ops.clear(); run->code_cap = cigar_code_cap(); }
+    const int rc = align_pairs_run(c, tseq, toff, nt, rseq, roff, nr, target, rev, P, A, run);
     if (rc != 0) { rattle_hip_alignment_free(A); return rc; }
     *out = A;
     return 0;
+}
+
+int rattle_hip_align_pairs(rattle_ctx *c, const uint8_t *tseq, const uint64_t *toff, uint32_t nt, const uint8_t *rseq, const uint64_t *roff,
+                           uint32_t nr, const int32_t *target, const uint8_t *rev, const rattle_align_params *P, rattle_alignment **out) {
+    if (out) *out = nullptr;
+    if (!c || !P || !out || !toff || !roff || (nr && (!target || !rev)) || (!tseq && toff[nt] != toff[0]) || (!rseq && roff[nr] != roff[0])) {
+        set_error("null argument");
+        return RATTLE_ERR_ARG;
+    }
+    return align_entry("align_pairs", c, tseq, toff, nt, rseq, roff, nr, target, rev, P, out, nullptr);
+}
+
+int rattle_hip_align_cigars(rattle_ctx *c, const uint8_t *tseq, const uint64_t *toff, uint32_t nt, const uint8_t *rseq, const uint64_t *roff,
+                            uint32_t nr, const int32_t *target, const uint8_t *rev, const rattle_align_params *P, rattle_alignment **out,
+                            rattle_cigars **cigars) {
+    if (out) *out = nullptr;
+    if (cigars) *cigars = nullptr;
+    if (!c || !P || !out || !cigars || !toff || !roff || (nr && (!target || !rev)) || (!tseq && toff[nt] != toff[0]) || (!rseq && roff[nr] != roff[0])) {
+        set_error("null argument");
+        return RATTLE_ERR_ARG;
+    }
+    cigar_run run;
+    RT_TRY(align_entry("align_cigars", c, tseq, toff, nt, rseq, roff, nr, target, rev, P, out, &run));
+    rattle_cigars *G = (rattle_cigars *)calloc(1, sizeof(rattle_cigars));
+    G->n = nr;
+    G->offset = (uint64_t *)calloc((size_t)nr + 1, 8);
+    G->ops = (uint32_t *)calloc(std::max<size_t>(1, run.ops.size()), 4);
+    for (uint32_t r = 0; r < nr; ++r) G->offset[r + 1] = G->offset[r] + run.count[r];
+    if (!run.ops.empty()) memcpy(G->ops, run.ops.data(), run.ops.size() * 4);
+    *cigars = G;
+    return 0;
+}
+
+void rattle_hip_cigars_free(rattle_cigars *g) {
+    if (!g) return;
+    free(g->offset); free(g->ops);
+    free(g);
 }
 
 void rattle_hip_alignment_free(rattle_alignment *a) {

@@ -129,7 +129,7 @@ struct hbuf {
     }
 };
 
-enum { K_KMER = 0, K_FILTER = 1, K_SCORE = 2, K_POA = 3, K_POST = 4, K_ASSIGN = 5, K_ALIGN = 6, K_COUNT = 7 };
+enum { K_KMER = 0, K_FILTER = 1, K_SCORE = 2, K_POA = 3, K_POST = 4, K_ASSIGN = 5, K_ALIGN = 6, K_CIGAR = 7, K_COUNT = 8 };
 
 struct kstat {
     double ms = 0;
@@ -503,9 +503,37 @@ int debug_evaluate(rattle_ctx *ctx, const rattle_cluster_params *P, int count_mo
 // records [out_base, out_base + n_reads) of A: the loaded reads read_ids placed on the loaded reads target_ids
 int assign_driver(rattle_ctx *ctx, const rattle_assign_params *P, const uint32_t *target_ids, uint32_t n_targets, const uint32_t *read_ids,
                   uint32_t n_reads, rattle_assignment *A, uint32_t out_base);
-// pair_align.hip : kernel E, the local alignment of every submitted read on its target; fills every array of A (arguments checked by the caller)
+// pair_cigar.hip : kernel F, the CIGAR of every pair kernel E aligned, chunk by chunk of kernel E while its sequences are on the device
+struct cigar_pair {                     // one pair of a launch: where its rectangle's sequences, code records, strip and ops region lie
+    uint64_t q, t;                      // byte offsets of the rectangle's first row (reverse strand: its last base as given) and first column
+    uint64_t codes, strip, ops;         // offsets in 16-byte records, in 4-byte words, in 4-byte words
+    uint32_t rows, cols, rev, pad;
+};
+struct cigar_in {                       // one pair of kernel E's chunk, from its record
+    uint64_t q, t;
+    uint32_t rows, cols, read;          // q_end - q_start, t_end - t_start, the read the ops belong to
+    uint8_t status, rev;
+};
+struct cigar_run {                      // one call of rattle_hip_align_cigars: the result so far and the buffers, kept from chunk to chunk
+    uint64_t code_cap = 0;              // cap on a sub-chunk's code bytes
+    std::vector<uint32_t> count;        // [n_reads] ops of every read
+    std::vector<uint32_t> ops;          // the ops of all reads, in read order
+    dbuf<cigar_pair> d_pairs;
+    dbuf<uint4> d_codes;
+    dbuf<int32_t> d_strip;
+    dbuf<uint32_t> d_ops, d_count, d_out;
+    dbuf<uint64_t> d_off;
+    hbuf<cigar_pair> h_pairs;
+    hbuf<uint32_t> h_count, h_out;
+    hbuf<uint64_t> h_off;
+};
+uint64_t cigar_code_cap();              // 4 GiB, or what RATTLE_CIGAR_CODE_BYTES says
+int pair_cigar_chunk(rattle_ctx *ctx, const uint8_t *d_q, const uint8_t *d_t, const cigar_in *in, uint32_t n, uint32_t pair_chunk, cigar_run &R);
+// pair_align.hip : kernel E, the local alignment of every submitted read on its target; fills every array of A (arguments checked by the caller).
+// With `cigars`, every chunk goes on to kernel F before its sequences leave the device (cigars->count sized n_reads by the caller).
 int align_pairs_run(rattle_ctx *ctx, const uint8_t *tseq, const uint64_t *toff, uint32_t n_targets, const uint8_t *rseq, const uint64_t *roff,
-                    uint32_t n_reads, const int32_t *target, const uint8_t *rev, const rattle_align_params *P, rattle_alignment *A);
+                    uint32_t n_reads, const int32_t *target, const uint8_t *rev, const rattle_align_params *P, rattle_alignment *A,
+                    cigar_run *cigars = nullptr);
 
 // correct_driver.hip
 int debug_post_msa(rattle_ctx *ctx, const rattle_correct_params *P, int mode, const rattle_debug_msa *in, rattle_debug_post **out);

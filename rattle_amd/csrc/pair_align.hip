@@ -127,9 +127,10 @@ __global__ __launch_bounds__(256) void pair_align_kernel(const align_pair *__res
 
 // Every read r with target_of_read[r] >= 0, both sequences non-empty and (max_cells == 0 or lq * lt <= max_cells) is aligned; the arguments
 // have been checked (abi.hip).  Fills every array of A.  The plan -- statuses settled without the device, strip records, chunks -- is
-// align_plan.h's; the strip buffer is sized from the lengths of the chunk.
+// align_plan.h's; the strip buffer is sized from the lengths of the chunk.  With `cigars` (rattle_hip_align_cigars) every chunk's records go on
+// to kernel F (pair_cigar.hip) while the chunk's sequences are on the device; A is filled exactly as without.
 int align_pairs_run(rattle_ctx *ctx, const uint8_t *tseq, const uint64_t *toff, uint32_t nt, const uint8_t *rseq, const uint64_t *roff, uint32_t nr,
-                    const int32_t *target, const uint8_t *rev, const rattle_align_params *AP, rattle_alignment *A) {
+                    const int32_t *target, const uint8_t *rev, const rattle_align_params *AP, rattle_alignment *A, cigar_run *cigars) {
     phase_timer T_all("align_pairs: total");
     align_plan plan;
     plan_align(toff, roff, nr, target, AP->max_cells, AP->pair_chunk ? AP->pair_chunk : 32768u, 1ull << 26 /* 1 GiB of records */, plan);
@@ -182,6 +183,20 @@ int align_pairs_run(rattle_ctx *ctx, const uint8_t *tseq, const uint64_t *toff, 
             A->status[r] = (uint8_t)R[0]; A->score[r] = R[1];
             A->q_start[r] = (uint32_t)R[2]; A->q_end[r] = (uint32_t)R[3]; A->t_start[r] = (uint32_t)R[4]; A->t_end[r] = (uint32_t)R[5];
             A->matches[r] = (uint32_t)R[6]; A->mismatches[r] = (uint32_t)R[7]; A->q_gap[r] = (uint32_t)R[8]; A->t_gap[r] = (uint32_t)R[9];
+        }
+        if (cigars) {
+            // kernel F on the chunk's rectangles, while d_q and d_t hold its sequences: rows (q_start, q_end] of the read as given, taken from
+            // its far end on the reverse strand, and columns (t_start, t_end] of the target
+            std::vector<cigar_in> in(n);
+            for (uint32_t i = 0; i < n; ++i) {
+                const uint32_t r = sub[a + i];
+                const align_pair &P = h_pairs.p[i];
+                cigar_in &I = in[i];
+                I.status = A->status[r]; I.rev = rev[r]; I.read = r;
+                I.rows = A->q_end[r] - A->q_start[r]; I.cols = A->t_end[r] - A->t_start[r];
+                I.q = P.q + (P.rev ? (uint64_t)A->q_end[r] - (I.rows ? 1 : 0) : (uint64_t)A->q_start[r]); I.t = P.t + A->t_start[r];
+            }
+            RT_TRY(pair_cigar_chunk(ctx, d_q.p, d_t.p, in.data(), n, AP->pair_chunk ? AP->pair_chunk : 32768u, *cigars));
         }
     }
     return 0;

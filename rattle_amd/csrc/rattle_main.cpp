@@ -781,7 +781,7 @@ struct assign_job {
     byte_buf rcat, xcat;
     std::vector<uint64_t> roff, xoff;
     rattle_assignment *A = nullptr;
-    bool want_paf = false;
+    bool want_paf = false, want_cigar = false;     // --paf, --cigar (cg:Z: on every PAF line)
     rattle_align_params AP;
     std::string text, counts, paf;                // assignments.tsv, target_counts.tsv, alignments.paf (--paf)
     void options(int argc, char **argv) {
@@ -791,8 +791,8 @@ struct assign_job {
             {"t_v", {"-v", "--max-variance"}, true}, {"bv_threshold", {"-B", "--bv-start-threshold"}, true}, {"rna", {"--rna"}, false},
             {"count-pass", {"--count-pass"}, true}, {"device", {"--device"}, true}, {"devices", {"--devices"}, true},
             {"target-batch", {"--target-batch"}, true}, {"read-chunk", {"--read-chunk"}, true}, {"paf", {"--paf"}, false},
-            {"paf-max-cells", {"--paf-max-cells"}, true}});
-        const char *usage = "rattle assign -i reads.fq -x transcripts.fq [-o dir] [-k 10] [-s 0.2] [-v 1000000] [-B 0.4] [--rna] [--device n] [--paf]\n"
+            {"paf-max-cells", {"--paf-max-cells"}, true}, {"cigar", {"--cigar"}, false}});
+        const char *usage = "rattle assign -i reads.fq -x transcripts.fq [-o dir] [-k 10] [-s 0.2] [-v 1000000] [-B 0.4] [--rna] [--device n] [--paf [--cigar]]\n"
                             "  places every read of -i on the transcript of -x that accepts it with the best score (the comparison `cluster` joins\n"
                             "  reads by, the transcript in the seed's role) and writes assignments.tsv (one line per read: target, strand, score,\n"
                             "  second_score, n_accepted, bases, hc_bases, min_len, variance) and target_counts.tsv (reads per transcript)\n"
@@ -800,7 +800,9 @@ struct assign_job {
                             "  --target-batch n / --read-chunk n     transcripts per evaluation / reads indexed at a time (the result does not depend on them)\n"
                             "  --paf                                 also align every placed read to its transcript (local, match 5, mismatch -4, gap -8 per\n"
                             "                                        column) and write alignments.paf: one PAF line per aligned read, in file order\n"
-                            "  --paf-max-cells n                     with --paf: skip a read whose length x its transcript's length exceeds n (default 0: no limit)\n";
+                            "  --paf-max-cells n                     with --paf: skip a read whose length x its transcript's length exceeds n (default 0: no limit)\n"
+                            "  --cigar                               with --paf: end every line of alignments.paf with cg:Z:<CIGAR>, the alignment's columns\n"
+                            "                                        in the extended set (= match, X mismatch, I read base on a gap, D transcript base on a gap)\n";
         if (a.has("help")) { std::cerr << usage; exit(EXIT_SUCCESS); }
         if (!a.has("input")) die("ERROR: No input file provided (-i reads)");
         if (!a.has("targets")) die("ERROR: No transcript file provided (-x transcripts)");
@@ -814,6 +816,8 @@ struct assign_job {
         P.is_rna = a.has("rna") ? 1 : 0;
         want_paf = a.has("paf");
         if (a.has("paf-max-cells") && !want_paf) die("\nError: --paf-max-cells needs --paf\n");
+        want_cigar = a.has("cigar");
+        if (want_cigar && !want_paf) die("\nError: --cigar needs --paf\n");
         memset(&AP, 0, sizeof AP);
         AP.max_cells = std::stoull(a.str("paf-max-cells", "0"));
         P.target_batch = (uint32_t)std::max(0, a.i("target-batch", 0)); P.read_chunk = (uint32_t)std::max(0, a.i("read-chunk", 0));
@@ -842,9 +846,11 @@ struct assign_job {
     }
     // --paf: the submitted reads on the transcripts `run` placed them on; one PAF line per read that aligns, in file order
     void align() {
-        cli_timer t("library: align_pairs");
+        cli_timer t(want_cigar ? "library: align_cigars" : "library: align_pairs");
         rattle_alignment *L = nullptr;
-        chk(rattle_hip_align_pairs(team.ctx[0], xcat.data(), xoff.data(), (uint32_t)xid.size(), rcat.data(), roff.data(), (uint32_t)rid.size(), A->target, A->rev, &AP, &L));
+        rattle_cigars *G = nullptr;
+        if (want_cigar) chk(rattle_hip_align_cigars(team.ctx[0], xcat.data(), xoff.data(), (uint32_t)xid.size(), rcat.data(), roff.data(), (uint32_t)rid.size(), A->target, A->rev, &AP, &L, &G));
+        else chk(rattle_hip_align_pairs(team.ctx[0], xcat.data(), xoff.data(), (uint32_t)xid.size(), rcat.data(), roff.data(), (uint32_t)rid.size(), A->target, A->rev, &AP, &L));
         uint64_t skipped = 0;
         for (uint32_t at = 0; at < L->n; ++at) {
             skipped += L->status[at] == 2;
@@ -855,9 +861,18 @@ struct assign_job {
                    (A->rev[at] ? "-" : "+") + "\t" + record_name(X.header[x]) + "\t" + std::to_string(X.seq[x].n) + "\t" + std::to_string(L->t_start[at]) + "\t" +
                    std::to_string(L->t_end[at]) + "\t" + std::to_string(L->matches[at]) + "\t" + std::to_string(cols) + "\t255\tAS:i:" + std::to_string(L->score[at]) +
                    "\tNM:i:" + std::to_string(L->mismatches[at] + gaps) + "\tnx:i:" + std::to_string(L->mismatches[at]) + "\tni:i:" + std::to_string(L->q_gap[at]) +
-                   "\tnd:i:" + std::to_string(L->t_gap[at]) + "\n";
+                   "\tnd:i:" + std::to_string(L->t_gap[at]);
+            if (G) {
+                paf += "\tcg:Z:";
+                for (uint64_t o = G->offset[at]; o < G->offset[at + 1]; ++o) {
+                    const uint32_t op = G->ops[o] & 15u;
+                    paf += std::to_string(G->ops[o] >> 4) + (op == 7 ? "=" : op == 8 ? "X" : op == 1 ? "I" : "D");
+                }
+            }
+            paf += "\n";
         }
         rattle_hip_alignment_free(L);
+        rattle_hip_cigars_free(G);
         if (skipped) std::cerr << "\n" << skipped << "  reads over --paf-max-cells are left out of alignments.paf" << std::endl;
     }
     // one line per read of -i, the reads that were not submitted included; then one line per transcript
