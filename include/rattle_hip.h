@@ -239,7 +239,8 @@ void rattle_hip_assignment_free(rattle_assignment *a);
  * submitted), reverse-complemented first when rev[r] == 1 (A<->T, C<->G, U complements to A).  Only A, C, G, T, U occur; two letters
  * match iff they are equal after U is read as T.  The alignment is a Smith-Waterman local alignment with match +5, mismatch -4 and
  * gap -8 PER GAPPED COLUMN: the match, mismatch and gap-open values of `correct`'s engine (a15), but with LINEAR gaps, deliberately not
- * affine -- that is what makes the record below derivable without a traceback (the device writes no traceback matrix):
+ * affine (affine gaps and other scorings: rattle_hip_align_pairs_scored, below) -- that is what makes the record below derivable
+ * without a traceback (the device writes no traceback matrix):
  *   H[i][j] = max(0, H[i-1][j-1] + s(q_i, t_j), H[i-1][j] - 8, H[i][j-1] - 8),  H[0][*] = H[*][0] = 0,  i over the read, j over the target
  * and it is fully determined: a cell with H == 0 begins a new alignment (a path never runs through a zero); predecessors that tie are
  * taken diagonal, then up (a read base against a gap), then left (a target base against a gap); the end cell is the largest H, ties to
@@ -292,6 +293,38 @@ int  rattle_hip_align_cigars(rattle_ctx *ctx, const uint8_t *target_concat, cons
                              const int32_t *target_of_read /* -1: not submitted */, const uint8_t *rev,
                              const rattle_align_params *params, rattle_alignment **out, rattle_cigars **cigars);
 void rattle_hip_cigars_free(rattle_cigars *c);
+
+/* ------------------------------------------------------------------------------------
+ * align_pairs_scored, align_cigars_scored: the two calls above with AFFINE gaps and a scoring the caller chooses (the three-state forms
+ * of kernels E and F, csrc/pair_align_affine.hip and csrc/pair_cigar_affine.hip).  The scoring is four positive magnitudes, spoa's
+ * convention: match +match, mismatch -mismatch, the first gapped column of a gap -gap_open, every further one -gap_extend;
+ *   1 <= match <= 64, 1 <= mismatch <= 64, 1 <= gap_extend <= gap_open <= 64
+ * so {5, 4, 8, 6} is `correct`'s engine, {5, 4, 8, 8} the linear rule of align_pairs and {2, 4, 4, 2} minimap2's.  Gotoh's recurrence:
+ *   U[i][j] = max(H[i-1][j] - open, U[i-1][j] - extend)     a read base against a gap      U[0][*] = -inf
+ *   L[i][j] = max(H[i][j-1] - open, L[i][j-1] - extend)     a target base against a gap    L[*][0] = -inf
+ *   H[i][j] = max(0, H[i-1][j-1] + s(q_i, t_j), U[i][j], L[i][j])                          H[0][*] = H[*][0] = 0
+ * fully determined as align_pairs is: a cell with H == 0 begins a new alignment; in H ties go diagonal, then U, then L; in U and in L
+ * OPEN WINS A TIE WITH EXTEND; the end cell is the largest H, ties to the smallest i, then the smallest j.  Since H >= U and H >= L, no
+ * path runs through a cell whose H is 0, and with gap_open == gap_extend the path is cell for cell the linear one.  The structs returned,
+ * their fields and their free functions are those of align_pairs and align_cigars; every state of every cell carries (start_i, start_j,
+ * matches, mismatches) of its path, and q_gap, t_gap follow from the spans.  A CIGAR's 'I' and 'D' runs are the gaps of the path.
+ * These two ALWAYS run the three-state kernels, for {5, 4, 8, 8} too (ids 8 and 9 of rattle_hip_kernel_stats; ids 6 and 7 do not move):
+ * alg_bytes of id 8 is that of id 6, of id 9 that of id 7 with 32 in place of 16 (4 bits per cell: H's 2-bit code, "U extends",
+ * "L extends").  The strip of id 8 takes 40 bytes per column of a read longer than 64 bases, that of id 9 8 bytes.
+ * Errors: those of rattle_hip_align_pairs (rattle_hip_align_cigars), checked in the same order; then, still before the device is looked
+ * at, RATTLE_ERR_ARG for scoring == NULL, a magnitude outside the limits above or gap_extend > gap_open, and a submitted pair with
+ * match * min(Lq, Lt) > 2^31 - 1 (its score might not fit the record).
+ */
+typedef struct { uint32_t match, mismatch, gap_open, gap_extend; } rattle_align_scoring;
+int  rattle_hip_align_pairs_scored(rattle_ctx *ctx, const uint8_t *target_concat, const uint64_t *target_offsets, uint32_t n_targets,
+                                   const uint8_t *read_concat, const uint64_t *read_offsets, uint32_t n_reads,
+                                   const int32_t *target_of_read /* -1: not submitted */, const uint8_t *rev,
+                                   const rattle_align_params *params, const rattle_align_scoring *scoring, rattle_alignment **out);
+int  rattle_hip_align_cigars_scored(rattle_ctx *ctx, const uint8_t *target_concat, const uint64_t *target_offsets, uint32_t n_targets,
+                                    const uint8_t *read_concat, const uint64_t *read_offsets, uint32_t n_reads,
+                                    const int32_t *target_of_read /* -1: not submitted */, const uint8_t *rev,
+                                    const rattle_align_params *params, const rattle_align_scoring *scoring, rattle_alignment **out,
+                                    rattle_cigars **cigars);
 
 /* ------------------------------------------------------------------------------------
  * a15  spoa engine + graph as called from /root/reference/correct.cpp:395-405,428-436,520-532
@@ -646,7 +679,8 @@ void rattle_hip_debug_consensus_support_free(rattle_debug_support *d);
  * Per-kernel timing measured with HIP events on the stream the kernels run on.
  * kernel: 0 kmer_extract, 1 bv_filter, 2 pair_score, 3 poa_align, 4 post_msa, 5 the per-read reduction of
  * assign (alg_bytes: the bytes of its records copied to the host), 6 pair_align (kernel E; alg_bytes: the sequence bytes read plus
- * the record bytes written), 7 pair_cigar (kernel F; alg_bytes: see align_cigars).  Accumulated since
+ * the record bytes written), 7 pair_cigar (kernel F; alg_bytes: see align_cigars), 8 and 9 their three-state forms
+ * (align_pairs_scored, align_cigars_scored).  Accumulated since
  * the last reset: total milliseconds, number of launches, algorithmic bytes moved.
  */
 int rattle_hip_kernel_stats(rattle_ctx *ctx, int kernel, double *total_ms, uint64_t *launches, uint64_t *alg_bytes);

@@ -149,6 +149,11 @@ class AlignParams(C.Structure):
     _fields_ = [("max_cells", C.c_uint64), ("pair_chunk", C.c_uint32)]
 
 
+# the scoring of align_pairs_scored / align_cigars_scored (rattle_align_scoring): four positive magnitudes
+class AlignScoring(C.Structure):
+    _fields_ = [("match", C.c_uint32), ("mismatch", C.c_uint32), ("gap_open", C.c_uint32), ("gap_extend", C.c_uint32)]
+
+
 # the per-read record of align_pairs (rattle_alignment): one entry per read
 ALIGN_FIELDS = (("status", C.c_uint8), ("score", C.c_int32), ("q_start", C.c_uint32), ("q_end", C.c_uint32), ("t_start", C.c_uint32),
                 ("t_end", C.c_uint32), ("matches", C.c_uint32), ("mismatches", C.c_uint32), ("q_gap", C.c_uint32), ("t_gap", C.c_uint32))
@@ -215,6 +220,10 @@ SIGNATURES = {
     "rattle_hip_align_cigars": (C.c_int, [C.c_void_p, _u8p, _u64p, C.c_uint32, _u8p, _u64p, C.c_uint32, _i32p, _u8p, _P(AlignParams),
                                           _P(_P(Alignment)), _P(_P(Cigars))]),
     "rattle_hip_cigars_free": (None, [_P(Cigars)]),
+    "rattle_hip_align_pairs_scored": (C.c_int, [C.c_void_p, _u8p, _u64p, C.c_uint32, _u8p, _u64p, C.c_uint32, _i32p, _u8p, _P(AlignParams),
+                                                _P(AlignScoring), _P(_P(Alignment))]),
+    "rattle_hip_align_cigars_scored": (C.c_int, [C.c_void_p, _u8p, _u64p, C.c_uint32, _u8p, _u64p, C.c_uint32, _i32p, _u8p, _P(AlignParams),
+                                                 _P(AlignScoring), _P(_P(Alignment)), _P(_P(Cigars))]),
     "rattle_hip_poa_msa": (C.c_int, [C.c_void_p, _u8p, _u64p, C.c_uint32, _u32p, C.c_uint32, _P(_P(MsaSet))]),
     "rattle_hip_msa_set_free": (None, [_P(MsaSet)]),
     "rattle_hip_correct_reads": (C.c_int, [C.c_void_p, _u8p, _u8p, _u64p, C.c_uint32, C.c_uint32, _u32p, _i32p, _u8p,

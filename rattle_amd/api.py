@@ -19,6 +19,7 @@ from . import _lib
 from ._lib import ClusterParams, ClusterSet, Correction, CorrectParams, MsaSet, check
 
 K_KMER, K_FILTER, K_SCORE, K_POA, K_POST, K_ASSIGN, K_ALIGN, K_CIGAR = 0, 1, 2, 3, 4, 5, 6, 7
+K_ALIGN_AFFINE, K_CIGAR_AFFINE = 8, 9          # the three-state forms of kernels E and F (align_pairs / align_cigars with a scoring)
 
 
 def _ptr(a: np.ndarray, t):
@@ -611,17 +612,27 @@ class Context:
         self.n = self.k = 0               # the loaded read set was replaced by the last chunk's
         return self._take_assignment(out)
 
-    def align_pairs(self, targets: Sequence[bytes], reads: Sequence[bytes], target_of_read, rev, max_cells=0, pair_chunk=0) -> dict:
+    @staticmethod
+    def _scoring(scoring):
+        """(match, mismatch, gap_open, gap_extend), four positive magnitudes, as the library's struct; the library checks the limits"""
+        if len(scoring) != 4:
+            raise ValueError("scoring is (match, mismatch, gap_open, gap_extend)")
+        return _lib.AlignScoring(*(int(v) for v in scoring))
+
+    def align_pairs(self, targets: Sequence[bytes], reads: Sequence[bytes], target_of_read, rev, max_cells=0, pair_chunk=0, scoring=None) -> dict:
         """Every read r with target_of_read[r] >= 0 aligned locally to that target, reverse-complemented first where rev[r] == 1
         (rattle_hip_align_pairs, kernel E): the two arrays are `target` and `rev` of an assignment.  Returns a dict of arrays with one
         entry per read (_lib.ALIGN_FIELDS): status (0 aligned, 1 nothing aligns, 2 skipped by max_cells, 3 not submitted), score,
-        q_start, q_end (on the read as given), t_start, t_end, matches, mismatches, q_gap, t_gap."""
+        q_start, q_end (on the read as given), t_start, t_end, matches, mismatches, q_gap, t_gap.
+        scoring: None is that call -- match 5, mismatch -4, gap -8 per column; a tuple (match, mismatch, gap_open, gap_extend) of positive
+        magnitudes, each in [1, 64] with gap_extend <= gap_open, is rattle_hip_align_pairs_scored: affine gaps, the three-state kernel E,
+        also for (5, 4, 8, 8), which gives the records of None."""
         tcat, toff = pack_reads(targets)
         rcat, roff = pack_reads(reads)
-        return self.align_pairs_packed(tcat, toff, rcat, roff, target_of_read, rev, max_cells, pair_chunk)
+        return self.align_pairs_packed(tcat, toff, rcat, roff, target_of_read, rev, max_cells, pair_chunk, scoring)
 
     def align_pairs_packed(self, tcat: np.ndarray, toff: np.ndarray, rcat: np.ndarray, roff: np.ndarray, target_of_read, rev,
-                           max_cells=0, pair_chunk=0) -> dict:
+                           max_cells=0, pair_chunk=0, scoring=None) -> dict:
         """align_pairs() on packed arrays (pack_reads)"""
         P = _lib.AlignParams(int(max_cells), int(pair_chunk))
         n = len(roff) - 1
@@ -630,25 +641,31 @@ class Context:
         if len(t) != n or len(r) != n:
             raise ValueError("target_of_read and rev need one entry per read")
         out = C.POINTER(_lib.Alignment)()
-        check(self.lib.rattle_hip_align_pairs(self.h, _ptr(tcat, C.c_uint8) if len(tcat) else None, _ptr(toff, C.c_uint64), len(toff) - 1,
-                                              _ptr(rcat, C.c_uint8) if len(rcat) else None, _ptr(roff, C.c_uint64), n,
-                                              _ptr(t, C.c_int32) if n else None, _ptr(r, C.c_uint8) if n else None, C.byref(P), C.byref(out)))
+        args = (self.h, _ptr(tcat, C.c_uint8) if len(tcat) else None, _ptr(toff, C.c_uint64), len(toff) - 1,
+                _ptr(rcat, C.c_uint8) if len(rcat) else None, _ptr(roff, C.c_uint64), n, _ptr(t, C.c_int32) if n else None,
+                _ptr(r, C.c_uint8) if n else None, C.byref(P))
+        if scoring is None:
+            check(self.lib.rattle_hip_align_pairs(*args, C.byref(out)))
+        else:
+            S = self._scoring(scoring)
+            check(self.lib.rattle_hip_align_pairs_scored(*args, C.byref(S), C.byref(out)))
         m = int(out.contents.n)
         res = {f: np.ctypeslib.as_array(getattr(out.contents, f), (max(m, 1),))[:m].copy() for f, _ in _lib.ALIGN_FIELDS}
         self.lib.rattle_hip_alignment_free(out)
         return res
 
-    def align_cigars(self, targets: Sequence[bytes], reads: Sequence[bytes], target_of_read, rev, max_cells=0, pair_chunk=0):
+    def align_cigars(self, targets: Sequence[bytes], reads: Sequence[bytes], target_of_read, rev, max_cells=0, pair_chunk=0, scoring=None):
         """align_pairs(), and the CIGAR of every read that aligns (rattle_hip_align_cigars, kernels E and F).  Returns (records, offsets,
         ops): the dict align_pairs returns for the same arguments, and the ops of read r as ops[offsets[r]:offsets[r + 1]], uint32
         len << 4 | op with BAM's numbers (= 7, X 8, I 1, D 2), from the alignment's start to its end on the strand that was aligned
-        (cigar_bytes formats them).  A read whose status is not 0 has none."""
+        (cigar_bytes formats them).  A read whose status is not 0 has none.  scoring: as in align_pairs (a tuple is
+        rattle_hip_align_cigars_scored, the three-state kernels E and F)."""
         tcat, toff = pack_reads(targets)
         rcat, roff = pack_reads(reads)
-        return self.align_cigars_packed(tcat, toff, rcat, roff, target_of_read, rev, max_cells, pair_chunk)
+        return self.align_cigars_packed(tcat, toff, rcat, roff, target_of_read, rev, max_cells, pair_chunk, scoring)
 
     def align_cigars_packed(self, tcat: np.ndarray, toff: np.ndarray, rcat: np.ndarray, roff: np.ndarray, target_of_read, rev,
-                            max_cells=0, pair_chunk=0):
+                            max_cells=0, pair_chunk=0, scoring=None):
         """align_cigars() on packed arrays (pack_reads)"""
         P = _lib.AlignParams(int(max_cells), int(pair_chunk))
         n = len(roff) - 1
@@ -658,10 +675,14 @@ class Context:
             raise ValueError("target_of_read and rev need one entry per read")
         out = C.POINTER(_lib.Alignment)()
         cg = C.POINTER(_lib.Cigars)()
-        check(self.lib.rattle_hip_align_cigars(self.h, _ptr(tcat, C.c_uint8) if len(tcat) else None, _ptr(toff, C.c_uint64), len(toff) - 1,
-                                               _ptr(rcat, C.c_uint8) if len(rcat) else None, _ptr(roff, C.c_uint64), n,
-                                               _ptr(t, C.c_int32) if n else None, _ptr(r, C.c_uint8) if n else None, C.byref(P), C.byref(out),
-                                               C.byref(cg)))
+        args = (self.h, _ptr(tcat, C.c_uint8) if len(tcat) else None, _ptr(toff, C.c_uint64), len(toff) - 1,
+                _ptr(rcat, C.c_uint8) if len(rcat) else None, _ptr(roff, C.c_uint64), n, _ptr(t, C.c_int32) if n else None,
+                _ptr(r, C.c_uint8) if n else None, C.byref(P))
+        if scoring is None:
+            check(self.lib.rattle_hip_align_cigars(*args, C.byref(out), C.byref(cg)))
+        else:
+            S = self._scoring(scoring)
+            check(self.lib.rattle_hip_align_cigars_scored(*args, C.byref(S), C.byref(out), C.byref(cg)))
         m = int(out.contents.n)
         res = {f: np.ctypeslib.as_array(getattr(out.contents, f), (max(m, 1),))[:m].copy() for f, _ in _lib.ALIGN_FIELDS}
         offsets = np.ctypeslib.as_array(cg.contents.offset, (m + 1,)).copy()
@@ -1026,10 +1047,11 @@ def paf_text(read_names: Sequence[bytes], read_lengths: Sequence[int], target_na
 
 def assign_paf_command(ctx: Context, read_headers: Sequence[bytes], reads: Sequence[bytes], target_headers: Sequence[bytes],
                        targets: Sequence[bytes], *, k=10, t_s=0.2, t_v=1000000.0, bv_threshold=0.4, is_rna=False, count_pass="auto",
-                       target_batch=0, read_chunk=0, max_cells=0, pair_chunk=0, cigar=False):
+                       target_batch=0, read_chunk=0, max_cells=0, pair_chunk=0, cigar=False, scoring=None):
     """`rattle assign --paf`: assign_command, then every placed read aligned to its transcript (Context.align_pairs).  Returns the bytes
     of assignments.tsv, target_counts.tsv and alignments.paf; the first two are what assign_command returns.  cigar=True is
-    `--paf --cigar`: Context.align_cigars, and a cg:Z: tag on every line."""
+    `--paf --cigar`: Context.align_cigars, and a cg:Z: tag on every line.  scoring=(m, x, o, e) is `--paf-scoring m,x,o,e`: affine gaps
+    (Context.align_pairs); None is the linear default."""
     sent = [i for i, s in enumerate(reads) if not s.translate(None, b"ACGTU")]
     got = ctx.assign(targets, [reads[i] for i in sent], k, t_s, t_v, bv_threshold, False, is_rna, target_batch, read_chunk, count_pass)
     rec = unassigned_records(len(reads))
@@ -1037,10 +1059,10 @@ def assign_paf_command(ctx: Context, read_headers: Sequence[bytes], reads: Seque
         rec[f][sent] = got[f]
     cigars = None
     if cigar:
-        aln, offsets, ops = ctx.align_cigars(targets, reads, rec["target"], rec["rev"], max_cells, pair_chunk)
+        aln, offsets, ops = ctx.align_cigars(targets, reads, rec["target"], rec["rev"], max_cells, pair_chunk, scoring)
         cigars = (offsets, ops)
     else:
-        aln = ctx.align_pairs(targets, reads, rec["target"], rec["rev"], max_cells, pair_chunk)
+        aln = ctx.align_pairs(targets, reads, rec["target"], rec["rev"], max_cells, pair_chunk, scoring)
     tn = [_first_token(h) for h in target_headers]
     rn = [_first_token(h) for h in read_headers]
     tl = [len(s) for s in targets]

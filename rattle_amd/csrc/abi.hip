@@ -630,10 +630,12 @@ void rattle_hip_assignment_free(rattle_assignment *a) {
     free(a);
 }
 
-// ---- align_pairs (kernel E), align_cigars (kernels E and F) ---------------------------------------------------------------
-// the body of both entry points; `who` names the entry point in the messages, `run` (align_cigars) takes the ops of kernel F
+// ---- align_pairs (kernel E), align_cigars (kernels E and F), and their _scored forms (the three-state kernels) ------------
+// the body of the four entry points; `who` names the entry point in the messages, `run` (align_cigars) takes the ops of kernel F; `scored`:
+// S is checked behind every check of align_pairs, still before the device is looked at, and the three-state kernels run
 static int align_entry(const char *who, rattle_ctx *c, const uint8_t *tseq, const uint64_t *toff, uint32_t nt, const uint8_t *rseq, const uint64_t *roff,
-                       uint32_t nr, const int32_t *target, const uint8_t *rev, const rattle_align_params *P, rattle_alignment **out, cigar_run *run) {
+                       uint32_t nr, const int32_t *target, const uint8_t *rev, const rattle_align_params *P, rattle_alignment **out, cigar_run *run,
+                       bool scored = false, const rattle_align_scoring *S = nullptr) {
     const std::string w = std::string(who) + ": ";
     // the arguments, on the host: indices, strands, lengths, and the letters of every sequence that is submitted (a target once)
     auto clean = [](const uint8_t *s, uint64_t n) { for (uint64_t i = 0; i < n; ++i) if (!s[i] || !strchr("ACGTU", s[i])) return false; return true; };
@@ -654,6 +656,23 @@ static int align_entry(const char *who, rattle_ctx *c, const uint8_t *tseq, cons
         set_error(std::string(who) + " is not available on a context that is one rank of several: sharded jobs are not built, align on one device");
         return RATTLE_ERR_STATE;
     }
+    if (scored) {
+        if (!S) { set_error(w + "null scoring"); return RATTLE_ERR_ARG; }
+        if (S->match < 1 || S->match > 64 || S->mismatch < 1 || S->mismatch > 64 || S->gap_open < 1 || S->gap_open > 64 || S->gap_extend < 1 ||
+            S->gap_extend > S->gap_open) {
+            set_error(w + "scoring " + std::to_string(S->match) + "," + std::to_string(S->mismatch) + "," + std::to_string(S->gap_open) + "," +
+                      std::to_string(S->gap_extend) + ": match, mismatch, gap_open, gap_extend must be in [1, 64] and gap_extend <= gap_open");
+            return RATTLE_ERR_ARG;
+        }
+        for (uint32_t r = 0; r < nr; ++r) {
+            if (target[r] < 0) continue;
+            const uint64_t lq = roff[r + 1] - roff[r], lt = toff[target[r] + 1] - toff[target[r]];
+            if (S->match * std::min(lq, lt) > 0x7FFFFFFFull) {
+                set_error(w + "read " + std::to_string(r) + ": match * min(Lq, Lt) exceeds 2^31 - 1, the score might not fit the record");
+                return RATTLE_ERR_ARG;
+            }
+        }
+    }
     RT_TRY(use_device(c));
     const size_t m = std::max<size_t>(1, nr);
     rattle_alignment *A = (rattle_alignment *)calloc(1, sizeof(rattle_alignment));
@@ -661,7 +680,7 @@ static int align_entry(const char *who, rattle_ctx *c, const uint8_t *tseq, cons
     A->status = (uint8_t *)calloc(m, 1); A->score = (int32_t *)calloc(m, 4);
     for (uint32_t **f : {&A->q_start, &A->q_end, &A->t_start, &A->t_end, &A->matches, &A->mismatches, &A->q_gap, &A->t_gap}) *f = (uint32_t *)calloc(m, 4);
     if (run) { run->count.assign(nr, 0); run->ops.clear(); run->code_cap = cigar_code_cap(); }
-    const int rc = align_pairs_run(c, tseq, toff, nt, rseq, roff, nr, target, rev, P, A, run);
+    const int rc = align_pairs_run(c, tseq, toff, nt, rseq, roff, nr, target, rev, P, A, run, scored ? S : nullptr);
     if (rc != 0) { rattle_hip_alignment_free(A); return rc; }
     *out = A;
     return 0;
@@ -677,9 +696,21 @@ int rattle_hip_align_pairs(rattle_ctx *c, const uint8_t *tseq, const uint64_t *t
     return align_entry("align_pairs", c, tseq, toff, nt, rseq, roff, nr, target, rev, P, out, nullptr);
 }
 
-int rattle_hip_align_cigars(rattle_ctx *c, const uint8_t *tseq, const uint64_t *toff, uint32_t nt, const uint8_t *rseq, const uint64_t *roff,
-                            uint32_t nr, const int32_t *target, const uint8_t *rev, const rattle_align_params *P, rattle_alignment **out,
-                            rattle_cigars **cigars) {
+int rattle_hip_align_pairs_scored(rattle_ctx *c, const uint8_t *tseq, const uint64_t *toff, uint32_t nt, const uint8_t *rseq, const uint64_t *roff,
+                                  uint32_t nr, const int32_t *target, const uint8_t *rev, const rattle_align_params *P, const rattle_align_scoring *S,
+                                  rattle_alignment **out) {
+    if (out) *out = nullptr;
+    if (!c || !P || !out || !toff || !roff || (nr && (!target || !rev)) || (!tseq && toff[nt] != toff[0]) || (!rseq && roff[nr] != roff[0])) {
+        set_error("null argument");
+        return RATTLE_ERR_ARG;
+    }
+    return align_entry("align_pairs_scored", c, tseq, toff, nt, rseq, roff, nr, target, rev, P, out, nullptr, true, S);
+}
+
+// the body of align_cigars and align_cigars_scored
+static int cigars_entry(const char *who, rattle_ctx *c, const uint8_t *tseq, const uint64_t *toff, uint32_t nt, const uint8_t *rseq, const uint64_t *roff,
+                        uint32_t nr, const int32_t *target, const uint8_t *rev, const rattle_align_params *P, rattle_alignment **out,
+                        rattle_cigars **cigars, bool scored, const rattle_align_scoring *S) {
     if (out) *out = nullptr;
     if (cigars) *cigars = nullptr;
     if (!c || !P || !out || !cigars || !toff || !roff || (nr && (!target || !rev)) || (!tseq && toff[nt] != toff[0]) || (!rseq && roff[nr] != roff[0])) {
@@ -687,7 +718,7 @@ int rattle_hip_align_cigars(rattle_ctx *c, const uint8_t *tseq, const uint64_t *
         return RATTLE_ERR_ARG;
     }
     cigar_run run;
-    RT_TRY(align_entry("align_cigars", c, tseq, toff, nt, rseq, roff, nr, target, rev, P, out, &run));
+    RT_TRY(align_entry(who, c, tseq, toff, nt, rseq, roff, nr, target, rev, P, out, &run, scored, S));
     rattle_cigars *G = (rattle_cigars *)calloc(1, sizeof(rattle_cigars));
     G->n = nr;
     G->offset = (uint64_t *)calloc((size_t)nr + 1, 8);
@@ -696,6 +727,18 @@ int rattle_hip_align_cigars(rattle_ctx *c, const uint8_t *tseq, const uint64_t *
     if (!run.ops.empty()) memcpy(G->ops, run.ops.data(), run.ops.size() * 4);
     *cigars = G;
     return 0;
+}
+
+int rattle_hip_align_cigars(rattle_ctx *c, const uint8_t *tseq, const uint64_t *toff, uint32_t nt, const uint8_t *rseq, const uint64_t *roff,
+                            uint32_t nr, const int32_t *target, const uint8_t *rev, const rattle_align_params *P, rattle_alignment **out,
+                            rattle_cigars **cigars) {
+    return cigars_entry("align_cigars", c, tseq, toff, nt, rseq, roff, nr, target, rev, P, out, cigars, false, nullptr);
+}
+
+int rattle_hip_align_cigars_scored(rattle_ctx *c, const uint8_t *tseq, const uint64_t *toff, uint32_t nt, const uint8_t *rseq, const uint64_t *roff,
+                                   uint32_t nr, const int32_t *target, const uint8_t *rev, const rattle_align_params *P, const rattle_align_scoring *S,
+                                   rattle_alignment **out, rattle_cigars **cigars) {
+    return cigars_entry("align_cigars_scored", c, tseq, toff, nt, rseq, roff, nr, target, rev, P, out, cigars, true, S);
 }
 
 void rattle_hip_cigars_free(rattle_cigars *g) {

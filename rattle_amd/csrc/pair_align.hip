@@ -26,13 +26,6 @@ namespace rattle {
 namespace {
 
 constexpr int32_t AL_MATCH = 5, AL_MISMATCH = -4, AL_GAP = -8;
-constexpr uint32_t AL_REC_WORDS = 10;            // status, score, q_start, q_end, t_start, t_end, matches, mismatches, q_gap, t_gap
-
-// one submitted pair: where its sequences lie in the uploaded buffers, and its strip (in 16-byte records; unused when the read has one block)
-struct align_pair {
-    uint64_t q, t, strip;
-    uint32_t lq, lt, rev, pad;
-};
 
 // value of lane - 1 (lane 0 receives `fill`): the helper of poa.hip
 __device__ __forceinline__ int32_t al_shr1(int32_t v, int32_t fill) {
@@ -128,12 +121,15 @@ __global__ __launch_bounds__(256) void pair_align_kernel(const align_pair *__res
 // Every read r with target_of_read[r] >= 0, both sequences non-empty and (max_cells == 0 or lq * lt <= max_cells) is aligned; the arguments
 // have been checked (abi.hip).  Fills every array of A.  The plan -- statuses settled without the device, strip records, chunks -- is
 // align_plan.h's; the strip buffer is sized from the lengths of the chunk.  With `cigars` (rattle_hip_align_cigars) every chunk's records go on
-// to kernel F (pair_cigar.hip) while the chunk's sequences are on the device; A is filled exactly as without.
+// to kernel F (pair_cigar.hip) while the chunk's sequences are on the device; A is filled exactly as without.  With `scoring`
+// (rattle_hip_align_*_scored) the launches are those of the three-state kernels (pair_align_affine.hip, pair_cigar_affine.hip); the plan, the
+// uploads and the records are the same, the strip's records are 40 bytes.
 int align_pairs_run(rattle_ctx *ctx, const uint8_t *tseq, const uint64_t *toff, uint32_t nt, const uint8_t *rseq, const uint64_t *roff, uint32_t nr,
-                    const int32_t *target, const uint8_t *rev, const rattle_align_params *AP, rattle_alignment *A, cigar_run *cigars) {
+                    const int32_t *target, const uint8_t *rev, const rattle_align_params *AP, rattle_alignment *A, cigar_run *cigars, const rattle_align_scoring *scoring) {
     phase_timer T_all("align_pairs: total");
     align_plan plan;
-    plan_align(toff, roff, nr, target, AP->max_cells, AP->pair_chunk ? AP->pair_chunk : 32768u, 1ull << 26 /* 1 GiB of records */, plan);
+    plan_align(toff, roff, nr, target, AP->max_cells, AP->pair_chunk ? AP->pair_chunk : 32768u,
+               scoring ? (1ull << 30) / AL_AFFINE_STRIP_BYTES : 1ull << 26 /* 1 GiB of records */, plan);
     for (uint32_t r = 0; r < nr; ++r) A->status[r] = plan.status[r];
     if (plan.sub.empty()) return 0;
     const std::vector<uint32_t> &sub = plan.sub, &first = plan.first;
@@ -165,14 +161,15 @@ int align_pairs_run(rattle_ctx *ctx, const uint8_t *tseq, const uint64_t *toff, 
         }
         RT_TRY(d_q.reserve(qbytes));
         RT_TRY(d_pairs.reserve(n));
-        RT_TRY(d_strip.reserve(std::max<uint64_t>(1, strip_recs)));
+        RT_TRY(d_strip.reserve(std::max<uint64_t>(1, scoring ? (strip_recs * (AL_AFFINE_STRIP_BYTES / 8) + 1) / 2 : strip_recs)));      // (uint4s)
         RT_TRY(d_rec.reserve((size_t)n * AL_REC_WORDS));
         RT_TRY(h_rec.reserve((size_t)n * AL_REC_WORDS));
         RT_HIP(hipMemcpyAsync(d_q.p, rseq + q0, qbytes, hipMemcpyHostToDevice, ctx->stream));
         RT_HIP(hipMemcpyAsync(d_pairs.p, h_pairs.p, (size_t)n * sizeof(align_pair), hipMemcpyHostToDevice, ctx->stream));
         {
-            ktimer kt(ctx, K_ALIGN, seq_bytes + (uint64_t)n * AL_REC_WORDS * 4);
-            hipLaunchKernelGGL(pair_align_kernel, dim3((n + 3) / 4), dim3(256), 0, ctx->stream, d_pairs.p, n, d_q.p, d_t.p, d_strip.p, d_rec.p);
+            ktimer kt(ctx, scoring ? K_ALIGN_AFFINE : K_ALIGN, seq_bytes + (uint64_t)n * AL_REC_WORDS * 4);
+            if (scoring) pair_align_affine_launch(ctx->stream, d_pairs.p, n, d_q.p, d_t.p, (uint2 *)d_strip.p, d_rec.p, *scoring);
+            else hipLaunchKernelGGL(pair_align_kernel, dim3((n + 3) / 4), dim3(256), 0, ctx->stream, d_pairs.p, n, d_q.p, d_t.p, d_strip.p, d_rec.p);
             RT_HIP(hipGetLastError());
         }
         RT_HIP(hipMemcpyAsync(h_rec.p, d_rec.p, (size_t)n * AL_REC_WORDS * 4, hipMemcpyDeviceToHost, ctx->stream));
@@ -196,7 +193,7 @@ int align_pairs_run(rattle_ctx *ctx, const uint8_t *tseq, const uint64_t *toff, 
                 I.rows = A->q_end[r] - A->q_start[r]; I.cols = A->t_end[r] - A->t_start[r];
                 I.q = P.q + (P.rev ? (uint64_t)A->q_end[r] - (I.rows ? 1 : 0) : (uint64_t)A->q_start[r]); I.t = P.t + A->t_start[r];
             }
-            RT_TRY(pair_cigar_chunk(ctx, d_q.p, d_t.p, in.data(), n, AP->pair_chunk ? AP->pair_chunk : 32768u, *cigars));
+            RT_TRY(pair_cigar_chunk(ctx, d_q.p, d_t.p, in.data(), n, AP->pair_chunk ? AP->pair_chunk : 32768u, *cigars, scoring));
         }
     }
     return 0;

@@ -177,13 +177,17 @@ uint64_t cigar_code_cap() {
 
 // The pairs `in` of one chunk of kernel E, whose sequences lie in d_q and d_t: the ops of every pair with status 0 appended to R.ops, their
 // number to R.count[read].  Sub-chunks as cigar_plan.h plans them; per sub-chunk one launch of kernel F (id 7 of the stats), the counts to
-// the host, offsets from them, one gather launch, and the compact ops back.
-int pair_cigar_chunk(rattle_ctx *ctx, const uint8_t *d_q, const uint8_t *d_t, const cigar_in *in, uint32_t n, uint32_t pair_chunk, cigar_run &R) {
+// the host, offsets from them, one gather launch, and the compact ops back.  With `scoring` the launch is that of the three-state kernel
+// (pair_cigar_affine.hip, id 9): 32-byte records, two strip words per column; everything around it is the same.
+int pair_cigar_chunk(rattle_ctx *ctx, const uint8_t *d_q, const uint8_t *d_t, const cigar_in *in, uint32_t n, uint32_t pair_chunk, cigar_run &R,
+                     const rattle_align_scoring *scoring) {
+    const uint64_t rec_bytes = scoring ? CG_AFFINE_REC_BYTES : CG_REC_BYTES;
+    const int kid = scoring ? K_CIGAR_AFFINE : K_CIGAR;
     std::vector<uint8_t> status(n);
     std::vector<uint32_t> rows(n), cols(n);
     for (uint32_t i = 0; i < n; ++i) { status[i] = in[i].status; rows[i] = in[i].rows; cols[i] = in[i].cols; }
     cigar_plan plan;
-    plan_cigar(status.data(), rows.data(), cols.data(), n, pair_chunk, R.code_cap, plan);
+    plan_cigar(status.data(), rows.data(), cols.data(), n, pair_chunk, R.code_cap, plan, rec_bytes, scoring ? CG_AFFINE_STRIP_WORDS : 1);
     for (size_t c = 0; c + 1 < plan.first.size(); ++c) {
         const uint32_t a = plan.first[c], m = plan.first[c + 1] - a;
         RT_TRY(R.h_pairs.reserve(m));
@@ -196,11 +200,11 @@ int pair_cigar_chunk(rattle_ctx *ctx, const uint8_t *d_q, const uint8_t *d_t, co
             recs = cg_add(recs, plan.recs[a + i]); strip += plan.strip[a + i]; words += plan.ops[a + i];
             // the rectangle's sequence bytes, the code records written (a block of h rows writes cols + h - 1 of them), the count
             const uint64_t blocks = ((uint64_t)I.rows + CG_ROWS - 1) / CG_ROWS;
-            alg += (uint64_t)I.rows + I.cols + CG_REC_BYTES * (blocks * ((uint64_t)I.cols - 1) + I.rows) + 4;
+            alg += (uint64_t)I.rows + I.cols + rec_bytes * (blocks * ((uint64_t)I.cols - 1) + I.rows) + 4;
         }
         if (recs > (~0ull >> 8)) { set_error("align_cigars: out of memory (the code records of one pair)"); return RATTLE_ERR_HIP; }
         RT_TRY(R.d_pairs.reserve(m));
-        RT_TRY(R.d_codes.reserve(recs));
+        RT_TRY(R.d_codes.reserve(recs * (rec_bytes / sizeof(uint4))));
         RT_TRY(R.d_strip.reserve(std::max<uint64_t>(1, strip)));
         RT_TRY(R.d_ops.reserve(words));
         RT_TRY(R.d_count.reserve(m));
@@ -209,8 +213,9 @@ int pair_cigar_chunk(rattle_ctx *ctx, const uint8_t *d_q, const uint8_t *d_t, co
         RT_TRY(R.h_off.reserve((size_t)m + 1));
         RT_HIP(hipMemcpyAsync(R.d_pairs.p, R.h_pairs.p, (size_t)m * sizeof(cigar_pair), hipMemcpyHostToDevice, ctx->stream));
         {
-            ktimer kt(ctx, K_CIGAR, alg);
-            hipLaunchKernelGGL(pair_cigar_kernel, dim3((m + 3) / 4), dim3(256), 0, ctx->stream, R.d_pairs.p, m, d_q, d_t, R.d_codes.p, R.d_strip.p,
+            ktimer kt(ctx, kid, alg);
+            if (scoring) pair_cigar_affine_launch(ctx->stream, R.d_pairs.p, m, d_q, d_t, R.d_codes.p, R.d_strip.p, R.d_ops.p, R.d_count.p, *scoring);
+            else hipLaunchKernelGGL(pair_cigar_kernel, dim3((m + 3) / 4), dim3(256), 0, ctx->stream, R.d_pairs.p, m, d_q, d_t, R.d_codes.p, R.d_strip.p,
                                R.d_ops.p, R.d_count.p);
             RT_HIP(hipGetLastError());
         }
@@ -224,7 +229,7 @@ int pair_cigar_chunk(rattle_ctx *ctx, const uint8_t *d_q, const uint8_t *d_t, co
             total += cnt;
         }
         R.h_off.p[m] = total;
-        ctx->stats[K_CIGAR].bytes += 4 * total;                      // ... and 4 bytes per op
+        ctx->stats[kid].bytes += 4 * total;                      // ... and 4 bytes per op
         if (!total) continue;
         RT_TRY(R.d_out.reserve(total));
         RT_TRY(R.h_out.reserve(total));

@@ -783,7 +783,9 @@ struct assign_job {
     rattle_assignment *A = nullptr;
     bool want_paf = false, want_cigar = false;     // --paf, --cigar (cg:Z: on every PAF line)
     rattle_align_params AP;
-    std::string text, counts, paf;                // assignments.tsv, target_counts.tsv, alignments.paf (--paf)
+    bool want_scoring = false;                    // --paf-scoring m,x,o,e: affine gaps, the three-state kernels
+    rattle_align_scoring AS;
+    std::string text, counts, paf;               // assignments.tsv, target_counts.tsv, alignments.paf (--paf)
     void options(int argc, char **argv) {
         a = parse(argc, argv, {
             {"help", {"-h", "--help"}, false}, {"input", {"-i", "--input"}, true}, {"targets", {"-x", "--transcripts"}, true},
@@ -791,7 +793,7 @@ struct assign_job {
             {"t_v", {"-v", "--max-variance"}, true}, {"bv_threshold", {"-B", "--bv-start-threshold"}, true}, {"rna", {"--rna"}, false},
             {"count-pass", {"--count-pass"}, true}, {"device", {"--device"}, true}, {"devices", {"--devices"}, true},
             {"target-batch", {"--target-batch"}, true}, {"read-chunk", {"--read-chunk"}, true}, {"paf", {"--paf"}, false},
-            {"paf-max-cells", {"--paf-max-cells"}, true}, {"cigar", {"--cigar"}, false}});
+            {"paf-max-cells", {"--paf-max-cells"}, true}, {"cigar", {"--cigar"}, false}, {"paf-scoring", {"--paf-scoring"}, true}});
         const char *usage = "rattle assign -i reads.fq -x transcripts.fq [-o dir] [-k 10] [-s 0.2] [-v 1000000] [-B 0.4] [--rna] [--device n] [--paf [--cigar]]\n"
                             "  places every read of -i on the transcript of -x that accepts it with the best score (the comparison `cluster` joins\n"
                             "  reads by, the transcript in the seed's role) and writes assignments.tsv (one line per read: target, strand, score,\n"
@@ -802,7 +804,10 @@ struct assign_job {
                             "                                        column) and write alignments.paf: one PAF line per aligned read, in file order\n"
                             "  --paf-max-cells n                     with --paf: skip a read whose length x its transcript's length exceeds n (default 0: no limit)\n"
                             "  --cigar                               with --paf: end every line of alignments.paf with cg:Z:<CIGAR>, the alignment's columns\n"
-                            "                                        in the extended set (= match, X mismatch, I read base on a gap, D transcript base on a gap)\n";
+                            "                                        in the extended set (= match, X mismatch, I read base on a gap, D transcript base on a gap)\n"
+                            "  --paf-scoring m,x,o,e                 with --paf: affine gaps and this scoring, four positive integers: match +m, mismatch -x,\n"
+                            "                                        the first column of a gap -o, every further one -e; each in 1..64, e <= o.  5,4,8,6 is the\n"
+                            "                                        scoring of `correct`, 2,4,4,2 minimap2's.  Default: linear gaps, 5,4,8,8\n";
         if (a.has("help")) { std::cerr << usage; exit(EXIT_SUCCESS); }
         if (!a.has("input")) die("ERROR: No input file provided (-i reads)");
         if (!a.has("targets")) die("ERROR: No transcript file provided (-x transcripts)");
@@ -818,6 +823,21 @@ struct assign_job {
         if (a.has("paf-max-cells") && !want_paf) die("\nError: --paf-max-cells needs --paf\n");
         want_cigar = a.has("cigar");
         if (want_cigar && !want_paf) die("\nError: --cigar needs --paf\n");
+        want_scoring = a.has("paf-scoring");
+        if (want_scoring && !want_paf) die("\nError: --paf-scoring needs --paf\n");
+        if (want_scoring) {
+            const char *limit = "\nError: --paf-scoring takes four integers m,x,o,e, each in 1..64 and e <= o (match, mismatch, gap open, gap extend)\n";
+            const std::vector<std::string> v = split_string(a.str("paf-scoring", ""), ',');
+            uint32_t w[4] = {0, 0, 0, 0};
+            if (v.size() != 4) die(limit);
+            for (int i = 0; i < 4; ++i) {
+                if (v[i].empty() || v[i].size() > 2 || v[i].find_first_not_of("0123456789") != std::string::npos) die(limit);
+                w[i] = (uint32_t)std::stoul(v[i]);
+                if (w[i] < 1 || w[i] > 64) die(limit);
+            }
+            if (w[3] > w[2]) die(limit);
+            AS.match = w[0]; AS.mismatch = w[1]; AS.gap_open = w[2]; AS.gap_extend = w[3];
+        }
         memset(&AP, 0, sizeof AP);
         AP.max_cells = std::stoull(a.str("paf-max-cells", "0"));
         P.target_batch = (uint32_t)std::max(0, a.i("target-batch", 0)); P.read_chunk = (uint32_t)std::max(0, a.i("read-chunk", 0));
@@ -849,7 +869,9 @@ struct assign_job {
         cli_timer t(want_cigar ? "library: align_cigars" : "library: align_pairs");
         rattle_alignment *L = nullptr;
         rattle_cigars *G = nullptr;
-        if (want_cigar) chk(rattle_hip_align_cigars(team.ctx[0], xcat.data(), xoff.data(), (uint32_t)xid.size(), rcat.data(), roff.data(), (uint32_t)rid.size(), A->target, A->rev, &AP, &L, &G));
+        if (want_scoring && want_cigar) chk(rattle_hip_align_cigars_scored(team.ctx[0], xcat.data(), xoff.data(), (uint32_t)xid.size(), rcat.data(), roff.data(), (uint32_t)rid.size(), A->target, A->rev, &AP, &AS, &L, &G));
+        else if (want_scoring) chk(rattle_hip_align_pairs_scored(team.ctx[0], xcat.data(), xoff.data(), (uint32_t)xid.size(), rcat.data(), roff.data(), (uint32_t)rid.size(), A->target, A->rev, &AP, &AS, &L));
+        else if (want_cigar) chk(rattle_hip_align_cigars(team.ctx[0], xcat.data(), xoff.data(), (uint32_t)xid.size(), rcat.data(), roff.data(), (uint32_t)rid.size(), A->target, A->rev, &AP, &L, &G));
         else chk(rattle_hip_align_pairs(team.ctx[0], xcat.data(), xoff.data(), (uint32_t)xid.size(), rcat.data(), roff.data(), (uint32_t)rid.size(), A->target, A->rev, &AP, &L));
         uint64_t skipped = 0;
         for (uint32_t at = 0; at < L->n; ++at) {
