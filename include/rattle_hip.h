@@ -233,6 +233,41 @@ int rattle_hip_assign_reads(rattle_ctx *ctx, const uint8_t *target_concat, const
                             const rattle_assign_params *params, rattle_assignment **out);
 void rattle_hip_assignment_free(rattle_assignment *a);
 
+/* The candidate list (ABI 4): not only the best target of a read but its k best, k in 1..8, each with the fields of a line of
+ * assignments.tsv, so that the runner-up of an isoform family can be named, aligned (align_pairs takes slot j's target and rev as they
+ * are) and compared with the winner.  For read r:
+ *   one candidate per target   of the accepted comparisons of r -- exactly those rattle_hip_assign_* reduces -- every target t that
+ *                              accepts r on at least one strand gives ONE candidate, its comparison with the larger score; an equal
+ *                              score goes to forward; the other strand of the same target is not a second candidate
+ *   order                      score descending, compared as doubles; ties go to the lower target index
+ *   length                     count[r] = min(k, number of accepting targets); the list is the first count[r] candidates
+ *   slot r * k + j             target, rev, bases, hc_bases, min_len, score, variance of the j-th candidate; an unused slot
+ *                              (j >= count[r]) has target -1, score -1.0 and zeros elsewhere
+ * By construction slot 0 is the record of rattle_assignment and slot 1's score is its second_score.  Like that record the list does not
+ * depend on target_batch, read_chunk, count_pass or the order in which the device scores the pairs: it is selected ON THE DEVICE
+ * beside the record (csrc/assign.hip), 4 + 28 k bytes per read return to the host, and no pair is ever listed for it. */
+typedef struct {
+    uint32_t n, k;          /* reads, slots per read */
+    uint32_t *count;        /* [n] filled slots of every read */
+    int32_t  *target;       /* [n * k] from here on: slot r * k + j */
+    uint8_t  *rev;
+    int32_t  *bases, *hc_bases;
+    uint32_t *min_len;
+    double   *score, *variance;
+} rattle_candidates;
+
+/* rattle_hip_assign_loaded / rattle_hip_assign_reads with the candidate list: *out is field for field what the call without _top
+ * returns for the same arguments, produced by the same code.  The errors are those of that call, in the same order; then
+ * RATTLE_ERR_ARG for k == 0, k > 8 or cands == NULL -- all argument errors come before the refusal of a context that is one rank of
+ * several (RATTLE_ERR_STATE) and before the device is looked at.  On an error both *out and *cands are NULL. */
+int rattle_hip_assign_loaded_top(rattle_ctx *ctx, const rattle_assign_params *params, const uint32_t *target_ids, uint32_t n_targets,
+                                 const uint32_t *read_ids, uint32_t n_reads, uint32_t k, rattle_assignment **out,
+                                 rattle_candidates **cands);
+int rattle_hip_assign_reads_top(rattle_ctx *ctx, const uint8_t *target_concat, const uint64_t *target_offsets, uint32_t n_targets,
+                                const uint8_t *read_concat, const uint64_t *read_offsets, uint32_t n_reads, int kmer_size,
+                                const rattle_assign_params *params, uint32_t k, rattle_assignment **out, rattle_candidates **cands);
+void rattle_hip_candidates_free(rattle_candidates *c);
+
 /* ------------------------------------------------------------------------------------
  * align_pairs: WHERE on its transcript every placed read lies (kernel E, csrc/pair_align.hip); the reference has no counterpart.
  * target_of_read and rev are exactly rattle_assignment::target and ::rev: read r is aligned to target target_of_read[r] (-1: not

@@ -145,6 +145,15 @@ class Assignment(C.Structure):
     _fields_ = [("n", C.c_uint32)] + [(f, C.POINTER(t)) for f, t in ASSIGN_FIELDS]
 
 
+# a slot of the candidate list of assign_*_top (rattle_candidates): k entries per read, slot r * k + j
+CANDIDATE_FIELDS = (("target", C.c_int32), ("rev", C.c_uint8), ("bases", C.c_int32), ("hc_bases", C.c_int32), ("min_len", C.c_uint32),
+                    ("score", C.c_double), ("variance", C.c_double))
+
+
+class Candidates(C.Structure):
+    _fields_ = [("n", C.c_uint32), ("k", C.c_uint32), ("count", C.POINTER(C.c_uint32))] + [(f, C.POINTER(t)) for f, t in CANDIDATE_FIELDS]
+
+
 class AlignParams(C.Structure):
     _fields_ = [("max_cells", C.c_uint64), ("pair_chunk", C.c_uint32)]
 
@@ -214,6 +223,11 @@ SIGNATURES = {
     "rattle_hip_assign_reads": (C.c_int, [C.c_void_p, _u8p, _u64p, C.c_uint32, _u8p, _u64p, C.c_uint32, C.c_int, _P(AssignParams),
                                           _P(_P(Assignment))]),
     "rattle_hip_assignment_free": (None, [_P(Assignment)]),
+    "rattle_hip_assign_loaded_top": (C.c_int, [C.c_void_p, _P(AssignParams), _u32p, C.c_uint32, _u32p, C.c_uint32, C.c_uint32,
+                                               _P(_P(Assignment)), _P(_P(Candidates))]),
+    "rattle_hip_assign_reads_top": (C.c_int, [C.c_void_p, _u8p, _u64p, C.c_uint32, _u8p, _u64p, C.c_uint32, C.c_int, _P(AssignParams),
+                                              C.c_uint32, _P(_P(Assignment)), _P(_P(Candidates))]),
+    "rattle_hip_candidates_free": (None, [_P(Candidates)]),
     "rattle_hip_align_pairs": (C.c_int, [C.c_void_p, _u8p, _u64p, C.c_uint32, _u8p, _u64p, C.c_uint32, _i32p, _u8p, _P(AlignParams),
                                          _P(_P(Alignment))]),
     "rattle_hip_alignment_free": (None, [_P(Alignment)]),

@@ -612,6 +612,53 @@ class Context:
         self.n = self.k = 0               # the loaded read set was replaced by the last chunk's
         return self._take_assignment(out)
 
+    # assign with the candidate list
+    def _take_candidates(self, cands) -> dict:
+        n, k = int(cands.contents.n), int(cands.contents.k)
+        res = {"count": np.ctypeslib.as_array(cands.contents.count, (max(n, 1),))[:n].copy()}
+        for f, _ in _lib.CANDIDATE_FIELDS:
+            res[f] = np.ctypeslib.as_array(getattr(cands.contents, f), (max(n * k, 1),))[:n * k].copy().reshape(n, k)
+        self.lib.rattle_hip_candidates_free(cands)
+        return res
+
+    def assign_loaded_top(self, target_ids, read_ids, top, t_s=0.2, t_v=1000000.0, bv_threshold=0.4, use_hc=False, is_rna=False,
+                          target_batch=0, count_pass="auto"):
+        """assign_loaded(), and the `top` (1..8) best targets of every read (rattle_hip_assign_loaded_top).  Returns (assignment,
+        candidates): the dict assign_loaded returns for the same arguments, and a dict with "count" [n] -- min(top, accepting
+        targets) -- and one [n, top] array per field of _lib.CANDIDATE_FIELDS: slot [r, j] is read r's j-th best target (one candidate
+        per target, its better strand, forward on a tie; score descending, ties to the lower target index).  Slots j >= count[r] hold
+        target -1, score -1.0 and zeros.  Slot 0 is the assignment's record."""
+        P = _lib.AssignParams(t_s, t_v, bv_threshold, int(use_hc), int(is_rna), int(target_batch), 0,
+                              {"auto": 0, "seed": 1, "search": 2, "index": 3}[count_pass])
+        t = np.ascontiguousarray(target_ids, np.uint32)
+        r = np.ascontiguousarray(read_ids, np.uint32)
+        out = C.POINTER(_lib.Assignment)()
+        cands = C.POINTER(_lib.Candidates)()
+        check(self.lib.rattle_hip_assign_loaded_top(self.h, C.byref(P), _ptr(t, C.c_uint32) if len(t) else None, len(t),
+                                                    _ptr(r, C.c_uint32) if len(r) else None, len(r), int(top), C.byref(out), C.byref(cands)))
+        return self._take_assignment(out), self._take_candidates(cands)
+
+    def assign_top(self, targets: Sequence[bytes], reads: Sequence[bytes], top, k=10, t_s=0.2, t_v=1000000.0, bv_threshold=0.4,
+                   use_hc=False, is_rna=False, target_batch=0, read_chunk=0, count_pass="auto"):
+        """assign(), and the `top` best targets of every read (rattle_hip_assign_reads_top): (assignment, candidates) as for
+        assign_loaded_top, targets as indices into `targets`."""
+        P = _lib.AssignParams(t_s, t_v, bv_threshold, int(use_hc), int(is_rna), int(target_batch), int(read_chunk),
+                              {"auto": 0, "seed": 1, "search": 2, "index": 3}[count_pass])
+        tcat, toff = pack_reads(targets)
+        rcat, roff = pack_reads(reads)
+        return self.assign_packed_top(tcat, toff, rcat, roff, top, k, P)
+
+    def assign_packed_top(self, tcat: np.ndarray, toff: np.ndarray, rcat: np.ndarray, roff: np.ndarray, top, k=10, params=None):
+        """assign_top() on packed arrays (pack_reads); params: an _lib.AssignParams, None = the defaults of assign()."""
+        P = params if params is not None else _lib.AssignParams(0.2, 1000000.0, 0.4, 0, 0, 0, 0, 0)
+        out = C.POINTER(_lib.Assignment)()
+        cands = C.POINTER(_lib.Candidates)()
+        check(self.lib.rattle_hip_assign_reads_top(self.h, _ptr(tcat, C.c_uint8) if len(tcat) else None, _ptr(toff, C.c_uint64), len(toff) - 1,
+                                                   _ptr(rcat, C.c_uint8) if len(rcat) else None, _ptr(roff, C.c_uint64), len(roff) - 1, k,
+                                                   C.byref(P), int(top), C.byref(out), C.byref(cands)))
+        self.n = self.k = 0               # the loaded read set was replaced by the last chunk's
+        return self._take_assignment(out), self._take_candidates(cands)
+
     @staticmethod
     def _scoring(scoring):
         """(match, mismatch, gap_open, gap_extend), four positive magnitudes, as the library's struct; the library checks the limits"""
@@ -1005,18 +1052,61 @@ def target_counts_tsv(target_names: Sequence[bytes], target_lengths: Sequence[in
         b"%s\t%d\t%d\t%d\n" % (n, int(l), int(reads[i]), int(uniq[i])) for i, (n, l) in enumerate(zip(target_names, target_lengths)))
 
 
-def assign_command(ctx: Context, read_headers: Sequence[bytes], reads: Sequence[bytes], target_headers: Sequence[bytes],
-                   targets: Sequence[bytes], *, k=10, t_s=0.2, t_v=1000000.0, bv_threshold=0.4, is_rna=False, count_pass="auto",
-                   target_batch=0, read_chunk=0):
-    """`rattle assign -i reads -x transcripts` after input parsing: every record of both files takes part, in file order.  Returns the
-    bytes of assignments.tsv and of target_counts.tsv.  A read with a base other than A, C, G, T, U is not compared: unassigned."""
+def _assign_submitted(ctx, reads, targets, k, t_s, t_v, bv_threshold, is_rna, count_pass, target_batch, read_chunk, secondary):
+    """the clean reads through assign (secondary == 0) or assign_top, spread back over all reads: (record, candidates or None)"""
+    if not 0 <= int(secondary) <= 7:
+        raise ValueError("secondary is in 0..7")
     sent = [i for i, s in enumerate(reads) if not s.translate(None, b"ACGTU")]
-    got = ctx.assign(targets, [reads[i] for i in sent], k, t_s, t_v, bv_threshold, False, is_rna, target_batch, read_chunk, count_pass)
     rec = unassigned_records(len(reads))
+    cands = None
+    if secondary:
+        got, part = ctx.assign_top(targets, [reads[i] for i in sent], secondary + 1, k, t_s, t_v, bv_threshold, False, is_rna, target_batch,
+                                   read_chunk, count_pass)
+        cands = unused_candidates(len(reads), secondary + 1)
+        for f in cands:
+            cands[f][sent] = part[f]
+    else:
+        got = ctx.assign(targets, [reads[i] for i in sent], k, t_s, t_v, bv_threshold, False, is_rna, target_batch, read_chunk, count_pass)
     for f in rec:
         rec[f][sent] = got[f]
+    return rec, cands
+
+
+def unused_candidates(n: int, top: int) -> dict:
+    """the candidate lists of n reads that nothing accepts, as the library makes them"""
+    c = {f: np.zeros((n, top), np.dtype(t)) for f, t in _lib.CANDIDATE_FIELDS}
+    c["count"] = np.zeros(n, np.uint32)
+    c["target"][:] = -1
+    c["score"][:] = -1.0
+    return c
+
+
+def candidates_tsv(read_names: Sequence[bytes], target_names: Sequence[bytes], cands: dict) -> bytes:
+    """candidates.tsv as `rattle assign --secondary N` writes it: a header line, then one line per filled slot, in file order of the
+    reads and then by rank: read, rank (0-based), target, strand (+ / -), score, bases, hc_bases, min_len, variance; doubles as
+    %.17g.  A read with no candidate has no line."""
+    lines = [b"read\trank\ttarget\tstrand\tscore\tbases\thc_bases\tmin_len\tvariance\n"]
+    for i, name in enumerate(read_names):
+        for j in range(int(cands["count"][i])):
+            lines.append(b"%s\t%d\t%s\t%s\t%s\t%d\t%d\t%d\t%s\n" % (
+                name, j, target_names[int(cands["target"][i, j])], b"-" if cands["rev"][i, j] else b"+",
+                ("%.17g" % cands["score"][i, j]).encode(), int(cands["bases"][i, j]), int(cands["hc_bases"][i, j]),
+                int(cands["min_len"][i, j]), ("%.17g" % cands["variance"][i, j]).encode()))
+    return b"".join(lines)
+
+
+def assign_command(ctx: Context, read_headers: Sequence[bytes], reads: Sequence[bytes], target_headers: Sequence[bytes],
+                   targets: Sequence[bytes], *, k=10, t_s=0.2, t_v=1000000.0, bv_threshold=0.4, is_rna=False, count_pass="auto",
+                   target_batch=0, read_chunk=0, secondary=0):
+    """`rattle assign -i reads -x transcripts` after input parsing: every record of both files takes part, in file order.  Returns the
+    bytes of assignments.tsv and of target_counts.tsv.  A read with a base other than A, C, G, T, U is not compared: unassigned.
+    secondary=N (1..7) is `--secondary N`: the first two are unchanged and the bytes of candidates.tsv (candidates_tsv, N + 1 slots per
+    read) come third."""
+    rec, cands = _assign_submitted(ctx, reads, targets, k, t_s, t_v, bv_threshold, is_rna, count_pass, target_batch, read_chunk, secondary)
     tn = [_first_token(h) for h in target_headers]
-    return (assignments_tsv([_first_token(h) for h in read_headers], tn, rec), target_counts_tsv(tn, [len(s) for s in targets], rec))
+    rn = [_first_token(h) for h in read_headers]
+    out = (assignments_tsv(rn, tn, rec), target_counts_tsv(tn, [len(s) for s in targets], rec))
+    return out if cands is None else out + (candidates_tsv(rn, tn, cands),)
 
 
 _CIGAR_LETTER = {1: b"I", 2: b"D", 7: b"=", 8: b"X"}
@@ -1027,6 +1117,18 @@ def cigar_bytes(ops) -> bytes:
     return b"".join(b"%d%s" % (int(o) >> 4, _CIGAR_LETTER[int(o) & 15]) for o in ops)
 
 
+def _paf_line(name, lq, tname, lt, rev, alignment, i, tags=b"") -> bytes:
+    """the PAF line of entry i of an alignment record set, up to and including nd:i:, then `tags`; no line end"""
+    M, X, qg, tg = (int(alignment[f][i]) for f in ("matches", "mismatches", "q_gap", "t_gap"))
+    return b"%s\t%d\t%d\t%d\t%s\t%s\t%d\t%d\t%d\t%d\t%d\t255\tAS:i:%d\tNM:i:%d\tnx:i:%d\tni:i:%d\tnd:i:%d%s" % (
+        name, int(lq), int(alignment["q_start"][i]), int(alignment["q_end"][i]), b"-" if rev else b"+", tname, int(lt),
+        int(alignment["t_start"][i]), int(alignment["t_end"][i]), M, M + X + qg + tg, int(alignment["score"][i]), X + qg + tg, X, qg, tg, tags)
+
+
+def _cigar_tag(cigars, i) -> bytes:
+    return b"" if cigars is None else b"\tcg:Z:" + cigar_bytes(cigars[1][int(cigars[0][i]):int(cigars[0][i + 1])])
+
+
 def paf_text(read_names: Sequence[bytes], read_lengths: Sequence[int], target_names: Sequence[bytes], target_lengths: Sequence[int],
              assignment: dict, alignment: dict, cigars=None) -> bytes:
     """alignments.paf as `rattle assign --paf` writes it: one line per read with status 0, in file order (none for unassigned, unaligned
@@ -1034,36 +1136,71 @@ def paf_text(read_names: Sequence[bytes], read_lengths: Sequence[int], target_na
     t_gap), 255, AS:i:score, NM:i:mismatches + q_gap + t_gap, nx:i:mismatches, ni:i:q_gap, nd:i:t_gap.  cigars: (offsets, ops) of
     align_cigars; with them every line ends in a further tag, cg:Z:<the read's CIGAR> (`--paf --cigar`)."""
     lines = []
-    tag = (lambda i: b"") if cigars is None else (lambda i: b"\tcg:Z:" + cigar_bytes(cigars[1][int(cigars[0][i]):int(cigars[0][i + 1])]))
     for i in np.nonzero(np.asarray(alignment["status"]) == 0)[0]:
         t = int(assignment["target"][i])
-        M, X, qg, tg = (int(alignment[f][i]) for f in ("matches", "mismatches", "q_gap", "t_gap"))
-        lines.append(b"%s\t%d\t%d\t%d\t%s\t%s\t%d\t%d\t%d\t%d\t%d\t255\tAS:i:%d\tNM:i:%d\tnx:i:%d\tni:i:%d\tnd:i:%d%s\n" % (
-            read_names[i], int(read_lengths[i]), int(alignment["q_start"][i]), int(alignment["q_end"][i]),
-            b"-" if assignment["rev"][i] else b"+", target_names[t], int(target_lengths[t]), int(alignment["t_start"][i]),
-            int(alignment["t_end"][i]), M, M + X + qg + tg, int(alignment["score"][i]), X + qg + tg, X, qg, tg, tag(i)))
+        lines.append(_paf_line(read_names[i], read_lengths[i], target_names[t], target_lengths[t], assignment["rev"][i], alignment, i,
+                               _cigar_tag(cigars, i)) + b"\n")
     return b"".join(lines)
+
+
+def paf_ranked_text(read_names: Sequence[bytes], read_lengths: Sequence[int], target_names: Sequence[bytes], target_lengths: Sequence[int],
+                    cands: dict, alignments: Sequence[dict], cigars=None) -> bytes:
+    """alignments.paf as `rattle assign --paf --secondary N` writes it.  alignments[j] is the alignment record set of rank j: every
+    read on its slot j (align_ranks); ranks beyond len(alignments) have no line.  One line per (read, rank) whose own alignment has
+    status 0, in file order of the reads and then by rank; the fields of paf_text, then tp:A:P (rank 0) or tp:A:S and rk:i:<rank>
+    behind nd:i: and, with cigars (one (offsets, ops) per rank), before cg:Z:."""
+    lines = []
+    ok = [np.asarray(a["status"]) == 0 for a in alignments]
+    for i, name in enumerate(read_names):
+        for j in range(min(int(cands["count"][i]), len(alignments))):
+            if not ok[j][i]:
+                continue
+            t = int(cands["target"][i, j])
+            tags = (b"\ttp:A:P" if j == 0 else b"\ttp:A:S") + b"\trk:i:%d" % j + _cigar_tag(None if cigars is None else cigars[j], i)
+            lines.append(_paf_line(name, read_lengths[i], target_names[t], target_lengths[t], cands["rev"][i, j], alignments[j], i, tags) + b"\n")
+    return b"".join(lines)
+
+
+def align_ranks(ctx: Context, targets: Sequence[bytes], reads: Sequence[bytes], cands: dict, max_cells=0, pair_chunk=0, cigar=False,
+                scoring=None):
+    """Every read aligned to each of its candidates: one call of Context.align_pairs (cigar: align_cigars) per rank j, with slot j's
+    target and strand as target_of_read and rev, up to the first rank no read has.  Returns (alignments, cigars): one record set
+    per rank, and one (offsets, ops) per rank or None."""
+    alns, cgs = [], []
+    for j in range(cands["target"].shape[1]):
+        if not (np.asarray(cands["count"]) > j).any():
+            break
+        t = np.ascontiguousarray(cands["target"][:, j]); r = np.ascontiguousarray(cands["rev"][:, j])
+        if cigar:
+            aln, offsets, ops = ctx.align_cigars(targets, reads, t, r, max_cells, pair_chunk, scoring)
+            cgs.append((offsets, ops))
+        else:
+            aln = ctx.align_pairs(targets, reads, t, r, max_cells, pair_chunk, scoring)
+        alns.append(aln)
+    return alns, (cgs if cigar else None)
 
 
 def assign_paf_command(ctx: Context, read_headers: Sequence[bytes], reads: Sequence[bytes], target_headers: Sequence[bytes],
                        targets: Sequence[bytes], *, k=10, t_s=0.2, t_v=1000000.0, bv_threshold=0.4, is_rna=False, count_pass="auto",
-                       target_batch=0, read_chunk=0, max_cells=0, pair_chunk=0, cigar=False, scoring=None):
+                       target_batch=0, read_chunk=0, max_cells=0, pair_chunk=0, cigar=False, scoring=None, secondary=0):
     """`rattle assign --paf`: assign_command, then every placed read aligned to its transcript (Context.align_pairs).  Returns the bytes
     of assignments.tsv, target_counts.tsv and alignments.paf; the first two are what assign_command returns.  cigar=True is
     `--paf --cigar`: Context.align_cigars, and a cg:Z: tag on every line.  scoring=(m, x, o, e) is `--paf-scoring m,x,o,e`: affine gaps
-    (Context.align_pairs); None is the linear default."""
-    sent = [i for i, s in enumerate(reads) if not s.translate(None, b"ACGTU")]
-    got = ctx.assign(targets, [reads[i] for i in sent], k, t_s, t_v, bv_threshold, False, is_rna, target_batch, read_chunk, count_pass)
-    rec = unassigned_records(len(reads))
-    for f in rec:
-        rec[f][sent] = got[f]
+    (Context.align_pairs); None is the linear default.  secondary=N (1..7) is `--secondary N`: every read is aligned to each of its
+    N + 1 candidates (align_ranks), alignments.paf is the ranked one (paf_ranked_text) and the bytes of candidates.tsv come fourth."""
+    rec, cands = _assign_submitted(ctx, reads, targets, k, t_s, t_v, bv_threshold, is_rna, count_pass, target_batch, read_chunk, secondary)
+    tn = [_first_token(h) for h in target_headers]
+    rn = [_first_token(h) for h in read_headers]
+    tl = [len(s) for s in targets]
+    rl = [len(s) for s in reads]
+    if cands is not None:
+        alns, cgs = align_ranks(ctx, targets, reads, cands, max_cells, pair_chunk, cigar, scoring)
+        return (assignments_tsv(rn, tn, rec), target_counts_tsv(tn, tl, rec), paf_ranked_text(rn, rl, tn, tl, cands, alns, cgs),
+                candidates_tsv(rn, tn, cands))
     cigars = None
     if cigar:
         aln, offsets, ops = ctx.align_cigars(targets, reads, rec["target"], rec["rev"], max_cells, pair_chunk, scoring)
         cigars = (offsets, ops)
     else:
         aln = ctx.align_pairs(targets, reads, rec["target"], rec["rev"], max_cells, pair_chunk, scoring)
-    tn = [_first_token(h) for h in target_headers]
-    rn = [_first_token(h) for h in read_headers]
-    tl = [len(s) for s in targets]
-    return (assignments_tsv(rn, tn, rec), target_counts_tsv(tn, tl, rec), paf_text(rn, [len(s) for s in reads], tn, tl, rec, aln, cigars))
+    return (assignments_tsv(rn, tn, rec), target_counts_tsv(tn, tl, rec), paf_text(rn, rl, tn, tl, rec, aln, cigars))

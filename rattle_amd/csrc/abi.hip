@@ -556,10 +556,28 @@ static rattle_assignment *new_assignment(uint32_t n) {
     return A;
 }
 
-// what both entry points require of their parameters and of the context, in the order the header promises: arguments, then the
-// refusal of a sharded job (before anything is exchanged), then the device
-static int assign_enter(rattle_ctx *c, const rattle_assign_params *P) {
+// n reads of k slots, every slot unused
+static rattle_candidates *new_candidates(uint32_t n, uint32_t k) {
+    const size_t m = std::max<size_t>(1, (size_t)n * k);
+    rattle_candidates *C = (rattle_candidates *)calloc(1, sizeof(rattle_candidates));
+    C->n = n; C->k = k;
+    C->count = (uint32_t *)calloc(std::max<size_t>(1, n), 4);
+    C->target = (int32_t *)malloc(4 * m); C->rev = (uint8_t *)calloc(m, 1);
+    C->bases = (int32_t *)calloc(m, 4); C->hc_bases = (int32_t *)calloc(m, 4); C->min_len = (uint32_t *)calloc(m, 4);
+    C->score = (double *)malloc(8 * m); C->variance = (double *)calloc(m, 8);
+    for (size_t i = 0; i < m; ++i) { C->target[i] = -1; C->score[i] = -1.0; }
+    return C;
+}
+
+// the candidate list a call asks for (the _top entry points): none for the plain ones
+struct top_request { bool on; uint32_t k; rattle_candidates **cands; };
+
+// what the entry points require of their parameters and of the context, in the order the header promises: arguments (the _top
+// calls' own last), then the refusal of a sharded job (before anything is exchanged), then the device
+static int assign_enter(rattle_ctx *c, const rattle_assign_params *P, const top_request &T) {
     if (P->count_pass < 0 || P->count_pass > 3) { set_error("count_pass must be 0 (auto), 1 (seed-major), 2 (search) or 3 (index)"); return RATTLE_ERR_ARG; }
+    if (T.on && (T.k < 1 || T.k > 8)) { set_error("k, the candidates per read, must be in [1,8]"); return RATTLE_ERR_ARG; }
+    if (T.on && !T.cands) { set_error("null argument"); return RATTLE_ERR_ARG; }
     if (c->xchg.nranks > 1) {
         set_error("assign is not available on a context that is one rank of several: sharded jobs are not built, assign on one device");
         return RATTLE_ERR_STATE;
@@ -567,12 +585,13 @@ static int assign_enter(rattle_ctx *c, const rattle_assign_params *P) {
     return use_device(c);
 }
 
-int rattle_hip_assign_loaded(rattle_ctx *c, const rattle_assign_params *P, const uint32_t *tids, uint32_t nt, const uint32_t *rids,
-                             uint32_t nr, rattle_assignment **out) {
+static int assign_loaded(rattle_ctx *c, const rattle_assign_params *P, const uint32_t *tids, uint32_t nt, const uint32_t *rids, uint32_t nr,
+                         rattle_assignment **out, const top_request &T) {
     if (out) *out = nullptr;
+    if (T.cands) *T.cands = nullptr;
     if (!c || !P || !out || (nt && !tids) || (nr && !rids)) { set_error("null argument"); return RATTLE_ERR_ARG; }
     if (nt >= (1u << 31)) { set_error("too many targets"); return RATTLE_ERR_ARG; }
-    RT_TRY(assign_enter(c, P));
+    RT_TRY(assign_enter(c, P, T));
     if (nt && nr) {
         if (c->idx.k == 0) { set_error("no reads loaded"); return RATTLE_ERR_STATE; }
         if (!P->is_rna && !c->idx.both) { set_error("cDNA mode needs the reads loaded with both_strands=1"); return RATTLE_ERR_STATE; }
@@ -581,22 +600,36 @@ int rattle_hip_assign_loaded(rattle_ctx *c, const rattle_assign_params *P, const
         for (uint32_t i = 0; i < nr; ++i) if (rids[i] >= c->idx.n) { set_error("read id out of range"); return RATTLE_ERR_ARG; }
     }
     rattle_assignment *A = new_assignment(nr);
-    const int rc = assign_driver(c, P, tids, nt, rids, nr, A, 0);
-    if (rc != 0) { rattle_hip_assignment_free(A); return rc; }
+    rattle_candidates *C = T.on ? new_candidates(nr, T.k) : nullptr;
+    const int rc = assign_driver(c, P, tids, nt, rids, nr, A, 0, C);
+    if (rc != 0) { rattle_hip_assignment_free(A); rattle_hip_candidates_free(C); return rc; }
     *out = A;
+    if (T.on) *T.cands = C;
     return 0;
 }
 
-int rattle_hip_assign_reads(rattle_ctx *c, const uint8_t *tseq, const uint64_t *toff, uint32_t nt, const uint8_t *rseq, const uint64_t *roff,
-                            uint32_t nr, int k, const rattle_assign_params *P, rattle_assignment **out) {
+int rattle_hip_assign_loaded(rattle_ctx *c, const rattle_assign_params *P, const uint32_t *tids, uint32_t nt, const uint32_t *rids,
+                             uint32_t nr, rattle_assignment **out) {
+    return assign_loaded(c, P, tids, nt, rids, nr, out, top_request{false, 0, nullptr});
+}
+
+int rattle_hip_assign_loaded_top(rattle_ctx *c, const rattle_assign_params *P, const uint32_t *tids, uint32_t nt, const uint32_t *rids,
+                                 uint32_t nr, uint32_t k, rattle_assignment **out, rattle_candidates **cands) {
+    return assign_loaded(c, P, tids, nt, rids, nr, out, top_request{true, k, cands});
+}
+
+static int assign_reads(rattle_ctx *c, const uint8_t *tseq, const uint64_t *toff, uint32_t nt, const uint8_t *rseq, const uint64_t *roff,
+                        uint32_t nr, int k, const rattle_assign_params *P, rattle_assignment **out, const top_request &T) {
     if (out) *out = nullptr;
+    if (T.cands) *T.cands = nullptr;
     if (!c || !P || !out || !toff || !roff || (nt && !tseq) || (nr && !rseq)) { set_error("null argument"); return RATTLE_ERR_ARG; }
     if (k < 1 || k > 16) { set_error("kmer size must be in [1,16] (main.cpp:223)"); return RATTLE_ERR_ARG; }
     if (nt >= (1u << 31)) { set_error("too many targets"); return RATTLE_ERR_ARG; }
-    RT_TRY(assign_enter(c, P));
+    RT_TRY(assign_enter(c, P, T));
     phase_timer T_all("assign_reads: total");
     rattle_assignment *A = new_assignment(nr);
-    struct freer { rattle_assignment *p; ~freer() { rattle_hip_assignment_free(p); } } guard{A};
+    rattle_candidates *C = T.on ? new_candidates(nr, T.k) : nullptr;
+    struct freer { rattle_assignment *p; rattle_candidates *q; ~freer() { rattle_hip_assignment_free(p); rattle_hip_candidates_free(q); } } guard{A, C};
     const uint64_t tbytes = nt ? toff[nt] - toff[0] : 0;
     const uint32_t chunk = (uint32_t)std::min<uint64_t>(P->read_chunk ? P->read_chunk : 1u << 20, 0xFFFFFFF0ull - nt);
     std::vector<uint32_t> tids(nt), rids;
@@ -616,11 +649,29 @@ int rattle_hip_assign_reads(rattle_ctx *c, const uint8_t *tseq, const uint64_t *
         RT_TRY(build_index(c, cat.get(), off.data(), nt + m, k, P->is_rna ? 0 : 1));
         rids.resize(m);
         for (uint32_t i = 0; i < m; ++i) rids[i] = nt + i;
-        RT_TRY(assign_driver(c, P, tids.data(), nt, rids.data(), m, A, (uint32_t)r0));
+        RT_TRY(assign_driver(c, P, tids.data(), nt, rids.data(), m, A, (uint32_t)r0, C));
     }
-    guard.p = nullptr;
+    guard.p = nullptr; guard.q = nullptr;
     *out = A;
+    if (T.on) *T.cands = C;
     return 0;
+}
+
+int rattle_hip_assign_reads(rattle_ctx *c, const uint8_t *tseq, const uint64_t *toff, uint32_t nt, const uint8_t *rseq, const uint64_t *roff,
+                            uint32_t nr, int k, const rattle_assign_params *P, rattle_assignment **out) {
+    return assign_reads(c, tseq, toff, nt, rseq, roff, nr, k, P, out, top_request{false, 0, nullptr});
+}
+
+int rattle_hip_assign_reads_top(rattle_ctx *c, const uint8_t *tseq, const uint64_t *toff, uint32_t nt, const uint8_t *rseq, const uint64_t *roff,
+                                uint32_t nr, int kmer_size, const rattle_assign_params *P, uint32_t k, rattle_assignment **out,
+                                rattle_candidates **cands) {
+    return assign_reads(c, tseq, toff, nt, rseq, roff, nr, kmer_size, P, out, top_request{true, k, cands});
+}
+
+void rattle_hip_candidates_free(rattle_candidates *c) {
+    if (!c) return;
+    free(c->count); free(c->target); free(c->rev); free(c->bases); free(c->hc_bases); free(c->min_len); free(c->score); free(c->variance);
+    free(c);
 }
 
 void rattle_hip_assignment_free(rattle_assignment *a) {

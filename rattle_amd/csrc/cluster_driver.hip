@@ -243,6 +243,7 @@ struct evaluator {
     // evaluation: target batch x reads); the batch's state and the index of the batch's first target
     const assign_dev *best = nullptr;
     uint32_t best_base = 0;
+    const top_dev *top = nullptr;             // the batch's candidate list, if the call asks for one (assign_*_top)
     // RATTLE_TIMING: where the host's wall time of a clustering goes, by run_local's laps.  Lap 3 is the crediting of the count bound's
     // statistics to the jobs (the line prints it as "host bound test": the test itself has run on the device since round 3).
     double t_split[5] = {0, 0, 0, 0, 0};
@@ -638,6 +639,12 @@ struct evaluator {
         if (V.hv[1]) RT_TRY(oversize_pass(V, pass1));
         RT_TRY(launch_assign_pick(ctx, V.n2, use_hc, P->t_s, P->t_v, best_base, *best));
         launches += 2;
+        // the candidate list is a further ending over the same pairs, behind the oversize pass like passes 2 and 3 (it starts from their
+        // record); it adds no synchronisation
+        if (top) {
+            RT_TRY(launch_assign_top(ctx, V.n2, (uint32_t)V.nc, use_hc, P->t_s, P->t_v, best_base, *best, *top));
+            launches += top->k > 1 ? 2 * top->k : 1;
+        }
         return 0;
     }
 
@@ -1141,9 +1148,10 @@ int debug_evaluate(rattle_ctx *ctx, const rattle_cluster_params *P, int count_mo
 
 // `assign`: the loaded reads read_ids against the loaded reads target_ids, the targets as seeds in batches against all the reads, every
 // batch one evaluation that ends in the per-read reduction; the batches' states are folded on the device in target order and the
-// call's state -- 40 bytes per read -- is the only thing copied back.
+// call's state -- 40 bytes per read -- is the only thing copied back.  With C the batches also leave their k best targets per read
+// (assign.hip, the candidate list), folded in the same way: 4 + 28 k bytes per read more, in both states and on the way back.
 int assign_driver(rattle_ctx *ctx, const rattle_assign_params *AP, const uint32_t *tids, uint32_t nt, const uint32_t *rids, uint32_t nr,
-                  rattle_assignment *A, uint32_t out_base) {
+                  rattle_assignment *A, uint32_t out_base, rattle_candidates *C) {
     if (nt == 0 || nr == 0) return 0;                    // (the records start out unassigned)
     hipStream_t st = ctx->stream;
     const read_index &X = ctx->idx;
@@ -1154,9 +1162,16 @@ int assign_driver(rattle_ctx *ctx, const rattle_assign_params *AP, const uint32_
     RT_TRY(batch.reserve(nr)); RT_TRY(call.reserve(nr));
     RT_TRY(batch.clear(st, nr)); RT_TRY(call.clear(st, nr));
     const assign_dev B = batch.dev(), G = call.dev();
+    top_state tbatch, tcall;
+    if (C) {
+        RT_TRY(tbatch.reserve(nr, C->k)); RT_TRY(tcall.reserve(nr, C->k));
+        RT_TRY(tbatch.clear(st, nr)); RT_TRY(tcall.clear(st, nr));
+    }
+    const top_dev TB = tbatch.dev(), TG = tcall.dev();
     evaluator E{ctx, &CP};
     E.count_mode = AP->count_pass;
     E.best = &B;
+    if (C) E.top = &TB;
     uint64_t counters[8] = {0, 0, 0, 0, 0, 0, 0, 0};
     request rq;
     rq.cands.assign(rids, rids + nr);
@@ -1169,6 +1184,7 @@ int assign_driver(rattle_ctx *ctx, const rattle_assign_params *AP, const uint32_
         E.best_base = t0;
         RT_TRY(E.run_chunks(reqs));
         RT_TRY(launch_assign_merge(ctx, nr, B, G));
+        if (C) RT_TRY(launch_assign_top_merge(ctx, nr, TB, TG));
     }
     std::vector<unsigned long long> best(nr), second(nr);
     std::vector<uint32_t> key(nr), n(nr);
@@ -1194,6 +1210,31 @@ int assign_driver(rattle_ctx *ctx, const rattle_assign_params *AP, const uint32_
         A->score[o] = score_of(best[r]);
         A->second_score[o] = second[r] ? score_of(second[r]) : -1.0;
         A->n_accepted[o] = n[r];
+    }
+    if (!C) return 0;
+    const uint32_t k = C->k;
+    std::vector<unsigned long long> pat((size_t)nr * k);
+    std::vector<uint32_t> tkey((size_t)nr * k), cnt(nr);
+    std::vector<hit_evidence> tev((size_t)nr * k);
+    RT_HIP(hipMemcpyAsync(pat.data(), TG.pat, pat.size() * 8, hipMemcpyDeviceToHost, st));
+    RT_HIP(hipMemcpyAsync(tkey.data(), TG.key, tkey.size() * 4, hipMemcpyDeviceToHost, st));
+    RT_HIP(hipMemcpyAsync(tev.data(), TG.ev, tev.size() * sizeof(uint4), hipMemcpyDeviceToHost, st));
+    RT_HIP(hipMemcpyAsync(cnt.data(), TG.cnt, (size_t)nr * 4, hipMemcpyDeviceToHost, st));
+    RT_HIP(hipStreamSynchronize(st));
+    ctx->stats[K_ASSIGN].bytes += (4ull + 28ull * k) * nr;
+    for (uint32_t r = 0; r < nr; ++r) {
+        if (cnt[r] > k) { set_error("assign: more candidates than slots"); return RATTLE_ERR_HIP; }
+        C->count[(size_t)out_base + r] = cnt[r];
+        for (uint32_t j = 0; j < cnt[r]; ++j) {
+            const size_t s = (size_t)r * k + j, o = ((size_t)out_base + r) * k + j;
+            const uint32_t t = tkey[s] >> 1;
+            if (pat[s] == 0 || t >= nt) { set_error("assign: a candidate outside the targets"); return RATTLE_ERR_HIP; }
+            const uint32_t li = X.h_len[tids[t]], lj = X.h_len[rids[r]];
+            C->target[o] = (int32_t)t; C->rev[o] = (uint8_t)(tkey[s] & 1u);
+            C->bases[o] = tev[s].bases; C->hc_bases[o] = tev[s].hc; C->variance[o] = tev[s].var;
+            C->min_len[o] = li < lj ? li : lj;
+            C->score[o] = score_of(pat[s]);
+        }
     }
     return 0;
 }

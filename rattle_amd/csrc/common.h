@@ -335,6 +335,19 @@ struct assign_state {
     int clear(hipStream_t st, size_t nr);
     assign_dev dev() const { return assign_dev{best.p, second.p, key.p, n.p, ev.p}; }
 };
+// The candidate list (`assign_*_top`): k slots per read, slot r * k + j the read's j-th best target.  pat: bit pattern of the slot's
+// score + 1 (0: unused; a read's slots are filled from 0 without a hole); key: target index << 1 | strand (0xFFFFFFFF: unused); ev: as
+// assign_dev::ev; cnt: filled slots (kept by the merge in the call's state only).  28 bytes per slot, 4 per read.
+struct top_dev { unsigned long long *pat; uint32_t *key; uint4 *ev; uint32_t *cnt; uint32_t k; };
+struct top_state {
+    dbuf<unsigned long long> pat;
+    dbuf<uint32_t> key, cnt;
+    dbuf<uint4> ev;
+    uint32_t k = 0;
+    int reserve(size_t nr, uint32_t k_);
+    int clear(hipStream_t st, size_t nr);
+    top_dev dev() const { return top_dev{pat.p, key.p, ev.p, cnt.p, k}; }
+};
 
 int hw_queues();      // hardware queues the HIP runtime of this process hands out (settled when the library is loaded, abi.hip)
 
@@ -462,6 +475,11 @@ int launch_assign_max(rattle_ctx *ctx, uint32_t n, const uint32_t *d_remap, int 
                       uint32_t *d_big, const assign_dev &B);
 int launch_assign_pick(rattle_ctx *ctx, uint32_t n, int use_hc, double t_s, double t_v, uint32_t target_base, const assign_dev &B);
 int launch_assign_merge(rattle_ctx *ctx, uint32_t nr, const assign_dev &B, const assign_dev &G);
+// the candidate list of the batch: slots 0 .. T.k - 1 of every read over the same n kept pairs, after launch_assign_pick and before
+// launch_assign_merge (it reads B); then the batch's slots TB folded into the call's TG, TB left cleared
+int launch_assign_top(rattle_ctx *ctx, uint32_t n, uint32_t nr, int use_hc, double t_s, double t_v, uint32_t target_base, const assign_dev &B,
+                      const top_dev &T);
+int launch_assign_top_merge(rattle_ctx *ctx, uint32_t nr, const top_dev &TB, const top_dev &TG);
 // poa.hip : the words of kernel C's counter block (poa_args::counters, POA_CNT_WORDS on the device); poa_device_run hands the first
 // POA_CNT_PUBLIC of them back in h_cnt.  The only place that says which slot is what.  The measurement builds reuse slots by number:
 // POA_PREDSTAT 4 .. 6, POA_PROFILE 2 and 4 .. 7, POA_BARPROF 8 .. 15 (and POA_CNT_BARPROF ..), POA_HIST 16 + d and 80 + d.
@@ -501,8 +519,9 @@ int cluster_driver(rattle_ctx *ctx, const rattle_cluster_params *P, const uint32
 int debug_evaluate(rattle_ctx *ctx, const rattle_cluster_params *P, int count_mode, const rattle_debug_rect *R, uint32_t n_rects,
                    rattle_debug_eval **out);
 // records [out_base, out_base + n_reads) of A: the loaded reads read_ids placed on the loaded reads target_ids
+// C (or nullptr): the candidate lists of the same reads, slots [out_base * C->k, (out_base + n_reads) * C->k), and their counts
 int assign_driver(rattle_ctx *ctx, const rattle_assign_params *P, const uint32_t *target_ids, uint32_t n_targets, const uint32_t *read_ids,
-                  uint32_t n_reads, rattle_assignment *A, uint32_t out_base);
+                  uint32_t n_reads, rattle_assignment *A, uint32_t out_base, rattle_candidates *C = nullptr);
 // pair_cigar.hip : kernel F, the CIGAR of every pair kernel E aligned, chunk by chunk of kernel E while its sequences are on the device
 struct cigar_pair {                     // one pair of a launch: where its rectangle's sequences, code records, strip and ops region lie
     uint64_t q, t;                      // byte offsets of the rectangle's first row (reverse strand: its last base as given) and first column

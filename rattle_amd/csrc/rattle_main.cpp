@@ -768,7 +768,8 @@ int mode_cluster(int argc, char **argv) {
 // The reads of -i placed on the transcripts of -x by their best cluster_together score (include/rattle_hip.h, "assign").
 // Every record of both files takes part, in file order: there is no length filter and no sort.  A read with a base other than A, C,
 // G, T, U is not compared and comes out unassigned (`cluster` skips such reads).  --paf: every placed read is then aligned to its transcript
-// (include/rattle_hip.h, "align_pairs") and alignments.paf appears beside the two tables.
+// (include/rattle_hip.h, "align_pairs") and alignments.paf appears beside the two tables.  --secondary N: the N next-best transcripts of
+// every read beside its best (include/rattle_hip.h, "The candidate list") as candidates.tsv, and with --paf each of them aligned.
 struct assign_job {
     args_t a;
     int k = 10;
@@ -781,11 +782,13 @@ struct assign_job {
     byte_buf rcat, xcat;
     std::vector<uint64_t> roff, xoff;
     rattle_assignment *A = nullptr;
+    uint32_t secondary = 0;                       // --secondary N: N + 1 candidates per read
+    rattle_candidates *C = nullptr;
     bool want_paf = false, want_cigar = false;     // --paf, --cigar (cg:Z: on every PAF line)
     rattle_align_params AP;
     bool want_scoring = false;                    // --paf-scoring m,x,o,e: affine gaps, the three-state kernels
     rattle_align_scoring AS;
-    std::string text, counts, paf;               // assignments.tsv, target_counts.tsv, alignments.paf (--paf)
+    std::string text, counts, paf, cand;         // assignments.tsv, target_counts.tsv, alignments.paf (--paf), candidates.tsv (--secondary)
     void options(int argc, char **argv) {
         a = parse(argc, argv, {
             {"help", {"-h", "--help"}, false}, {"input", {"-i", "--input"}, true}, {"targets", {"-x", "--transcripts"}, true},
@@ -793,8 +796,9 @@ struct assign_job {
             {"t_v", {"-v", "--max-variance"}, true}, {"bv_threshold", {"-B", "--bv-start-threshold"}, true}, {"rna", {"--rna"}, false},
             {"count-pass", {"--count-pass"}, true}, {"device", {"--device"}, true}, {"devices", {"--devices"}, true},
             {"target-batch", {"--target-batch"}, true}, {"read-chunk", {"--read-chunk"}, true}, {"paf", {"--paf"}, false},
-            {"paf-max-cells", {"--paf-max-cells"}, true}, {"cigar", {"--cigar"}, false}, {"paf-scoring", {"--paf-scoring"}, true}});
-        const char *usage = "rattle assign -i reads.fq -x transcripts.fq [-o dir] [-k 10] [-s 0.2] [-v 1000000] [-B 0.4] [--rna] [--device n] [--paf [--cigar]]\n"
+            {"paf-max-cells", {"--paf-max-cells"}, true}, {"cigar", {"--cigar"}, false}, {"paf-scoring", {"--paf-scoring"}, true},
+            {"secondary", {"--secondary"}, true}});
+        const char *usage = "rattle assign -i reads.fq -x transcripts.fq [-o dir] [-k 10] [-s 0.2] [-v 1000000] [-B 0.4] [--rna] [--device n] [--paf [--cigar]] [--secondary n]\n"
                             "  places every read of -i on the transcript of -x that accepts it with the best score (the comparison `cluster` joins\n"
                             "  reads by, the transcript in the seed's role) and writes assignments.tsv (one line per read: target, strand, score,\n"
                             "  second_score, n_accepted, bases, hc_bases, min_len, variance) and target_counts.tsv (reads per transcript)\n"
@@ -807,7 +811,11 @@ struct assign_job {
                             "                                        in the extended set (= match, X mismatch, I read base on a gap, D transcript base on a gap)\n"
                             "  --paf-scoring m,x,o,e                 with --paf: affine gaps and this scoring, four positive integers: match +m, mismatch -x,\n"
                             "                                        the first column of a gap -o, every further one -e; each in 1..64, e <= o.  5,4,8,6 is the\n"
-                            "                                        scoring of `correct`, 2,4,4,2 minimap2's.  Default: linear gaps, 5,4,8,8\n";
+                            "                                        scoring of `correct`, 2,4,4,2 minimap2's.  Default: linear gaps, 5,4,8,8\n"
+                            "  --secondary n                         n in 1..7: also write candidates.tsv, the best transcript of every read and its n next-best\n"
+                            "                                        (one line per read and rank: read, rank, target, strand, score, bases, hc_bases, min_len,\n"
+                            "                                        variance); with --paf every one of them is aligned, and each line of alignments.paf carries\n"
+                            "                                        tp:A:P (rank 0) or tp:A:S and rk:i:<rank>.  The other two files do not change\n";
         if (a.has("help")) { std::cerr << usage; exit(EXIT_SUCCESS); }
         if (!a.has("input")) die("ERROR: No input file provided (-i reads)");
         if (!a.has("targets")) die("ERROR: No transcript file provided (-x transcripts)");
@@ -838,6 +846,11 @@ struct assign_job {
             if (w[3] > w[2]) die(limit);
             AS.match = w[0]; AS.mismatch = w[1]; AS.gap_open = w[2]; AS.gap_extend = w[3];
         }
+        if (a.has("secondary")) {
+            const std::string v = a.str("secondary", "");
+            if (v.size() != 1 || v[0] < '1' || v[0] > '7') die("\nError: --secondary takes a number of further transcripts per read in 1..7\n");
+            secondary = (uint32_t)(v[0] - '0');
+        }
         memset(&AP, 0, sizeof AP);
         AP.max_cells = std::stoull(a.str("paf-max-cells", "0"));
         P.target_batch = (uint32_t)std::max(0, a.i("target-batch", 0)); P.read_chunk = (uint32_t)std::max(0, a.i("read-chunk", 0));
@@ -862,40 +875,87 @@ struct assign_job {
     }
     void run() {
         cli_timer t("library: assign");
-        chk(rattle_hip_assign_reads(team.ctx[0], xcat.data(), xoff.data(), (uint32_t)xid.size(), rcat.data(), roff.data(), (uint32_t)rid.size(), k, &P, &A));
+        if (secondary) chk(rattle_hip_assign_reads_top(team.ctx[0], xcat.data(), xoff.data(), (uint32_t)xid.size(), rcat.data(), roff.data(), (uint32_t)rid.size(), k, &P, secondary + 1, &A, &C));
+        else chk(rattle_hip_assign_reads(team.ctx[0], xcat.data(), xoff.data(), (uint32_t)xid.size(), rcat.data(), roff.data(), (uint32_t)rid.size(), k, &P, &A));
+    }
+    // the submitted reads on target[r] / rev[r] each (-1: not aligned): one call of the library
+    void align_on(const int32_t *target, const uint8_t *rev, rattle_alignment **L, rattle_cigars **G) {
+        if (want_scoring && want_cigar) chk(rattle_hip_align_cigars_scored(team.ctx[0], xcat.data(), xoff.data(), (uint32_t)xid.size(), rcat.data(), roff.data(), (uint32_t)rid.size(), target, rev, &AP, &AS, L, G));
+        else if (want_scoring) chk(rattle_hip_align_pairs_scored(team.ctx[0], xcat.data(), xoff.data(), (uint32_t)xid.size(), rcat.data(), roff.data(), (uint32_t)rid.size(), target, rev, &AP, &AS, L));
+        else if (want_cigar) chk(rattle_hip_align_cigars(team.ctx[0], xcat.data(), xoff.data(), (uint32_t)xid.size(), rcat.data(), roff.data(), (uint32_t)rid.size(), target, rev, &AP, L, G));
+        else chk(rattle_hip_align_pairs(team.ctx[0], xcat.data(), xoff.data(), (uint32_t)xid.size(), rcat.data(), roff.data(), (uint32_t)rid.size(), target, rev, &AP, L));
+    }
+    // the PAF line of submitted read `at` on transcript x; tags: what stands between nd:i: and cg:Z:
+    void paf_line(uint32_t at, uint32_t x, bool rev, const rattle_alignment *L, const rattle_cigars *G, const std::string &tags) {
+        const uint64_t gaps = (uint64_t)L->q_gap[at] + L->t_gap[at], cols = (uint64_t)L->matches[at] + L->mismatches[at] + gaps;
+        paf += record_name(R.header[rid[at]]) + "\t" + std::to_string(R.seq[rid[at]].n) + "\t" + std::to_string(L->q_start[at]) + "\t" + std::to_string(L->q_end[at]) + "\t" +
+               (rev ? "-" : "+") + "\t" + record_name(X.header[x]) + "\t" + std::to_string(X.seq[x].n) + "\t" + std::to_string(L->t_start[at]) + "\t" +
+               std::to_string(L->t_end[at]) + "\t" + std::to_string(L->matches[at]) + "\t" + std::to_string(cols) + "\t255\tAS:i:" + std::to_string(L->score[at]) +
+               "\tNM:i:" + std::to_string(L->mismatches[at] + gaps) + "\tnx:i:" + std::to_string(L->mismatches[at]) + "\tni:i:" + std::to_string(L->q_gap[at]) +
+               "\tnd:i:" + std::to_string(L->t_gap[at]) + tags;
+        if (G) {
+            paf += "\tcg:Z:";
+            for (uint64_t o = G->offset[at]; o < G->offset[at + 1]; ++o) {
+                const uint32_t op = G->ops[o] & 15u;
+                paf += std::to_string(G->ops[o] >> 4) + (op == 7 ? "=" : op == 8 ? "X" : op == 1 ? "I" : "D");
+            }
+        }
+        paf += "\n";
     }
     // --paf: the submitted reads on the transcripts `run` placed them on; one PAF line per read that aligns, in file order
     void align() {
         cli_timer t(want_cigar ? "library: align_cigars" : "library: align_pairs");
         rattle_alignment *L = nullptr;
         rattle_cigars *G = nullptr;
-        if (want_scoring && want_cigar) chk(rattle_hip_align_cigars_scored(team.ctx[0], xcat.data(), xoff.data(), (uint32_t)xid.size(), rcat.data(), roff.data(), (uint32_t)rid.size(), A->target, A->rev, &AP, &AS, &L, &G));
-        else if (want_scoring) chk(rattle_hip_align_pairs_scored(team.ctx[0], xcat.data(), xoff.data(), (uint32_t)xid.size(), rcat.data(), roff.data(), (uint32_t)rid.size(), A->target, A->rev, &AP, &AS, &L));
-        else if (want_cigar) chk(rattle_hip_align_cigars(team.ctx[0], xcat.data(), xoff.data(), (uint32_t)xid.size(), rcat.data(), roff.data(), (uint32_t)rid.size(), A->target, A->rev, &AP, &L, &G));
-        else chk(rattle_hip_align_pairs(team.ctx[0], xcat.data(), xoff.data(), (uint32_t)xid.size(), rcat.data(), roff.data(), (uint32_t)rid.size(), A->target, A->rev, &AP, &L));
+        align_on(A->target, A->rev, &L, &G);
         uint64_t skipped = 0;
         for (uint32_t at = 0; at < L->n; ++at) {
             skipped += L->status[at] == 2;
-            if (L->status[at] != 0) continue;
-            const uint32_t x = (uint32_t)A->target[at];
-            const uint64_t gaps = (uint64_t)L->q_gap[at] + L->t_gap[at], cols = (uint64_t)L->matches[at] + L->mismatches[at] + gaps;
-            paf += record_name(R.header[rid[at]]) + "\t" + std::to_string(R.seq[rid[at]].n) + "\t" + std::to_string(L->q_start[at]) + "\t" + std::to_string(L->q_end[at]) + "\t" +
-                   (A->rev[at] ? "-" : "+") + "\t" + record_name(X.header[x]) + "\t" + std::to_string(X.seq[x].n) + "\t" + std::to_string(L->t_start[at]) + "\t" +
-                   std::to_string(L->t_end[at]) + "\t" + std::to_string(L->matches[at]) + "\t" + std::to_string(cols) + "\t255\tAS:i:" + std::to_string(L->score[at]) +
-                   "\tNM:i:" + std::to_string(L->mismatches[at] + gaps) + "\tnx:i:" + std::to_string(L->mismatches[at]) + "\tni:i:" + std::to_string(L->q_gap[at]) +
-                   "\tnd:i:" + std::to_string(L->t_gap[at]);
-            if (G) {
-                paf += "\tcg:Z:";
-                for (uint64_t o = G->offset[at]; o < G->offset[at + 1]; ++o) {
-                    const uint32_t op = G->ops[o] & 15u;
-                    paf += std::to_string(G->ops[o] >> 4) + (op == 7 ? "=" : op == 8 ? "X" : op == 1 ? "I" : "D");
-                }
-            }
-            paf += "\n";
+            if (L->status[at] == 0) paf_line(at, (uint32_t)A->target[at], A->rev[at] != 0, L, G, "");
         }
         rattle_hip_alignment_free(L);
         rattle_hip_cigars_free(G);
         if (skipped) std::cerr << "\n" << skipped << "  reads over --paf-max-cells are left out of alignments.paf" << std::endl;
+    }
+    // --paf --secondary: one call per rank, every read on its slot of that rank, up to the first rank no read has; then one PAF line
+    // per (read, rank) that aligns, in file order and then by rank
+    void align_ranks() {
+        cli_timer t(want_cigar ? "library: align_cigars, every rank" : "library: align_pairs, every rank");
+        const uint32_t n = C->n, K = C->k;
+        std::vector<rattle_alignment *> L;
+        std::vector<rattle_cigars *> G;
+        std::vector<int32_t> target(std::max<uint32_t>(1, n));
+        std::vector<uint8_t> rev(std::max<uint32_t>(1, n));
+        for (uint32_t j = 0; j < K; ++j) {
+            bool any = false;
+            for (uint32_t r = 0; r < n; ++r) { target[r] = C->target[(size_t)r * K + j]; rev[r] = C->rev[(size_t)r * K + j]; any = any || C->count[r] > j; }
+            if (!any) break;
+            L.push_back(nullptr); G.push_back(nullptr);
+            align_on(target.data(), rev.data(), &L.back(), &G.back());
+        }
+        uint64_t skipped = 0;
+        for (uint32_t at = 0; at < n; ++at)
+            for (uint32_t j = 0; j < C->count[at] && j < L.size(); ++j) {
+                skipped += L[j]->status[at] == 2;
+                if (L[j]->status[at] != 0) continue;
+                paf_line(at, (uint32_t)C->target[(size_t)at * K + j], C->rev[(size_t)at * K + j] != 0, L[j], G[j],
+                         std::string(j == 0 ? "\ttp:A:P" : "\ttp:A:S") + "\trk:i:" + std::to_string(j));
+            }
+        for (size_t j = 0; j < L.size(); ++j) { rattle_hip_alignment_free(L[j]); rattle_hip_cigars_free(G[j]); }
+        if (skipped) std::cerr << "\n" << skipped << "  pairs over --paf-max-cells are left out of alignments.paf" << std::endl;
+    }
+    // --secondary: one line per filled slot, in file order of the reads, then by rank
+    void format_candidates() {
+        cand = "read\trank\ttarget\tstrand\tscore\tbases\thc_bases\tmin_len\tvariance\n";
+        for (uint32_t at = 0; at < C->n; ++at)
+            for (uint32_t j = 0; j < C->count[at]; ++j) {
+                const size_t s = (size_t)at * C->k + j;
+                cand += record_name(R.header[rid[at]]) + "\t" + std::to_string(j) + "\t" + record_name(X.header[C->target[s]]) + "\t" + (C->rev[s] ? "-" : "+") + "\t" +
+                        g17(C->score[s]) + "\t" + std::to_string(C->bases[s]) + "\t" + std::to_string(C->hc_bases[s]) + "\t" + std::to_string(C->min_len[s]) + "\t" +
+                        g17(C->variance[s]) + "\n";
+            }
+        rattle_hip_candidates_free(C);
+        C = nullptr;
     }
     // one line per read of -i, the reads that were not submitted included; then one line per transcript
     void format() {
@@ -921,6 +981,7 @@ struct assign_job {
         write_text(outdir + "/assignments.tsv", text);
         write_text(outdir + "/target_counts.tsv", counts);
         if (want_paf) write_text(outdir + "/alignments.paf", paf);
+        if (secondary) write_text(outdir + "/candidates.tsv", cand);
         team.close();
         std::cerr << "Done" << std::endl;
     }
@@ -931,7 +992,8 @@ int mode_assign(int argc, char **argv) {
     J.options(argc, argv);
     J.read_input();
     J.run();
-    if (J.want_paf) J.align();
+    if (J.want_paf) { if (J.secondary) J.align_ranks(); else J.align(); }
+    if (J.secondary) J.format_candidates();
     J.format();
     J.write();
     return EXIT_SUCCESS;
