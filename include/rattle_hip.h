@@ -331,7 +331,7 @@ void rattle_hip_cigars_free(rattle_cigars *c);
 
 /* ------------------------------------------------------------------------------------
  * align_pairs_scored, align_cigars_scored: the two calls above with AFFINE gaps and a scoring the caller chooses (the three-state forms
- * of kernels E and F, csrc/pair_align_affine.hip and csrc/pair_cigar_affine.hip).  The scoring is four positive magnitudes, spoa's
+ * of kernels E and F: the <true> instantiations in csrc/pair_align.hip and csrc/pair_cigar.hip).  The scoring is four positive magnitudes, spoa's
  * convention: match +match, mismatch -mismatch, the first gapped column of a gap -gap_open, every further one -gap_extend;
  *   1 <= match <= 64, 1 <= mismatch <= 64, 1 <= gap_extend <= gap_open <= 64
  * so {5, 4, 8, 6} is `correct`'s engine, {5, 4, 8, 8} the linear rule of align_pairs and {2, 4, 4, 2} minimap2's.  Gotoh's recurrence:

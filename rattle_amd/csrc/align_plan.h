@@ -9,6 +9,8 @@
 namespace rattle {
 
 constexpr uint32_t AL_ROWS = 64;                 // rows of a block of kernel E = lanes of a wavefront
+constexpr uint64_t AL_STRIP_BYTES = 16;          // a column of the hand-over strip: H's score and its three payload words
+constexpr uint64_t AL_AFFINE_STRIP_BYTES = 40;   // ... of the three-state form: H and U, a score and four payload words each
 
 struct align_plan {
     std::vector<uint8_t> status;                 // [n_reads] 1, 2, 3 as in rattle_alignment; 0: submitted, the device decides between 0 and 1

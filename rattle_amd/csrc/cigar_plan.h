@@ -35,7 +35,7 @@ struct cigar_plan {
 // A sub-chunk holds at most pair_chunk pairs and at most code_cap bytes of code records; one pair always fits, whatever it needs (a pair that
 // alone exceeds the cap runs alone: its allocation succeeds or the call ends with the library's out-of-memory error).
 // rec_bytes, strip_words: the bytes of one code record and the strip's words per column -- 16 and 1 for kernel F, 32 and 2 for its
-// three-state form (pair_cigar_affine.hip: four bits per cell, H and U in the strip).
+// three-state form (pair_cigar_kernel<true>: four bits per cell, H and U in the strip); pair_wave.h names both sets as a gap_form.
 inline void plan_cigar(const uint8_t *status, const uint32_t *rows, const uint32_t *cols, uint32_t n, uint32_t pair_chunk, uint64_t code_cap,
                        cigar_plan &P, uint64_t rec_bytes = CG_REC_BYTES, uint64_t strip_words = 1) {
     P.sub.clear(); P.recs.clear(); P.strip.clear(); P.ops.clear(); P.first.clear();

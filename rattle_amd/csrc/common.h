@@ -547,12 +547,9 @@ struct cigar_run {                      // one call of rattle_hip_align_cigars: 
     hbuf<uint64_t> h_off;
 };
 uint64_t cigar_code_cap();              // 4 GiB, or what RATTLE_CIGAR_CODE_BYTES says
-// scoring == nullptr: kernel F (linear, id 7); else the three-state kernel (pair_cigar_affine.hip, id 9): 32-byte records, 2 strip words per column
+// scoring == nullptr: the linear form (GAP_LINEAR of pair_wave.h, id 7); else the affine form with that scoring (GAP_AFFINE, id 9)
 int pair_cigar_chunk(rattle_ctx *ctx, const uint8_t *d_q, const uint8_t *d_t, const cigar_in *in, uint32_t n, uint32_t pair_chunk, cigar_run &R,
                      const rattle_align_scoring *scoring = nullptr);
-// pair_cigar_affine.hip : the launch of the three-state kernel F; codes holds two uint4 per record, strips two words per column
-void pair_cigar_affine_launch(hipStream_t stream, const cigar_pair *pairs, uint32_t n_pairs, const uint8_t *d_q, const uint8_t *d_t, uint4 *codes,
-                              int32_t *strips, uint32_t *ops, uint32_t *counts, const rattle_align_scoring &S);
 // pair_align.hip : kernel E, the local alignment of every submitted read on its target; fills every array of A (arguments checked by the caller).
 // With `cigars`, every chunk goes on to kernel F before its sequences leave the device (cigars->count sized n_reads by the caller).
 // scoring == nullptr: kernels E and F (linear, ids 6 and 7); else their three-state forms with that scoring (ids 8 and 9).
@@ -563,11 +560,7 @@ struct align_pair {                     // one submitted pair: where its sequenc
 int align_pairs_run(rattle_ctx *ctx, const uint8_t *tseq, const uint64_t *toff, uint32_t n_targets, const uint8_t *rseq, const uint64_t *roff,
                     uint32_t n_reads, const int32_t *target, const uint8_t *rev, const rattle_align_params *P, rattle_alignment *A,
                     cigar_run *cigars = nullptr, const rattle_align_scoring *scoring = nullptr);
-// pair_align_affine.hip : the launch of the three-state kernel E; strips holds 40-byte records (five uint2)
 constexpr uint32_t AL_REC_WORDS = 10;   // a pair's record on the device: status, score, q_start, q_end, t_start, t_end, matches, mismatches, q_gap, t_gap
-constexpr uint64_t AL_AFFINE_STRIP_BYTES = 40;
-void pair_align_affine_launch(hipStream_t stream, const align_pair *pairs, uint32_t n_pairs, const uint8_t *d_q, const uint8_t *d_t, uint2 *strips,
-                              int32_t *recs, const rattle_align_scoring &S);
 
 // correct_driver.hip
 int debug_post_msa(rattle_ctx *ctx, const rattle_correct_params *P, int mode, const rattle_debug_msa *in, rattle_debug_post **out);

@@ -1,96 +1,163 @@
-// Kernel E: the local alignment of every placed read on its one transcript (include/rattle_hip.h, "align_pairs"; DESIGN.md, "Kernel E").
+// Kernel E: the local alignment of every placed read on its one transcript (include/rattle_hip.h, "align_pairs" and "align_pairs_scored";
+// DESIGN.md, "Kernel E" and "Kernels E and F with three states").  One templated kernel in two forms.
 //
-// Smith-Waterman with LINEAR gaps (match +5, mismatch -4, gap -8 per gapped column) over the letters A, C, G, T = U:
+// pair_align_kernel<false>: Smith-Waterman with LINEAR gaps (match +5, mismatch -4, gap -8 per gapped column) over the letters A, C, G, T = U:
 //   H[i][j] = max(0, H[i-1][j-1] + s(q_i, t_j), H[i-1][j] - 8, H[i][j-1] - 8),  H[0][*] = H[*][0] = 0,  i over the read, j over the transcript
-// A cell with H == 0 begins a new alignment; predecessors that tie are taken diagonal, then up, then left; the end cell is the largest H, ties
-// to the smallest i, then the smallest j.  No traceback: every cell carries (start_i, start_j, matches) of the path the rule picks, taken from
-// the predecessor it picks, and the other counts follow from the score and the two spans (where lane 0 writes the record).
+// pair_align_kernel<true>: Gotoh's recurrence with AFFINE gaps, the four magnitudes m, x, o, e as a kernel argument (scalars;
+// tests/align_affine_ref.py is the contract):
+//   U[i][j] = max(H[i-1][j] - o, U[i-1][j] - e)      L[i][j] = max(H[i][j-1] - o, L[i][j-1] - e)
+//   H[i][j] = max(0, H[i-1][j-1] + s(q_i, t_j), U[i][j], L[i][j])      H[0][*] = H[*][0] = 0,  U[0][*] = L[*][0] = -inf
+// A cell with H == 0 begins a new alignment; in H ties go diagonal, then up (U), then left (L); in U and in L open wins a tie with extend;
+// the end cell is the largest H, ties to the smallest i, then the smallest j.  No traceback: every state of a cell carries (start_i,
+// start_j, matches, mismatches) of the path the rule picks for it -- a gap step copies the payload of the state it comes from, a diagonal
+// step out of a zero cell starts at the cell's own coordinates -- and the two gap counts follow from the spans (where lane 0 writes the
+// record).  The linear form is the same body with both gap states opened from H alone (o = e = 8 makes U = H[i-1][j] - 8 exactly), so U
+// and L are never kept or carried; it never reads the mismatch count either (that chain is dead code) and takes X from the score and the
+// two spans.
 //
-// Shape: one wavefront per pair, the skewed form.  The read goes through in blocks of 64 rows, lane l owning row 64 b + l.  At step s lane l
-// computes column s - l: `left` is the lane's own previous cell, `up` is lane l - 1's previous cell and `diag` the one before that, both by the
-// DPP wave_shr:1, and the transcript's letter slides down the lanes the same way.  Lane 0's `up` -- the last row of the block before -- comes
-// from the pair's hand-over strip in device memory, 16 bytes (score + payload) per column: lane 63 writes it with one 16-byte vector store per
-// step, and it is read back 64 columns at a time, one record per lane and one refill ahead of its use, so no step waits on a load; the record
-// of column s then reaches lane 0 by v_readlane.  The strip is updated in place: column c is read one refill before step 64 floor(c / 64) and
-// written at step c + 63 of the same block, after the load's data has been consumed.  A lane keeps its best cell with a strict `>` over its rows in order (smallest i, then smallest j, per lane); the
-// lanes are reduced once, at the end, by (score desc, i asc, j asc).  No wavefront waits for another; every load and store lies inside the
-// pair's own two sequences, its own strip and its own record.
+// Shape: one wavefront per pair, four pairs per block, no LDS, the skewed form.  The read goes through in blocks of 64 rows, lane l owning
+// row 64 b + l.  At step s lane l computes column s - l: `left` (H, and L with three states) is the lane's own previous cell, `up` (H,
+// and U) is lane l - 1's previous cell and `diag` the H before that, both by the DPP wave_shr:1 -- five moves per step in the linear
+// form, eleven in the affine -- and the transcript's letter slides down the lanes the same way.  Lane 0's `up` -- the last row of the
+// block before -- comes from the pair's hand-over strip in device memory.  Linear: 16 bytes per column (H's score and start_i, start_j,
+// matches), written by lane 63 with one 16-byte vector store per step.  Affine: 40 bytes per column (five uint2: H, its payload, U, its
+// payload), five 8-byte stores.  The strip is read back 64 columns at a time, one record per lane and one refill ahead of its use, so no
+// step waits on a load; the record of column s then reaches lane 0 by v_readlane.  The strip is updated in place: column c is read one
+// refill before step 64 floor(c / 64) and written at step c + 63 of the same block, after the load's data has been consumed.  On the
+// first block lane 0's U is PW_NEG, and no U or L that is computed lies below -64 once an H has entered it.  Lanes whose cell is off the
+// matrix keep their state frozen.  A lane keeps its best cell with a strict `>` over its rows in order (smallest i, then smallest j, per
+// lane); the lanes are reduced once, at the end, by (score desc, i asc, j asc).  No wavefront waits for another; every load and store
+// lies inside the pair's own two sequences, its own strip and its own record.
 #include <algorithm>
 #include <cstring>
 
-#include "align_plan.h"
 #include "common.h"
+#include "pair_wave.h"
 
 namespace rattle {
 
 namespace {
 
-constexpr int32_t AL_MATCH = 5, AL_MISMATCH = -4, AL_GAP = -8;
+// a state of a cell: its score and the payload of its path
+struct al_cell {
+    int32_t s, i, j, m, x;
+};
 
-// value of lane - 1 (lane 0 receives `fill`): the helper of poa.hip
-__device__ __forceinline__ int32_t al_shr1(int32_t v, int32_t fill) {
-    return __builtin_amdgcn_update_dpp(fill, v, 0x138 /*wave_shr:1*/, 0xF, 0xF, false);
+__device__ __forceinline__ al_cell al_pick(bool first, const al_cell &a, const al_cell &b) {
+    al_cell r;
+    r.s = first ? a.s : b.s; r.i = first ? a.i : b.i; r.j = first ? a.j : b.j; r.m = first ? a.m : b.m; r.x = first ? a.x : b.x;
+    return r;
 }
 
-// A 0, C 1, G 2, T and U 3 (the complement of code c is 3 - c); the host has refused every other byte
-__device__ __forceinline__ int32_t al_code(uint32_t b) { return b == 'A' ? 0 : b == 'C' ? 1 : b == 'G' ? 2 : 3; }
+// A column of the strip in registers, as words: H {s, i, j, m} and with AFFINE H.x, U {s, i, j, m, x}.  Beyond the strip: H 0, U minus infinity.
+template <bool AFFINE>
+struct al_strip {
+    static constexpr uint32_t WORDS = AFFINE ? AL_AFFINE_STRIP_BYTES / 4 : AL_STRIP_BYTES / 4;
+    uint32_t w[WORDS];
+    __device__ __forceinline__ void clear() {
+#pragma unroll
+        for (uint32_t k = 0; k < WORDS; ++k) w[k] = 0;
+        if constexpr (AFFINE) w[5] = (uint32_t)PW_NEG;
+    }
+    __device__ __forceinline__ void load(const uint32_t *col) {      // one uint4, or five uint2
+        if constexpr (AFFINE) {
+#pragma unroll
+            for (uint32_t k = 0; k < WORDS / 2; ++k) { const uint2 v = reinterpret_cast<const uint2 *>(col)[k]; w[2 * k] = v.x; w[2 * k + 1] = v.y; }
+        } else { const uint4 v = *reinterpret_cast<const uint4 *>(col); w[0] = v.x; w[1] = v.y; w[2] = v.z; w[3] = v.w; }
+    }
+    __device__ __forceinline__ void store(uint32_t *col) const {
+        if constexpr (AFFINE) {
+#pragma unroll
+            for (uint32_t k = 0; k < WORDS / 2; ++k) reinterpret_cast<uint2 *>(col)[k] = make_uint2(w[2 * k], w[2 * k + 1]);
+        } else *reinterpret_cast<uint4 *>(col) = make_uint4(w[0], w[1], w[2], w[3]);
+    }
+    __device__ __forceinline__ int32_t lane(uint32_t word, uint32_t k) const { return __builtin_amdgcn_readlane((int32_t)w[word], k); }
+};
 
+template <bool AFFINE>
 __global__ __launch_bounds__(256) void pair_align_kernel(const align_pair *__restrict__ pairs, uint32_t n_pairs, const uint8_t *__restrict__ qseq,
-                                                         const uint8_t *__restrict__ tseq, uint4 *__restrict__ strips, int32_t *__restrict__ recs) {
+                                                         const uint8_t *__restrict__ tseq, uint32_t *__restrict__ strips, int32_t *__restrict__ recs,
+                                                         const rattle_align_scoring scoring) {
+    constexpr uint32_t SW = al_strip<AFFINE>::WORDS;
+    const rattle_align_scoring sc = AFFINE ? scoring : PW_LINEAR;    // the linear form's scores are compile-time constants
+    const int32_t sm = (int32_t)sc.match, sx = (int32_t)sc.mismatch, so = (int32_t)sc.gap_open, se = (int32_t)sc.gap_extend;
     const uint32_t lane = threadIdx.x & 63u;
     const uint32_t p = blockIdx.x * 4u + (threadIdx.x >> 6);
     if (p >= n_pairs) return;                                        // wave-uniform
     const align_pair P = pairs[p];
     const uint32_t lq = P.lq, lt = P.lt;
     const uint8_t *q = qseq + P.q, *t = tseq + P.t;
-    uint4 *strip = strips + P.strip;
+    uint32_t *strip = strips + P.strip * SW;
 
     int32_t bH = 0;                                                  // the lane's best cell: score, end (i, j) as DP indices, payload
-    uint32_t bi = 0, bj = 0, bsi = 0, bsj = 0, bm = 0;
+    uint32_t bi = 0, bj = 0, bsi = 0, bsj = 0, bm = 0, bx = 0;
 
     for (uint32_t r0 = 0; r0 < lq; r0 += AL_ROWS) {
         const uint32_t r = r0 + lane;                                // the lane's row: read base r (of the strand aligned)
         const bool row = r < lq;
         int32_t ql = 4;                                              // (matches nothing)
-        if (row) { const uint32_t c = al_code(q[P.rev ? lq - 1 - r : r]); ql = (int32_t)(P.rev ? 3 - c : c); }
+        if (row) { const uint32_t c = pw_code(q[P.rev ? lq - 1 - r : r]); ql = (int32_t)(P.rev ? 3 - c : c); }
         const bool from_strip = r0 > 0, to_strip = r0 + AL_ROWS < lq;
         const uint32_t n_steps = lt + min(AL_ROWS, lq - r0) - 1;       // the block's last row computes its last column at the last step
-        // the lane's previous cell (left), lane - 1's previous cell as received one step ago (diag), the sliding letter
-        int32_t cH = 0, cI = 0, cJ = 0, cM = 0, dH = 0, dI = 0, dJ = 0, dM = 0, tl = 4;
+        // the lane's previous cell in its states (H and U go down the lanes, L stays), lane - 1's previous H as received one step ago
+        // (diag), the sliding letter
+        al_cell cH = {0, 0, 0, 0, 0}, cU = {PW_NEG, 0, 0, 0, 0}, cL = {PW_NEG, 0, 0, 0, 0}, dH = {0, 0, 0, 0, 0};
+        int32_t tl = 4;
         // refill in flight: the transcript's letters and the strip's records of columns [S + 64, S + 128)
         int32_t nT = 4;
-        uint4 nR = make_uint4(0, 0, 0, 0);
-        if (lane < lt) { nT = al_code(t[lane]); if (from_strip) nR = strip[lane]; }
+        al_strip<AFFINE> nR;
+        nR.clear();
+        if (lane < lt) { nT = pw_code(t[lane]); if (from_strip) nR.load(strip + (uint64_t)lane * SW); }
         for (uint32_t S = 0; S < n_steps; S += 64) {
             const int32_t bT = nT;
-            const uint4 bR = nR;
-            nT = 4; nR = make_uint4(0, 0, 0, 0);
-            if (S + 64 + lane < lt) { nT = al_code(t[S + 64 + lane]); if (from_strip) nR = strip[S + 64 + lane]; }
+            const al_strip<AFFINE> bR = nR;
+            nT = 4; nR.clear();
+            if (S + 64 + lane < lt) { nT = pw_code(t[S + 64 + lane]); if (from_strip) nR.load(strip + (uint64_t)(S + 64 + lane) * SW); }
             const uint32_t k_end = min(64u, n_steps - S);
             for (uint32_t k = 0; k < k_end; ++k) {
                 const uint32_t s = S + k;
-                // lane 0's up cell and letter: column s of the buffers (zeros on the first block and beyond the transcript's end)
+                // lane 0's up cell and letter: column s of the buffers (H 0 and U minus infinity on the first block and beyond the transcript's end)
                 const int32_t fT = __builtin_amdgcn_readlane(bT, k);
-                const int32_t fH = __builtin_amdgcn_readlane((int32_t)bR.x, k), fI = __builtin_amdgcn_readlane((int32_t)bR.y, k);
-                const int32_t fJ = __builtin_amdgcn_readlane((int32_t)bR.z, k), fM = __builtin_amdgcn_readlane((int32_t)bR.w, k);
-                const int32_t uH = al_shr1(cH, fH), uI = al_shr1(cI, fI), uJ = al_shr1(cJ, fJ), uM = al_shr1(cM, fM);
-                tl = al_shr1(tl, fT);
+                al_cell uH, uU;
+                uH.s = pw_shr1(cH.s, bR.lane(0, k)); uH.i = pw_shr1(cH.i, bR.lane(1, k));
+                uH.j = pw_shr1(cH.j, bR.lane(2, k)); uH.m = pw_shr1(cH.m, bR.lane(3, k));
+                if constexpr (AFFINE) {
+                    uH.x = pw_shr1(cH.x, bR.lane(4, k));
+                    uU.s = pw_shr1(cU.s, bR.lane(5, k)); uU.i = pw_shr1(cU.i, bR.lane(6, k)); uU.j = pw_shr1(cU.j, bR.lane(7, k));
+                    uU.m = pw_shr1(cU.m, bR.lane(8, k)); uU.x = pw_shr1(cU.x, bR.lane(9, k));
+                } else uH.x = 0;
+                tl = pw_shr1(tl, fT);
                 const uint32_t c = s - lane;                         // the lane's column (wraps below 0: fails the test)
                 const bool on = row && c < lt;
                 const bool eq = ql == tl;
-                const int32_t d = dH + (eq ? AL_MATCH : AL_MISMATCH), u = uH + AL_GAP, l = cH + AL_GAP;
-                const int32_t h = max(max(d, 0), max(u, l));
-                int32_t nI, nJ, nM;
+                // the two gap states: open wins a tie with extend, and the payload is that of the state the step comes from (linear: H alone)
+                al_cell nU = uH, nL = cH;
+                if constexpr (AFFINE) {
+                    nU = al_pick(uH.s - so >= uU.s - se, uH, uU); nL = al_pick(cH.s - so >= cL.s - se, cH, cL);
+                    nU.s = max(uH.s - so, uU.s - se); nL.s = max(cH.s - so, cL.s - se);
+                } else { nU.s = uH.s - so; nL.s = cH.s - so; }
+                const int32_t d = dH.s + (eq ? sm : -sx), u = nU.s, l = nL.s;
+                al_cell nH;
                 if (d >= u && d >= l) {                              // diagonal first; a zero predecessor begins the alignment at this cell
-                    const bool fresh = dH == 0;
-                    nI = fresh ? (int32_t)r : dI; nJ = fresh ? (int32_t)c : dJ; nM = (fresh ? 0 : dM) + (eq ? 1 : 0);
-                } else if (u >= l) { nI = uI; nJ = uJ; nM = uM; }    // then up: a read base against a gap
-                else { nI = cI; nJ = cJ; nM = cM; }                  // then left: a transcript base against a gap
-                dH = uH; dI = uI; dJ = uJ; dM = uM;
+                    const bool fresh = dH.s == 0;
+                    nH.i = fresh ? (int32_t)r : dH.i; nH.j = fresh ? (int32_t)c : dH.j;
+                    nH.m = (fresh ? 0 : dH.m) + (eq ? 1 : 0); nH.x = (fresh ? 0 : dH.x) + (eq ? 0 : 1);
+                } else nH = al_pick(u >= l, nU, nL);                 // then up: a read base against a gap; then left: a transcript base against a gap
+                nH.s = max(max(d, 0), max(u, l));
+                dH = uH;
                 if (on) {
-                    cH = h; cI = nI; cJ = nJ; cM = nM;               // (payload of a zero cell is never read: see `fresh`, and u, l < 0 there)
-                    if (h > bH) { bH = h; bi = r + 1; bj = c + 1; bsi = (uint32_t)nI; bsj = (uint32_t)nJ; bm = (uint32_t)nM; }
-                    if (to_strip && lane == 63) strip[c] = make_uint4((uint32_t)h, (uint32_t)nI, (uint32_t)nJ, (uint32_t)nM);
+                    cH = nH;                                         // (payload of a zero cell is never read: see `fresh`, and a gap state opened there stays < 0)
+                    if constexpr (AFFINE) { cU = nU; cL = nL; }
+                    if (nH.s > bH) { bH = nH.s; bi = r + 1; bj = c + 1; bsi = (uint32_t)nH.i; bsj = (uint32_t)nH.j; bm = (uint32_t)nH.m; bx = (uint32_t)nH.x; }
+                    if (to_strip && lane == 63) {                    // c < lt: inside the pair's strip
+                        al_strip<AFFINE> o;
+                        o.w[0] = (uint32_t)nH.s; o.w[1] = (uint32_t)nH.i; o.w[2] = (uint32_t)nH.j; o.w[3] = (uint32_t)nH.m;
+                        if constexpr (AFFINE) {
+                            o.w[4] = (uint32_t)nH.x;
+                            o.w[5] = (uint32_t)nU.s; o.w[6] = (uint32_t)nU.i; o.w[7] = (uint32_t)nU.j; o.w[8] = (uint32_t)nU.m; o.w[9] = (uint32_t)nU.x;
+                        }
+                        o.store(strip + (uint64_t)c * SW);
+                    }
                 }
             }
         }
@@ -100,15 +167,16 @@ __global__ __launch_bounds__(256) void pair_align_kernel(const align_pair *__res
     // the best of the 64 lanes: score desc, i asc, j asc (a lane without a positive cell loses to every other)
     for (int off = 32; off > 0; off >>= 1) {
         const int32_t oH = __shfl_xor(bH, off);
-        const uint32_t oi = __shfl_xor(bi, off), oj = __shfl_xor(bj, off), osi = __shfl_xor(bsi, off), osj = __shfl_xor(bsj, off), om = __shfl_xor(bm, off);
-        if (oH > bH || (oH == bH && (oi < bi || (oi == bi && oj < bj)))) { bH = oH; bi = oi; bj = oj; bsi = osi; bsj = osj; bm = om; }
+        const uint32_t oi = __shfl_xor(bi, off), oj = __shfl_xor(bj, off), osi = __shfl_xor(bsi, off), osj = __shfl_xor(bsj, off);
+        const uint32_t om = __shfl_xor(bm, off), ox = __shfl_xor(bx, off);
+        if (oH > bH || (oH == bH && (oi < bi || (oi == bi && oj < bj)))) { bH = oH; bi = oi; bj = oj; bsi = osi; bsj = osj; bm = om; bx = ox; }
     }
     if (lane == 0) {
         int32_t *R = recs + (size_t)p * AL_REC_WORDS;
         if (bH <= 0) { for (uint32_t f = 0; f < AL_REC_WORDS; ++f) R[f] = f == 0 ? 1 : 0; return; }
-        // spans sq, st; S = 5 M - 4 X - 8 (q_gap + t_gap), sq = M + X + q_gap, st = M + X + t_gap  =>  12 X = 8 (sq + st) - 21 M + S
-        const uint32_t sq = bi - bsi, st = bj - bsj;
-        const uint32_t X = (uint32_t)((8ll * ((long long)sq + st) - 21ll * bm + bH) / 12);
+        const uint32_t sq = bi - bsi, st = bj - bsj;                 // the spans: sq = M + X + q_gap, st = M + X + t_gap
+        // linear: S = 5 M - 4 X - 8 (q_gap + t_gap) with the spans  =>  12 X = 8 (sq + st) - 21 M + S
+        const uint32_t X = AFFINE ? bx : (uint32_t)((8ll * ((long long)sq + st) - 21ll * bm + bH) / 12);
         R[0] = 0; R[1] = bH;
         R[2] = (int32_t)(P.rev ? lq - bi : bsi); R[3] = (int32_t)(P.rev ? lq - bsi : bi);      // on the read as given
         R[4] = (int32_t)bsj; R[5] = (int32_t)bj;
@@ -122,14 +190,14 @@ __global__ __launch_bounds__(256) void pair_align_kernel(const align_pair *__res
 // have been checked (abi.hip).  Fills every array of A.  The plan -- statuses settled without the device, strip records, chunks -- is
 // align_plan.h's; the strip buffer is sized from the lengths of the chunk.  With `cigars` (rattle_hip_align_cigars) every chunk's records go on
 // to kernel F (pair_cigar.hip) while the chunk's sequences are on the device; A is filled exactly as without.  With `scoring`
-// (rattle_hip_align_*_scored) the launches are those of the three-state kernels (pair_align_affine.hip, pair_cigar_affine.hip); the plan, the
-// uploads and the records are the same, the strip's records are 40 bytes.
+// (rattle_hip_align_*_scored) the form is GAP_AFFINE, the launches are those of the <true> kernels; the plan, the uploads and the records are the
+// same, the strip's records are 40 bytes.
 int align_pairs_run(rattle_ctx *ctx, const uint8_t *tseq, const uint64_t *toff, uint32_t nt, const uint8_t *rseq, const uint64_t *roff, uint32_t nr,
                     const int32_t *target, const uint8_t *rev, const rattle_align_params *AP, rattle_alignment *A, cigar_run *cigars, const rattle_align_scoring *scoring) {
     phase_timer T_all("align_pairs: total");
+    const gap_form &F = scoring ? GAP_AFFINE : GAP_LINEAR;
     align_plan plan;
-    plan_align(toff, roff, nr, target, AP->max_cells, AP->pair_chunk ? AP->pair_chunk : 32768u,
-               scoring ? (1ull << 30) / AL_AFFINE_STRIP_BYTES : 1ull << 26 /* 1 GiB of records */, plan);
+    plan_align(toff, roff, nr, target, AP->max_cells, AP->pair_chunk ? AP->pair_chunk : 32768u, (1ull << 30) / F.strip_bytes /* 1 GiB of records */, plan);
     for (uint32_t r = 0; r < nr; ++r) A->status[r] = plan.status[r];
     if (plan.sub.empty()) return 0;
     const std::vector<uint32_t> &sub = plan.sub, &first = plan.first;
@@ -138,7 +206,7 @@ int align_pairs_run(rattle_ctx *ctx, const uint8_t *tseq, const uint64_t *toff, 
     const uint64_t t0 = toff[0], tbytes = toff[nt] - t0;
     dbuf<uint8_t> d_t, d_q;
     dbuf<align_pair> d_pairs;
-    dbuf<uint4> d_strip;
+    dbuf<uint32_t> d_strip;
     dbuf<int32_t> d_rec;
     hbuf<align_pair> h_pairs;
     hbuf<int32_t> h_rec;
@@ -161,15 +229,15 @@ int align_pairs_run(rattle_ctx *ctx, const uint8_t *tseq, const uint64_t *toff, 
         }
         RT_TRY(d_q.reserve(qbytes));
         RT_TRY(d_pairs.reserve(n));
-        RT_TRY(d_strip.reserve(std::max<uint64_t>(1, scoring ? (strip_recs * (AL_AFFINE_STRIP_BYTES / 8) + 1) / 2 : strip_recs)));      // (uint4s)
+        RT_TRY(d_strip.reserve(std::max<uint64_t>(1, strip_recs * (F.strip_bytes / 4))));      // (words)
         RT_TRY(d_rec.reserve((size_t)n * AL_REC_WORDS));
         RT_TRY(h_rec.reserve((size_t)n * AL_REC_WORDS));
         RT_HIP(hipMemcpyAsync(d_q.p, rseq + q0, qbytes, hipMemcpyHostToDevice, ctx->stream));
         RT_HIP(hipMemcpyAsync(d_pairs.p, h_pairs.p, (size_t)n * sizeof(align_pair), hipMemcpyHostToDevice, ctx->stream));
         {
-            ktimer kt(ctx, scoring ? K_ALIGN_AFFINE : K_ALIGN, seq_bytes + (uint64_t)n * AL_REC_WORDS * 4);
-            if (scoring) pair_align_affine_launch(ctx->stream, d_pairs.p, n, d_q.p, d_t.p, (uint2 *)d_strip.p, d_rec.p, *scoring);
-            else hipLaunchKernelGGL(pair_align_kernel, dim3((n + 3) / 4), dim3(256), 0, ctx->stream, d_pairs.p, n, d_q.p, d_t.p, d_strip.p, d_rec.p);
+            ktimer kt(ctx, F.k_align, seq_bytes + (uint64_t)n * AL_REC_WORDS * 4);
+            const auto kernel = scoring ? pair_align_kernel<true> : pair_align_kernel<false>;
+            hipLaunchKernelGGL(kernel, dim3((n + 3) / 4), dim3(256), 0, ctx->stream, d_pairs.p, n, d_q.p, d_t.p, d_strip.p, d_rec.p, scoring ? *scoring : PW_LINEAR);
             RT_HIP(hipGetLastError());
         }
         RT_HIP(hipMemcpyAsync(h_rec.p, d_rec.p, (size_t)n * AL_REC_WORDS * 4, hipMemcpyDeviceToHost, ctx->stream));

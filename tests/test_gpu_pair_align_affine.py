@@ -1,4 +1,4 @@
-"""The three-state kernel E (csrc/pair_align_affine.hip) against the contract in plain Python (tests/align_affine_ref.py, fill + walk):
+"""The three-state kernel E (pair_align_kernel<true>, csrc/pair_align.hip) against the contract in plain Python (tests/align_affine_ref.py, fill + walk):
 every field of every pair, exactly.  Every case of align_ref, cigar_ref and align_affine_ref under 5,4,8,8 and 5,4,8,6, the edge and the
 new cases -- long gaps whose U state crosses block edges through the strip, gaps that end and begin on row 64, a D run across two
 refills, open / extend ties -- under 2,4,4,2 and 5,4,12,1 as well; 5,4,8,8 against kernel E itself, field for field; statuses and

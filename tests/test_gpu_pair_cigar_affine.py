@@ -1,4 +1,4 @@
-"""The three-state kernel F (csrc/pair_cigar_affine.hip) against the contract in plain Python (tests/align_affine_ref.py): the ops of
+"""The three-state kernel F (pair_cigar_kernel<true>, csrc/pair_cigar.hip) against the contract in plain Python (tests/align_affine_ref.py): the ops of
 every pair, exactly -- the reference's walk over the same matrices -- and beside them the records, field for field.  The cases and
 scorings of tests/test_gpu_pair_align_affine.py; the four op sums are the record's four counts; 5,4,8,8 against kernels E and F
 themselves; max_cells, empty input; the pair chunk, the cap on code bytes (32-byte records) and the input order change nothing; kernel id
