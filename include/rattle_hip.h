@@ -362,6 +362,48 @@ int  rattle_hip_align_cigars_scored(rattle_ctx *ctx, const uint8_t *target_conca
                                     rattle_cigars **cigars);
 
 /* ------------------------------------------------------------------------------------
+ * align_pairs_mode, align_cigars_mode (ABI 4): the four calls above with an alignment MODE.  scoring == NULL is the linear form (5, 4, 8, 8
+ * on the two-state kernels), any other the affine form.  RATTLE_ALIGN_LOCAL returns the bytes of the call it stands for (align_pairs /
+ * align_pairs_scored, align_cigars / align_cigars_scored).  RATTLE_ALIGN_READ aligns every read END TO END and leaves the target's ends
+ * free (semi-global): nothing of the read is clipped, so an overhang or a foreign exon shows as an I run or as X columns at the end of
+ * the line, and the scores of a read on two targets are scores of the same thing.  The <*, true> instantiations of kernels E and F.
+ * With i over the read (reverse-complemented first where rev == 1), j over the target and (m, x, o, e) the scoring:
+ *   H[0][j] = 0 for j = 0..Lt          U[0][*] = -inf        (the alignment may begin at any target position)
+ *   H[i][0] = U[i][0] = -(o + (i-1) e) L[*][0] = -inf        (read bases before the target's first base: a gap)
+ *   U[i][j] = max(H[i-1][j] - o, U[i-1][j] - e)
+ *   L[i][j] = max(H[i][j-1] - o, L[i][j-1] - e)
+ *   H[i][j] = max(H[i-1][j-1] + s(q_i, t_j), U[i][j], L[i][j])           -- no zero floor: a cell with H == 0 is an ordinary cell
+ * Ties as in the local mode: in H diagonal, then U, then L; in U and in L open wins a tie with extend.  The end cell is the largest
+ * H[Lq][j] over j = 1..Lt, ties to the smallest j.  The path goes back to row 0 and ends in (0, t_start); row 0 has no left moves, and a
+ * path that reaches column 0 goes straight up, the rows left being one I run.  So an alignment may begin and end with an I run, never
+ * with a D run.  Per read:
+ *   status      0 for every submitted pair of two non-empty sequences; 1 (a sequence is empty), 2 and 3 as in align_pairs
+ *   score       H of the end cell: may be zero or negative
+ *   q_start = 0 and q_end = Lq, on either strand;  t_start, t_end from the path, t_end - t_start may be 0 (the whole read one I run)
+ *   matches, mismatches, q_gap, t_gap as in align_pairs; in the linear form mismatches = (8 (Lq + st) - 21 matches + score) / 12 holds
+ * CIGAR: the same op set, no clipping op; '=' + 'X' + 'I' = Lq and '=' + 'X' + 'D' = t_end - t_start.  Kernel F works on the rectangle
+ * (0, Lq] x (t_start, t_end] with this mode's borders (top row H' = 0, U' = L' = -inf; left column H' = U' = -(o + (i-1) e), L' = -inf),
+ * which reproduces the path (DESIGN.md has the lemma, tests/test_align_ends_ref.py checks it).  A pair with t_end == t_start does not go
+ * to kernel F: the host writes its one op, Lq << 4 | I, and it does not count in alg_bytes.
+ * rattle_hip_kernel_stats: the launches count under the ids of their gap form (6 and 7, 8 and 9), alg_bytes by the same formulas.
+ * Errors: those of the call the scoring selects, in their order; then, still before the device is looked at, RATTLE_ERR_ARG for a mode
+ * that is neither of the two, and in read mode for a submitted pair with gap_open + gap_extend * (Lq - 1) >= 2^29 (the kernels' minus
+ * infinity, -2^30, has to stay below every score).
+ */
+#define RATTLE_ALIGN_LOCAL 0
+#define RATTLE_ALIGN_READ  1
+int  rattle_hip_align_pairs_mode(rattle_ctx *ctx, const uint8_t *target_concat, const uint64_t *target_offsets, uint32_t n_targets,
+                                 const uint8_t *read_concat, const uint64_t *read_offsets, uint32_t n_reads,
+                                 const int32_t *target_of_read /* -1: not submitted */, const uint8_t *rev,
+                                 const rattle_align_params *params, const rattle_align_scoring *scoring /* NULL: the linear form */, int mode,
+                                 rattle_alignment **out);
+int  rattle_hip_align_cigars_mode(rattle_ctx *ctx, const uint8_t *target_concat, const uint64_t *target_offsets, uint32_t n_targets,
+                                  const uint8_t *read_concat, const uint64_t *read_offsets, uint32_t n_reads,
+                                  const int32_t *target_of_read /* -1: not submitted */, const uint8_t *rev,
+                                  const rattle_align_params *params, const rattle_align_scoring *scoring /* NULL: the linear form */, int mode,
+                                  rattle_alignment **out, rattle_cigars **cigars);
+
+/* ------------------------------------------------------------------------------------
  * a15  spoa engine + graph as called from /root/reference/correct.cpp:395-405,428-436,520-532
  * (createAlignmentEngine(kSW,5,-4,-8,-6); align + add_alignment per sequence;
  * generate_multiple_sequence_alignment).  Packs are independent; pack p holds sequences

@@ -238,6 +238,10 @@ SIGNATURES = {
                                                 _P(AlignScoring), _P(_P(Alignment))]),
     "rattle_hip_align_cigars_scored": (C.c_int, [C.c_void_p, _u8p, _u64p, C.c_uint32, _u8p, _u64p, C.c_uint32, _i32p, _u8p, _P(AlignParams),
                                                  _P(AlignScoring), _P(_P(Alignment)), _P(_P(Cigars))]),
+    "rattle_hip_align_pairs_mode": (C.c_int, [C.c_void_p, _u8p, _u64p, C.c_uint32, _u8p, _u64p, C.c_uint32, _i32p, _u8p, _P(AlignParams),
+                                              _P(AlignScoring), C.c_int, _P(_P(Alignment))]),
+    "rattle_hip_align_cigars_mode": (C.c_int, [C.c_void_p, _u8p, _u64p, C.c_uint32, _u8p, _u64p, C.c_uint32, _i32p, _u8p, _P(AlignParams),
+                                               _P(AlignScoring), C.c_int, _P(_P(Alignment)), _P(_P(Cigars))]),
     "rattle_hip_poa_msa": (C.c_int, [C.c_void_p, _u8p, _u64p, C.c_uint32, _u32p, C.c_uint32, _P(_P(MsaSet))]),
     "rattle_hip_msa_set_free": (None, [_P(MsaSet)]),
     "rattle_hip_correct_reads": (C.c_int, [C.c_void_p, _u8p, _u8p, _u64p, C.c_uint32, C.c_uint32, _u32p, _i32p, _u8p,

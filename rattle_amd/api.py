@@ -20,6 +20,7 @@ from ._lib import ClusterParams, ClusterSet, Correction, CorrectParams, MsaSet, 
 
 K_KMER, K_FILTER, K_SCORE, K_POA, K_POST, K_ASSIGN, K_ALIGN, K_CIGAR = 0, 1, 2, 3, 4, 5, 6, 7
 K_ALIGN_AFFINE, K_CIGAR_AFFINE = 8, 9          # the three-state forms of kernels E and F (align_pairs / align_cigars with a scoring)
+ALIGN_MODES = {"local": 0, "read": 1}         # RATTLE_ALIGN_LOCAL, RATTLE_ALIGN_READ
 
 
 def _ptr(a: np.ndarray, t):
@@ -666,21 +667,35 @@ class Context:
             raise ValueError("scoring is (match, mismatch, gap_open, gap_extend)")
         return _lib.AlignScoring(*(int(v) for v in scoring))
 
-    def align_pairs(self, targets: Sequence[bytes], reads: Sequence[bytes], target_of_read, rev, max_cells=0, pair_chunk=0, scoring=None) -> dict:
+    @staticmethod
+    def _align_mode(mode):
+        """None for "local" (the four calls without a mode); else the integer the *_mode calls take: 1 for "read", an integer as it is
+        (0, RATTLE_ALIGN_LOCAL, goes through the *_mode calls too; the library refuses what it does not know)"""
+        if isinstance(mode, str):
+            if mode not in ALIGN_MODES:
+                raise ValueError('mode is "local" or "read"')
+            return None if mode == "local" else ALIGN_MODES[mode]
+        return int(mode)
+
+    def align_pairs(self, targets: Sequence[bytes], reads: Sequence[bytes], target_of_read, rev, max_cells=0, pair_chunk=0, scoring=None,
+                    mode="local") -> dict:
         """Every read r with target_of_read[r] >= 0 aligned locally to that target, reverse-complemented first where rev[r] == 1
         (rattle_hip_align_pairs, kernel E): the two arrays are `target` and `rev` of an assignment.  Returns a dict of arrays with one
         entry per read (_lib.ALIGN_FIELDS): status (0 aligned, 1 nothing aligns, 2 skipped by max_cells, 3 not submitted), score,
         q_start, q_end (on the read as given), t_start, t_end, matches, mismatches, q_gap, t_gap.
         scoring: None is that call -- match 5, mismatch -4, gap -8 per column; a tuple (match, mismatch, gap_open, gap_extend) of positive
         magnitudes, each in [1, 64] with gap_extend <= gap_open, is rattle_hip_align_pairs_scored: affine gaps, the three-state kernel E,
-        also for (5, 4, 8, 8), which gives the records of None."""
+        also for (5, 4, 8, 8), which gives the records of None.
+        mode: "local", or "read" (rattle_hip_align_pairs_mode with RATTLE_ALIGN_READ): the read end to end, the transcript's ends free;
+        status 0 for every pair of two non-empty sequences, q_start 0, q_end Lq, a score that may be negative."""
         tcat, toff = pack_reads(targets)
         rcat, roff = pack_reads(reads)
-        return self.align_pairs_packed(tcat, toff, rcat, roff, target_of_read, rev, max_cells, pair_chunk, scoring)
+        return self.align_pairs_packed(tcat, toff, rcat, roff, target_of_read, rev, max_cells, pair_chunk, scoring, mode)
 
     def align_pairs_packed(self, tcat: np.ndarray, toff: np.ndarray, rcat: np.ndarray, roff: np.ndarray, target_of_read, rev,
-                           max_cells=0, pair_chunk=0, scoring=None) -> dict:
+                           max_cells=0, pair_chunk=0, scoring=None, mode="local") -> dict:
         """align_pairs() on packed arrays (pack_reads)"""
+        M = self._align_mode(mode)
         P = _lib.AlignParams(int(max_cells), int(pair_chunk))
         n = len(roff) - 1
         t = np.ascontiguousarray(target_of_read, np.int32)
@@ -691,7 +706,10 @@ class Context:
         args = (self.h, _ptr(tcat, C.c_uint8) if len(tcat) else None, _ptr(toff, C.c_uint64), len(toff) - 1,
                 _ptr(rcat, C.c_uint8) if len(rcat) else None, _ptr(roff, C.c_uint64), n, _ptr(t, C.c_int32) if n else None,
                 _ptr(r, C.c_uint8) if n else None, C.byref(P))
-        if scoring is None:
+        if M is not None:
+            S = None if scoring is None else self._scoring(scoring)
+            check(self.lib.rattle_hip_align_pairs_mode(*args, None if S is None else C.byref(S), M, C.byref(out)))
+        elif scoring is None:
             check(self.lib.rattle_hip_align_pairs(*args, C.byref(out)))
         else:
             S = self._scoring(scoring)
@@ -701,19 +719,22 @@ class Context:
         self.lib.rattle_hip_alignment_free(out)
         return res
 
-    def align_cigars(self, targets: Sequence[bytes], reads: Sequence[bytes], target_of_read, rev, max_cells=0, pair_chunk=0, scoring=None):
+    def align_cigars(self, targets: Sequence[bytes], reads: Sequence[bytes], target_of_read, rev, max_cells=0, pair_chunk=0, scoring=None,
+                     mode="local"):
         """align_pairs(), and the CIGAR of every read that aligns (rattle_hip_align_cigars, kernels E and F).  Returns (records, offsets,
         ops): the dict align_pairs returns for the same arguments, and the ops of read r as ops[offsets[r]:offsets[r + 1]], uint32
         len << 4 | op with BAM's numbers (= 7, X 8, I 1, D 2), from the alignment's start to its end on the strand that was aligned
         (cigar_bytes formats them).  A read whose status is not 0 has none.  scoring: as in align_pairs (a tuple is
-        rattle_hip_align_cigars_scored, the three-state kernels E and F)."""
+        rattle_hip_align_cigars_scored, the three-state kernels E and F).  mode: as in align_pairs ("read" is
+        rattle_hip_align_cigars_mode: the ops of a read sum to its whole length, overhangs are I runs at the ends)."""
         tcat, toff = pack_reads(targets)
         rcat, roff = pack_reads(reads)
-        return self.align_cigars_packed(tcat, toff, rcat, roff, target_of_read, rev, max_cells, pair_chunk, scoring)
+        return self.align_cigars_packed(tcat, toff, rcat, roff, target_of_read, rev, max_cells, pair_chunk, scoring, mode)
 
     def align_cigars_packed(self, tcat: np.ndarray, toff: np.ndarray, rcat: np.ndarray, roff: np.ndarray, target_of_read, rev,
-                            max_cells=0, pair_chunk=0, scoring=None):
+                            max_cells=0, pair_chunk=0, scoring=None, mode="local"):
         """align_cigars() on packed arrays (pack_reads)"""
+        M = self._align_mode(mode)
         P = _lib.AlignParams(int(max_cells), int(pair_chunk))
         n = len(roff) - 1
         t = np.ascontiguousarray(target_of_read, np.int32)
@@ -725,7 +746,10 @@ class Context:
         args = (self.h, _ptr(tcat, C.c_uint8) if len(tcat) else None, _ptr(toff, C.c_uint64), len(toff) - 1,
                 _ptr(rcat, C.c_uint8) if len(rcat) else None, _ptr(roff, C.c_uint64), n, _ptr(t, C.c_int32) if n else None,
                 _ptr(r, C.c_uint8) if n else None, C.byref(P))
-        if scoring is None:
+        if M is not None:
+            S = None if scoring is None else self._scoring(scoring)
+            check(self.lib.rattle_hip_align_cigars_mode(*args, None if S is None else C.byref(S), M, C.byref(out), C.byref(cg)))
+        elif scoring is None:
             check(self.lib.rattle_hip_align_cigars(*args, C.byref(out), C.byref(cg)))
         else:
             S = self._scoring(scoring)
@@ -1162,45 +1186,49 @@ def paf_ranked_text(read_names: Sequence[bytes], read_lengths: Sequence[int], ta
 
 
 def align_ranks(ctx: Context, targets: Sequence[bytes], reads: Sequence[bytes], cands: dict, max_cells=0, pair_chunk=0, cigar=False,
-                scoring=None):
+                scoring=None, mode="local"):
     """Every read aligned to each of its candidates: one call of Context.align_pairs (cigar: align_cigars) per rank j, with slot j's
-    target and strand as target_of_read and rev, up to the first rank no read has.  Returns (alignments, cigars): one record set
-    per rank, and one (offsets, ops) per rank or None."""
+    target and strand as target_of_read and rev, up to the first rank no read has, every rank in the same `mode`.  Returns
+    (alignments, cigars): one record set per rank, and one (offsets, ops) per rank or None."""
     alns, cgs = [], []
     for j in range(cands["target"].shape[1]):
         if not (np.asarray(cands["count"]) > j).any():
             break
         t = np.ascontiguousarray(cands["target"][:, j]); r = np.ascontiguousarray(cands["rev"][:, j])
         if cigar:
-            aln, offsets, ops = ctx.align_cigars(targets, reads, t, r, max_cells, pair_chunk, scoring)
+            aln, offsets, ops = ctx.align_cigars(targets, reads, t, r, max_cells, pair_chunk, scoring, mode)
             cgs.append((offsets, ops))
         else:
-            aln = ctx.align_pairs(targets, reads, t, r, max_cells, pair_chunk, scoring)
+            aln = ctx.align_pairs(targets, reads, t, r, max_cells, pair_chunk, scoring, mode)
         alns.append(aln)
     return alns, (cgs if cigar else None)
 
 
 def assign_paf_command(ctx: Context, read_headers: Sequence[bytes], reads: Sequence[bytes], target_headers: Sequence[bytes],
                        targets: Sequence[bytes], *, k=10, t_s=0.2, t_v=1000000.0, bv_threshold=0.4, is_rna=False, count_pass="auto",
-                       target_batch=0, read_chunk=0, max_cells=0, pair_chunk=0, cigar=False, scoring=None, secondary=0):
+                       target_batch=0, read_chunk=0, max_cells=0, pair_chunk=0, cigar=False, scoring=None, secondary=0,
+                       end_to_end=False):
     """`rattle assign --paf`: assign_command, then every placed read aligned to its transcript (Context.align_pairs).  Returns the bytes
     of assignments.tsv, target_counts.tsv and alignments.paf; the first two are what assign_command returns.  cigar=True is
     `--paf --cigar`: Context.align_cigars, and a cg:Z: tag on every line.  scoring=(m, x, o, e) is `--paf-scoring m,x,o,e`: affine gaps
     (Context.align_pairs); None is the linear default.  secondary=N (1..7) is `--secondary N`: every read is aligned to each of its
-    N + 1 candidates (align_ranks), alignments.paf is the ranked one (paf_ranked_text) and the bytes of candidates.tsv come fourth."""
+    N + 1 candidates (align_ranks), alignments.paf is the ranked one (paf_ranked_text) and the bytes of candidates.tsv come fourth.
+    end_to_end=True is `--paf-end-to-end`: every alignment, of every rank, in mode "read" -- the whole read on every line; the tables
+    do not change."""
+    mode = "read" if end_to_end else "local"
     rec, cands = _assign_submitted(ctx, reads, targets, k, t_s, t_v, bv_threshold, is_rna, count_pass, target_batch, read_chunk, secondary)
     tn = [_first_token(h) for h in target_headers]
     rn = [_first_token(h) for h in read_headers]
     tl = [len(s) for s in targets]
     rl = [len(s) for s in reads]
     if cands is not None:
-        alns, cgs = align_ranks(ctx, targets, reads, cands, max_cells, pair_chunk, cigar, scoring)
+        alns, cgs = align_ranks(ctx, targets, reads, cands, max_cells, pair_chunk, cigar, scoring, mode)
         return (assignments_tsv(rn, tn, rec), target_counts_tsv(tn, tl, rec), paf_ranked_text(rn, rl, tn, tl, cands, alns, cgs),
                 candidates_tsv(rn, tn, cands))
     cigars = None
     if cigar:
-        aln, offsets, ops = ctx.align_cigars(targets, reads, rec["target"], rec["rev"], max_cells, pair_chunk, scoring)
+        aln, offsets, ops = ctx.align_cigars(targets, reads, rec["target"], rec["rev"], max_cells, pair_chunk, scoring, mode)
         cigars = (offsets, ops)
     else:
-        aln = ctx.align_pairs(targets, reads, rec["target"], rec["rev"], max_cells, pair_chunk, scoring)
+        aln = ctx.align_pairs(targets, reads, rec["target"], rec["rev"], max_cells, pair_chunk, scoring, mode)
     return (assignments_tsv(rn, tn, rec), target_counts_tsv(tn, tl, rec), paf_text(rn, rl, tn, tl, rec, aln, cigars))

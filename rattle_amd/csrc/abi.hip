@@ -686,7 +686,7 @@ void rattle_hip_assignment_free(rattle_assignment *a) {
 // S is checked behind every check of align_pairs, still before the device is looked at, and the three-state kernels run
 static int align_entry(const char *who, rattle_ctx *c, const uint8_t *tseq, const uint64_t *toff, uint32_t nt, const uint8_t *rseq, const uint64_t *roff,
                        uint32_t nr, const int32_t *target, const uint8_t *rev, const rattle_align_params *P, rattle_alignment **out, cigar_run *run,
-                       bool scored = false, const rattle_align_scoring *S = nullptr) {
+                       bool scored = false, const rattle_align_scoring *S = nullptr, int mode = RATTLE_ALIGN_LOCAL) {
     const std::string w = std::string(who) + ": ";
     // the arguments, on the host: indices, strands, lengths, and the letters of every sequence that is submitted (a target once)
     auto clean = [](const uint8_t *s, uint64_t n) { for (uint64_t i = 0; i < n; ++i) if (!s[i] || !strchr("ACGTU", s[i])) return false; return true; };
@@ -724,6 +724,20 @@ static int align_entry(const char *who, rattle_ctx *c, const uint8_t *tseq, cons
             }
         }
     }
+    // the mode (the *_mode entry points), behind every check of the four calls: the left border of the read mode, -(open + (Lq - 1) extend),
+    // has to stay well above PW_NEG = -2^30, the kernels' minus infinity
+    if (mode != RATTLE_ALIGN_LOCAL && mode != RATTLE_ALIGN_READ) { set_error(w + "mode " + std::to_string(mode) + " is neither RATTLE_ALIGN_LOCAL nor RATTLE_ALIGN_READ"); return RATTLE_ERR_ARG; }
+    if (mode == RATTLE_ALIGN_READ) {
+        const uint64_t o = scored ? S->gap_open : 8, e = scored ? S->gap_extend : 8;
+        for (uint32_t r = 0; r < nr; ++r) {
+            if (target[r] < 0) continue;
+            const uint64_t lq = roff[r + 1] - roff[r];
+            if (lq && o + e * (lq - 1) >= (1ull << 29)) {
+                set_error(w + "read " + std::to_string(r) + ": gap_open + gap_extend * (Lq - 1) reaches 2^29, a read that long cannot be aligned end to end");
+                return RATTLE_ERR_ARG;
+            }
+        }
+    }
     RT_TRY(use_device(c));
     const size_t m = std::max<size_t>(1, nr);
     rattle_alignment *A = (rattle_alignment *)calloc(1, sizeof(rattle_alignment));
@@ -731,7 +745,7 @@ static int align_entry(const char *who, rattle_ctx *c, const uint8_t *tseq, cons
     A->status = (uint8_t *)calloc(m, 1); A->score = (int32_t *)calloc(m, 4);
     for (uint32_t **f : {&A->q_start, &A->q_end, &A->t_start, &A->t_end, &A->matches, &A->mismatches, &A->q_gap, &A->t_gap}) *f = (uint32_t *)calloc(m, 4);
     if (run) { run->count.assign(nr, 0); run->ops.clear(); run->code_cap = cigar_code_cap(); }
-    const int rc = align_pairs_run(c, tseq, toff, nt, rseq, roff, nr, target, rev, P, A, run, scored ? S : nullptr);
+    const int rc = align_pairs_run(c, tseq, toff, nt, rseq, roff, nr, target, rev, P, A, run, scored ? S : nullptr, mode);
     if (rc != 0) { rattle_hip_alignment_free(A); return rc; }
     *out = A;
     return 0;
@@ -761,7 +775,7 @@ int rattle_hip_align_pairs_scored(rattle_ctx *c, const uint8_t *tseq, const uint
 // the body of align_cigars and align_cigars_scored
 static int cigars_entry(const char *who, rattle_ctx *c, const uint8_t *tseq, const uint64_t *toff, uint32_t nt, const uint8_t *rseq, const uint64_t *roff,
                         uint32_t nr, const int32_t *target, const uint8_t *rev, const rattle_align_params *P, rattle_alignment **out,
-                        rattle_cigars **cigars, bool scored, const rattle_align_scoring *S) {
+                        rattle_cigars **cigars, bool scored, const rattle_align_scoring *S, int mode = RATTLE_ALIGN_LOCAL) {
     if (out) *out = nullptr;
     if (cigars) *cigars = nullptr;
     if (!c || !P || !out || !cigars || !toff || !roff || (nr && (!target || !rev)) || (!tseq && toff[nt] != toff[0]) || (!rseq && roff[nr] != roff[0])) {
@@ -769,7 +783,7 @@ static int cigars_entry(const char *who, rattle_ctx *c, const uint8_t *tseq, con
         return RATTLE_ERR_ARG;
     }
     cigar_run run;
-    RT_TRY(align_entry(who, c, tseq, toff, nt, rseq, roff, nr, target, rev, P, out, &run, scored, S));
+    RT_TRY(align_entry(who, c, tseq, toff, nt, rseq, roff, nr, target, rev, P, out, &run, scored, S, mode));
     rattle_cigars *G = (rattle_cigars *)calloc(1, sizeof(rattle_cigars));
     G->n = nr;
     G->offset = (uint64_t *)calloc((size_t)nr + 1, 8);
@@ -790,6 +804,26 @@ int rattle_hip_align_cigars_scored(rattle_ctx *c, const uint8_t *tseq, const uin
                                    uint32_t nr, const int32_t *target, const uint8_t *rev, const rattle_align_params *P, const rattle_align_scoring *S,
                                    rattle_alignment **out, rattle_cigars **cigars) {
     return cigars_entry("align_cigars_scored", c, tseq, toff, nt, rseq, roff, nr, target, rev, P, out, cigars, true, S);
+}
+
+// the four calls above with a mode: scoring NULL is the linear form.  RATTLE_ALIGN_LOCAL is the call it stands for, name and all.
+int rattle_hip_align_pairs_mode(rattle_ctx *c, const uint8_t *tseq, const uint64_t *toff, uint32_t nt, const uint8_t *rseq, const uint64_t *roff,
+                                uint32_t nr, const int32_t *target, const uint8_t *rev, const rattle_align_params *P, const rattle_align_scoring *S,
+                                int mode, rattle_alignment **out) {
+    if (out) *out = nullptr;
+    if (!c || !P || !out || !toff || !roff || (nr && (!target || !rev)) || (!tseq && toff[nt] != toff[0]) || (!rseq && roff[nr] != roff[0])) {
+        set_error("null argument");
+        return RATTLE_ERR_ARG;
+    }
+    const char *who = mode != RATTLE_ALIGN_LOCAL ? "align_pairs_mode" : S ? "align_pairs_scored" : "align_pairs";
+    return align_entry(who, c, tseq, toff, nt, rseq, roff, nr, target, rev, P, out, nullptr, S != nullptr, S, mode);
+}
+
+int rattle_hip_align_cigars_mode(rattle_ctx *c, const uint8_t *tseq, const uint64_t *toff, uint32_t nt, const uint8_t *rseq, const uint64_t *roff,
+                                 uint32_t nr, const int32_t *target, const uint8_t *rev, const rattle_align_params *P, const rattle_align_scoring *S,
+                                 int mode, rattle_alignment **out, rattle_cigars **cigars) {
+    const char *who = mode != RATTLE_ALIGN_LOCAL ? "align_cigars_mode" : S ? "align_cigars_scored" : "align_cigars";
+    return cigars_entry(who, c, tseq, toff, nt, rseq, roff, nr, target, rev, P, out, cigars, S != nullptr, S, mode);
 }
 
 void rattle_hip_cigars_free(rattle_cigars *g) {

@@ -549,17 +549,18 @@ struct cigar_run {                      // one call of rattle_hip_align_cigars: 
 uint64_t cigar_code_cap();              // 4 GiB, or what RATTLE_CIGAR_CODE_BYTES says
 // scoring == nullptr: the linear form (GAP_LINEAR of pair_wave.h, id 7); else the affine form with that scoring (GAP_AFFINE, id 9)
 int pair_cigar_chunk(rattle_ctx *ctx, const uint8_t *d_q, const uint8_t *d_t, const cigar_in *in, uint32_t n, uint32_t pair_chunk, cigar_run &R,
-                     const rattle_align_scoring *scoring = nullptr);
+                     const rattle_align_scoring *scoring = nullptr, int mode = RATTLE_ALIGN_LOCAL);
 // pair_align.hip : kernel E, the local alignment of every submitted read on its target; fills every array of A (arguments checked by the caller).
 // With `cigars`, every chunk goes on to kernel F before its sequences leave the device (cigars->count sized n_reads by the caller).
 // scoring == nullptr: kernels E and F (linear, ids 6 and 7); else their three-state forms with that scoring (ids 8 and 9).
+// mode: RATTLE_ALIGN_LOCAL, or RATTLE_ALIGN_READ -- the whole read, the <*, true> instantiations of both kernels, the same ids.
 struct align_pair {                     // one submitted pair: where its sequences lie in the uploaded buffers, and its strip (in records; unused when
     uint64_t q, t, strip;               // the read has one block)
     uint32_t lq, lt, rev, pad;
 };
 int align_pairs_run(rattle_ctx *ctx, const uint8_t *tseq, const uint64_t *toff, uint32_t n_targets, const uint8_t *rseq, const uint64_t *roff,
                     uint32_t n_reads, const int32_t *target, const uint8_t *rev, const rattle_align_params *P, rattle_alignment *A,
-                    cigar_run *cigars = nullptr, const rattle_align_scoring *scoring = nullptr);
+                    cigar_run *cigars = nullptr, const rattle_align_scoring *scoring = nullptr, int mode = RATTLE_ALIGN_LOCAL);
 constexpr uint32_t AL_REC_WORDS = 10;   // a pair's record on the device: status, score, q_start, q_end, t_start, t_end, matches, mismatches, q_gap, t_gap
 
 // correct_driver.hip

@@ -28,6 +28,14 @@
 // matrix keep their state frozen.  A lane keeps its best cell with a strict `>` over its rows in order (smallest i, then smallest j, per
 // lane); the lanes are reduced once, at the end, by (score desc, i asc, j asc).  No wavefront waits for another; every load and store
 // lies inside the pair's own two sequences, its own strip and its own record.
+//
+// The second template argument is the MODE (include/rattle_hip.h, "align_pairs_mode"; tests/align_ends_ref.py is the contract): <*, false>
+// is the local alignment above, <*, true> (RATTLE_ALIGN_READ) aligns the read from its first base to its last with the transcript's
+// ends free: H[0][j] = 0, H[i][0] = U[i][0] = -(o + (i - 1) e), no zero floor, the end cell the largest H of the last row (the smallest
+// j).  In the same body: a lane starts with its row's border as `left` (lane 0 of a later block with the border of the row above as
+// `diag`; the other lanes receive theirs from lane l - 1's frozen state); a path begins in row 0 alone -- the refill registers carry the
+// payload (0, j, 0, 0) above the first block -- and a zero is an ordinary cell; only the lane that owns the last row keeps a best cell,
+// from PW_NEG; every submitted pair has status 0.  The host keeps o + e (Lq - 1) below 2^29 (abi.hip), so PW_NEG is below every score.
 #include <algorithm>
 #include <cstring>
 
@@ -74,7 +82,7 @@ struct al_strip {
     __device__ __forceinline__ int32_t lane(uint32_t word, uint32_t k) const { return __builtin_amdgcn_readlane((int32_t)w[word], k); }
 };
 
-template <bool AFFINE>
+template <bool AFFINE, bool READ>
 __global__ __launch_bounds__(256) void pair_align_kernel(const align_pair *__restrict__ pairs, uint32_t n_pairs, const uint8_t *__restrict__ qseq,
                                                          const uint8_t *__restrict__ tseq, uint32_t *__restrict__ strips, int32_t *__restrict__ recs,
                                                          const rattle_align_scoring scoring) {
@@ -89,7 +97,7 @@ __global__ __launch_bounds__(256) void pair_align_kernel(const align_pair *__res
     const uint8_t *q = qseq + P.q, *t = tseq + P.t;
     uint32_t *strip = strips + P.strip * SW;
 
-    int32_t bH = 0;                                                  // the lane's best cell: score, end (i, j) as DP indices, payload
+    int32_t bH = READ ? PW_NEG : 0;                                  // the lane's best cell: score, end (i, j) as DP indices, payload
     uint32_t bi = 0, bj = 0, bsi = 0, bsj = 0, bm = 0, bx = 0;
 
     for (uint32_t r0 = 0; r0 < lq; r0 += AL_ROWS) {
@@ -102,16 +110,25 @@ __global__ __launch_bounds__(256) void pair_align_kernel(const align_pair *__res
         // the lane's previous cell in its states (H and U go down the lanes, L stays), lane - 1's previous H as received one step ago
         // (diag), the sliding letter
         al_cell cH = {0, 0, 0, 0, 0}, cU = {PW_NEG, 0, 0, 0, 0}, cL = {PW_NEG, 0, 0, 0, 0}, dH = {0, 0, 0, 0, 0};
+        if constexpr (READ) {
+            // column 0 is a gap straight down from (0, 0): H = U = -(o + (i - 1) e) in DP row i = r + 1, start (0, 0).  Lanes l > 0 receive
+            // the border of the row above as `diag` one step before their first column, from lane l - 1's frozen state; lane 0 of a
+            // block behind the first starts with it
+            cH.s = cU.s = -(so + (int32_t)r * se);
+            if (from_strip) dH.s = -(so + (int32_t)(r0 - 1) * se);
+        }
         int32_t tl = 4;
         // refill in flight: the transcript's letters and the strip's records of columns [S + 64, S + 128)
         int32_t nT = 4;
         al_strip<AFFINE> nR;
         nR.clear();
+        if constexpr (READ) nR.w[2] = lane + 1;                      // above the first block lies row 0: column c begins a path at (0, c + 1)
         if (lane < lt) { nT = pw_code(t[lane]); if (from_strip) nR.load(strip + (uint64_t)lane * SW); }
         for (uint32_t S = 0; S < n_steps; S += 64) {
             const int32_t bT = nT;
             const al_strip<AFFINE> bR = nR;
             nT = 4; nR.clear();
+            if constexpr (READ) nR.w[2] = S + 64 + lane + 1;
             if (S + 64 + lane < lt) { nT = pw_code(t[S + 64 + lane]); if (from_strip) nR.load(strip + (uint64_t)(S + 64 + lane) * SW); }
             const uint32_t k_end = min(64u, n_steps - S);
             for (uint32_t k = 0; k < k_end; ++k) {
@@ -139,16 +156,16 @@ __global__ __launch_bounds__(256) void pair_align_kernel(const align_pair *__res
                 const int32_t d = dH.s + (eq ? sm : -sx), u = nU.s, l = nL.s;
                 al_cell nH;
                 if (d >= u && d >= l) {                              // diagonal first; a zero predecessor begins the alignment at this cell
-                    const bool fresh = dH.s == 0;
+                    const bool fresh = !READ && dH.s == 0;           // (READ: a path begins in row 0 alone, a zero is an ordinary cell)
                     nH.i = fresh ? (int32_t)r : dH.i; nH.j = fresh ? (int32_t)c : dH.j;
                     nH.m = (fresh ? 0 : dH.m) + (eq ? 1 : 0); nH.x = (fresh ? 0 : dH.x) + (eq ? 0 : 1);
                 } else nH = al_pick(u >= l, nU, nL);                 // then up: a read base against a gap; then left: a transcript base against a gap
-                nH.s = max(max(d, 0), max(u, l));
+                nH.s = READ ? max(d, max(u, l)) : max(max(d, 0), max(u, l));
                 dH = uH;
                 if (on) {
                     cH = nH;                                         // (payload of a zero cell is never read: see `fresh`, and a gap state opened there stays < 0)
                     if constexpr (AFFINE) { cU = nU; cL = nL; }
-                    if (nH.s > bH) { bH = nH.s; bi = r + 1; bj = c + 1; bsi = (uint32_t)nH.i; bsj = (uint32_t)nH.j; bm = (uint32_t)nH.m; bx = (uint32_t)nH.x; }
+                    if ((!READ || r + 1 == lq) && nH.s > bH) { bH = nH.s; bi = r + 1; bj = c + 1; bsi = (uint32_t)nH.i; bsj = (uint32_t)nH.j; bm = (uint32_t)nH.m; bx = (uint32_t)nH.x; }
                     if (to_strip && lane == 63) {                    // c < lt: inside the pair's strip
                         al_strip<AFFINE> o;
                         o.w[0] = (uint32_t)nH.s; o.w[1] = (uint32_t)nH.i; o.w[2] = (uint32_t)nH.j; o.w[3] = (uint32_t)nH.m;
@@ -173,7 +190,7 @@ __global__ __launch_bounds__(256) void pair_align_kernel(const align_pair *__res
     }
     if (lane == 0) {
         int32_t *R = recs + (size_t)p * AL_REC_WORDS;
-        if (bH <= 0) { for (uint32_t f = 0; f < AL_REC_WORDS; ++f) R[f] = f == 0 ? 1 : 0; return; }
+        if (!READ && bH <= 0) { for (uint32_t f = 0; f < AL_REC_WORDS; ++f) R[f] = f == 0 ? 1 : 0; return; }
         const uint32_t sq = bi - bsi, st = bj - bsj;                 // the spans: sq = M + X + q_gap, st = M + X + t_gap
         // linear: S = 5 M - 4 X - 8 (q_gap + t_gap) with the spans  =>  12 X = 8 (sq + st) - 21 M + S
         const uint32_t X = AFFINE ? bx : (uint32_t)((8ll * ((long long)sq + st) - 21ll * bm + bH) / 12);
@@ -191,9 +208,11 @@ __global__ __launch_bounds__(256) void pair_align_kernel(const align_pair *__res
 // align_plan.h's; the strip buffer is sized from the lengths of the chunk.  With `cigars` (rattle_hip_align_cigars) every chunk's records go on
 // to kernel F (pair_cigar.hip) while the chunk's sequences are on the device; A is filled exactly as without.  With `scoring`
 // (rattle_hip_align_*_scored) the form is GAP_AFFINE, the launches are those of the <true> kernels; the plan, the uploads and the records are the
-// same, the strip's records are 40 bytes.
+// same, the strip's records are 40 bytes.  With mode RATTLE_ALIGN_READ (rattle_hip_align_*_mode) the launches are those of the <*, true>
+// kernels under the ids of their gap form; every submitted pair comes back with status 0 and the rectangle (0, Lq] x (t_start, t_end].
 int align_pairs_run(rattle_ctx *ctx, const uint8_t *tseq, const uint64_t *toff, uint32_t nt, const uint8_t *rseq, const uint64_t *roff, uint32_t nr,
-                    const int32_t *target, const uint8_t *rev, const rattle_align_params *AP, rattle_alignment *A, cigar_run *cigars, const rattle_align_scoring *scoring) {
+                    const int32_t *target, const uint8_t *rev, const rattle_align_params *AP, rattle_alignment *A, cigar_run *cigars, const rattle_align_scoring *scoring,
+                    int mode) {
     phase_timer T_all("align_pairs: total");
     const gap_form &F = scoring ? GAP_AFFINE : GAP_LINEAR;
     align_plan plan;
@@ -236,7 +255,8 @@ int align_pairs_run(rattle_ctx *ctx, const uint8_t *tseq, const uint64_t *toff, 
         RT_HIP(hipMemcpyAsync(d_pairs.p, h_pairs.p, (size_t)n * sizeof(align_pair), hipMemcpyHostToDevice, ctx->stream));
         {
             ktimer kt(ctx, F.k_align, seq_bytes + (uint64_t)n * AL_REC_WORDS * 4);
-            const auto kernel = scoring ? pair_align_kernel<true> : pair_align_kernel<false>;
+            const auto kernel = mode == RATTLE_ALIGN_READ ? (scoring ? pair_align_kernel<true, true> : pair_align_kernel<false, true>)
+                                                          : (scoring ? pair_align_kernel<true, false> : pair_align_kernel<false, false>);
             hipLaunchKernelGGL(kernel, dim3((n + 3) / 4), dim3(256), 0, ctx->stream, d_pairs.p, n, d_q.p, d_t.p, d_strip.p, d_rec.p, scoring ? *scoring : PW_LINEAR);
             RT_HIP(hipGetLastError());
         }
@@ -258,10 +278,14 @@ int align_pairs_run(rattle_ctx *ctx, const uint8_t *tseq, const uint64_t *toff, 
                 const align_pair &P = h_pairs.p[i];
                 cigar_in &I = in[i];
                 I.status = A->status[r]; I.rev = rev[r]; I.read = r;
+                if (A->q_start[r] > A->q_end[r] || A->q_end[r] > P.lq || A->t_start[r] > A->t_end[r] || A->t_end[r] > P.lt) {
+                    set_error("align_cigars: a record of kernel E lies outside its pair");      // (never: kernel F must not be handed such a rectangle)
+                    return RATTLE_ERR_HIP;
+                }
                 I.rows = A->q_end[r] - A->q_start[r]; I.cols = A->t_end[r] - A->t_start[r];
                 I.q = P.q + (P.rev ? (uint64_t)A->q_end[r] - (I.rows ? 1 : 0) : (uint64_t)A->q_start[r]); I.t = P.t + A->t_start[r];
             }
-            RT_TRY(pair_cigar_chunk(ctx, d_q.p, d_t.p, in.data(), n, AP->pair_chunk ? AP->pair_chunk : 32768u, *cigars, scoring));
+            RT_TRY(pair_cigar_chunk(ctx, d_q.p, d_t.p, in.data(), n, AP->pair_chunk ? AP->pair_chunk : 32768u, *cigars, scoring, mode));
         }
     }
     return 0;

@@ -33,6 +33,13 @@
 // (affine: twice that) iterations whatever the codes say.  The window index is step - window start in [0, 64) by construction; the ops
 // cursor is checked before every store.  Every load and store lies in the pair's own sequences, strip, records, ops region or count.  A
 // wrong code gives a wrong string, never a hang or a store out of range.
+//
+// The second template argument is kernel E's MODE.  <*, true> (RATTLE_ALIGN_READ): the rectangle is every row of the read and columns
+// (t_start, t_end], its borders are the mode's -- top row H' = 0, U' = L' = -inf; left column H' = U' = -(o + (i - 1) e), L' = -inf (DESIGN.md,
+// "The read mode", has the lemma, tests/test_align_ends_ref.py checks it) -- there is no zero floor and code 0 means a cell off the matrix
+// alone.  The walk is the same loop, and may begin with a switch into U; when it leaves through the left column with rows above it,
+// those rows are the border's gap: one I run of that many rows, whatever blocks they span, added to the run at hand behind the loop in a
+// bounded number of rounds, through the same checked ops cursor.  A pair without a column never comes here (cigar_no_column, below).
 #include <algorithm>
 #include <cstdlib>
 #include <cstring>
@@ -47,7 +54,7 @@ namespace {
 
 constexpr uint32_t CG_H = 0, CG_U = 1, CG_L = 2;                              // the walk's state
 
-template <bool AFFINE>
+template <bool AFFINE, bool READ>
 __global__ __launch_bounds__(256) void pair_cigar_kernel(const cigar_pair *__restrict__ pairs, uint32_t n_pairs, const uint8_t *__restrict__ qseq,
                                                          const uint8_t *__restrict__ tseq, uint4 *__restrict__ codes, int32_t *__restrict__ strips,
                                                          uint32_t *__restrict__ ops, uint32_t *__restrict__ counts, const rattle_align_scoring scoring) {
@@ -80,6 +87,10 @@ __global__ __launch_bounds__(256) void pair_cigar_kernel(const cigar_pair *__res
         const uint32_t n_steps = st + min(CG_ROWS, sq - r0) - 1;     // the block's last row computes its last column at the last step
         uint4 *rec_b = code + RW * ((uint64_t)b * stride);
         int32_t cH = 0, cU = PW_NEG, cL = PW_NEG, dH = 0, tl = 4;    // the lane's previous cell in its states, lane - 1's H as received one step ago (diag)
+        if constexpr (READ) {                                        // the left border is a gap straight down: kernel E's values (pair_align.hip)
+            cH = cU = -(so + (int32_t)r * se);
+            if (from_strip) dH = -(so + (int32_t)(r0 - 1) * se);
+        }
         // refill in flight: the transcript's letters and the strip's scores (H, U) of columns [S + 64, S + 128)
         int32_t nT = 4, nH = 0, nU = PW_NEG;
         if (lane < st) { nT = pw_code(t[lane]); if (from_strip) strip_load(lane, nH, nU); }
@@ -103,8 +114,9 @@ __global__ __launch_bounds__(256) void pair_cigar_kernel(const cigar_pair *__res
                 if constexpr (AFFINE) { ue = pw_shr1(cU, __builtin_amdgcn_readlane(bU, k)) - se; le = cL - se; }
                 const int32_t u = AFFINE ? max(uo, ue) : uo, l = AFFINE ? max(lo_, le) : lo_;
                 const int32_t d = dH + (ql == tl ? sm : -sx);
-                const int32_t h = max(max(d, 0), max(u, l));
-                const uint32_t cd = !on || h == 0 ? 0u : d >= u && d >= l ? 1u : u >= l ? 2u : 3u;      // diagonal, then up, then left
+                const int32_t h = READ ? max(d, max(u, l)) : max(max(d, 0), max(u, l));
+                // diagonal, then up, then left; READ: no zero cells, code 0 is a cell off the matrix alone
+                const uint32_t cd = !on || (!READ && h == 0) ? 0u : d >= u && d >= l ? 1u : u >= l ? 2u : 3u;
                 dH = uH;
                 if (on) { cH = h; cU = u; cL = l; }
                 const bool mine = lane == k;
@@ -139,6 +151,7 @@ __global__ __launch_bounds__(256) void pair_cigar_kernel(const cigar_pair *__res
     uint32_t b = (sq - 1) >> 6, L = (sq - 1) & 63u, c = st - 1;      // block, lane (row 64 b + L), column
     const uint32_t region = sq + st;                                 // words of the ops region = the most moves that emit
     uint32_t pos = region, run_op = 0, run_len = 0, state = CG_H;
+    uint32_t left_rows = 0;                                          // READ: rows above the walk when it leaves through the left column
     uint32_t wb = ~0u, W = 0, qb = ~0u, T0 = ~0u;                    // the windows: block and first step of the records, block of the read bases, first column
     uint4 win0 = make_uint4(0, 0, 0, 0), win1 = make_uint4(0, 0, 0, 0);
     int32_t qw = 4, tw = 4;
@@ -189,8 +202,28 @@ __global__ __launch_bounds__(256) void pair_cigar_kernel(const cigar_pair *__res
         }
         bool done = false;
         if (mv != 3) { if (L) --L; else if (b) { --b; L = 63; } else done = true; }      // up out of lane 0: lane 63 of the block above
-        if (mv != 2) { if (c) --c; else done = true; }
+        if (mv != 2) {
+            if (c) --c;
+            else {
+                if constexpr (READ) if (!done) left_rows = b * CG_ROWS + L + 1;      // in the left column with rows above: (b, L) is the row the walk stands in
+                done = true;
+            }
+        }
         if (done) break;                                             // the rectangle's top row or left column
+    }
+    if constexpr (READ) {
+        // the left column is the border, a gap straight down from the corner: the rows left are one I run, whatever blocks they span,
+        // merged into the run at hand and cut at PW_MAX_RUN as every run is.  A round adds to the run or closes a full (or other) one, so
+        // left_rows < 2^31 is spent within 2 * 9 rounds
+        for (uint32_t round = 0; round < 18 && left_rows; ++round) {
+            if (run_op == PW_OP_I && run_len < PW_MAX_RUN) {
+                const uint32_t take = min(left_rows, PW_MAX_RUN - run_len);
+                run_len += take; left_rows -= take;
+            } else {
+                if (run_len && pos) { --pos; if (lane == 0) op[pos] = run_len << 4 | run_op; }
+                run_op = PW_OP_I; run_len = 0;
+            }
+        }
     }
     if (run_len && pos) { --pos; if (lane == 0) op[pos] = run_len << 4 | run_op; }
     if (lane == 0) counts[p] = region - pos;
@@ -215,13 +248,39 @@ uint64_t cigar_code_cap() {
     return v ? std::max<uint64_t>(1, strtoull(v, nullptr, 10)) : CG_CODE_CAP;
 }
 
+// RATTLE_ALIGN_READ: an aligned pair whose rectangle has no column (t_end == t_start: the whole read against a gap) is not planned, so
+// kernel F never sees it; its CIGAR is one I run of `rows`, written here, in pieces of at most PW_MAX_RUN with the short piece first as
+// kernel F leaves them.  The ops the chunk appended behind ops[before] lie in the order of the pairs that went to the device; they are
+// merged with the written ones into the order of the chunk's pairs.  Nothing is counted in the kernel stats.
+static void cigar_no_column(const cigar_in *in, uint32_t n, cigar_run &R, size_t before) {
+    bool any = false;
+    for (uint32_t i = 0; i < n && !any; ++i) any = in[i].status == 0 && in[i].rows && !in[i].cols;
+    if (!any) return;
+    const std::vector<uint32_t> dev(R.ops.begin() + before, R.ops.end());
+    R.ops.resize(before);
+    size_t at = 0;
+    for (uint32_t i = 0; i < n; ++i) {
+        if (in[i].status == 0 && in[i].rows && !in[i].cols) {
+            const uint32_t head = in[i].rows % PW_MAX_RUN, full = in[i].rows / PW_MAX_RUN;
+            if (head) R.ops.push_back(head << 4 | PW_OP_I);
+            for (uint32_t k = 0; k < full; ++k) R.ops.push_back(PW_MAX_RUN << 4 | PW_OP_I);
+            R.count[in[i].read] = full + (head ? 1 : 0);
+        } else {
+            const size_t cnt = std::min<size_t>(R.count[in[i].read], dev.size() - at);      // (0 for a pair that did not go on)
+            R.ops.insert(R.ops.end(), dev.begin() + at, dev.begin() + at + cnt);
+            at += cnt;
+        }
+    }
+}
+
 // The pairs `in` of one chunk of kernel E, whose sequences lie in d_q and d_t: the ops of every pair with status 0 appended to R.ops, their
 // number to R.count[read].  Sub-chunks as cigar_plan.h plans them; per sub-chunk one launch of kernel F (id 7 of the stats), the counts to
 // the host, offsets from them, one gather launch, and the compact ops back.  With `scoring` the form is GAP_AFFINE (id 9): the <true>
 // kernel, 32-byte records, two strip words per column; everything around it is the same.
 int pair_cigar_chunk(rattle_ctx *ctx, const uint8_t *d_q, const uint8_t *d_t, const cigar_in *in, uint32_t n, uint32_t pair_chunk, cigar_run &R,
-                     const rattle_align_scoring *scoring) {
+                     const rattle_align_scoring *scoring, int mode) {
     const gap_form &F = scoring ? GAP_AFFINE : GAP_LINEAR;
+    const size_t ops_before = R.ops.size();
     std::vector<uint8_t> status(n);
     std::vector<uint32_t> rows(n), cols(n);
     for (uint32_t i = 0; i < n; ++i) { status[i] = in[i].status; rows[i] = in[i].rows; cols[i] = in[i].cols; }
@@ -253,7 +312,8 @@ int pair_cigar_chunk(rattle_ctx *ctx, const uint8_t *d_q, const uint8_t *d_t, co
         RT_HIP(hipMemcpyAsync(R.d_pairs.p, R.h_pairs.p, (size_t)m * sizeof(cigar_pair), hipMemcpyHostToDevice, ctx->stream));
         {
             ktimer kt(ctx, F.k_cigar, alg);
-            const auto kernel = scoring ? pair_cigar_kernel<true> : pair_cigar_kernel<false>;
+            const auto kernel = mode == RATTLE_ALIGN_READ ? (scoring ? pair_cigar_kernel<true, true> : pair_cigar_kernel<false, true>)
+                                                          : (scoring ? pair_cigar_kernel<true, false> : pair_cigar_kernel<false, false>);
             hipLaunchKernelGGL(kernel, dim3((m + 3) / 4), dim3(256), 0, ctx->stream, R.d_pairs.p, m, d_q, d_t, R.d_codes.p, R.d_strip.p, R.d_ops.p,
                                R.d_count.p, scoring ? *scoring : PW_LINEAR);
             RT_HIP(hipGetLastError());
@@ -279,6 +339,7 @@ int pair_cigar_chunk(rattle_ctx *ctx, const uint8_t *d_q, const uint8_t *d_t, co
         RT_HIP(hipStreamSynchronize(ctx->stream));
         R.ops.insert(R.ops.end(), R.h_out.p, R.h_out.p + total);
     }
+    if (mode == RATTLE_ALIGN_READ) cigar_no_column(in, n, R, ops_before);
     return 0;
 }
 

@@ -10,7 +10,8 @@
 namespace rattle {
 
 // Each kernel is one template in two forms: <false> linear gaps at 5,4,8,8, <true> affine gaps with the caller's scoring, three states per
-// cell.  What the host has to know of a form:
+// cell.  The second template argument, the mode (local, or the whole read: RATTLE_ALIGN_READ), changes neither the ids nor the layouts.
+// What the host has to know of a form:
 struct gap_form {
     int k_align, k_cigar;               // ids of the kernel stats
     uint64_t strip_bytes;               // kernel E: bytes of the hand-over strip per column

@@ -788,6 +788,7 @@ struct assign_job {
     rattle_align_params AP;
     bool want_scoring = false;                    // --paf-scoring m,x,o,e: affine gaps, the three-state kernels
     rattle_align_scoring AS;
+    bool want_ends = false;                       // --paf-end-to-end: the whole read on every line (RATTLE_ALIGN_READ)
     std::string text, counts, paf, cand;         // assignments.tsv, target_counts.tsv, alignments.paf (--paf), candidates.tsv (--secondary)
     void options(int argc, char **argv) {
         a = parse(argc, argv, {
@@ -797,7 +798,7 @@ struct assign_job {
             {"count-pass", {"--count-pass"}, true}, {"device", {"--device"}, true}, {"devices", {"--devices"}, true},
             {"target-batch", {"--target-batch"}, true}, {"read-chunk", {"--read-chunk"}, true}, {"paf", {"--paf"}, false},
             {"paf-max-cells", {"--paf-max-cells"}, true}, {"cigar", {"--cigar"}, false}, {"paf-scoring", {"--paf-scoring"}, true},
-            {"secondary", {"--secondary"}, true}});
+            {"secondary", {"--secondary"}, true}, {"paf-end-to-end", {"--paf-end-to-end"}, false}});
         const char *usage = "rattle assign -i reads.fq -x transcripts.fq [-o dir] [-k 10] [-s 0.2] [-v 1000000] [-B 0.4] [--rna] [--device n] [--paf [--cigar]] [--secondary n]\n"
                             "  places every read of -i on the transcript of -x that accepts it with the best score (the comparison `cluster` joins\n"
                             "  reads by, the transcript in the seed's role) and writes assignments.tsv (one line per read: target, strand, score,\n"
@@ -812,6 +813,9 @@ struct assign_job {
                             "  --paf-scoring m,x,o,e                 with --paf: affine gaps and this scoring, four positive integers: match +m, mismatch -x,\n"
                             "                                        the first column of a gap -o, every further one -e; each in 1..64, e <= o.  5,4,8,6 is the\n"
                             "                                        scoring of `correct`, 2,4,4,2 minimap2's.  Default: linear gaps, 5,4,8,8\n"
+                            "  --paf-end-to-end                      with --paf: align every read from its first base to its last, the transcript's ends free\n"
+                            "                                        (semi-global): nothing is clipped, an overhang or a foreign exon shows as I or X at the\n"
+                            "                                        line's end, AS may be negative, and the AS of --secondary's ranks are comparable\n"
                             "  --secondary n                         n in 1..7: also write candidates.tsv, the best transcript of every read and its n next-best\n"
                             "                                        (one line per read and rank: read, rank, target, strand, score, bases, hc_bases, min_len,\n"
                             "                                        variance); with --paf every one of them is aligned, and each line of alignments.paf carries\n"
@@ -846,6 +850,8 @@ struct assign_job {
             if (w[3] > w[2]) die(limit);
             AS.match = w[0]; AS.mismatch = w[1]; AS.gap_open = w[2]; AS.gap_extend = w[3];
         }
+        want_ends = a.has("paf-end-to-end");
+        if (want_ends && !want_paf) die("\nError: --paf-end-to-end needs --paf\n");
         if (a.has("secondary")) {
             const std::string v = a.str("secondary", "");
             if (v.size() != 1 || v[0] < '1' || v[0] > '7') die("\nError: --secondary takes a number of further transcripts per read in 1..7\n");
@@ -880,7 +886,9 @@ struct assign_job {
     }
     // the submitted reads on target[r] / rev[r] each (-1: not aligned): one call of the library
     void align_on(const int32_t *target, const uint8_t *rev, rattle_alignment **L, rattle_cigars **G) {
-        if (want_scoring && want_cigar) chk(rattle_hip_align_cigars_scored(team.ctx[0], xcat.data(), xoff.data(), (uint32_t)xid.size(), rcat.data(), roff.data(), (uint32_t)rid.size(), target, rev, &AP, &AS, L, G));
+        if (want_ends && want_cigar) chk(rattle_hip_align_cigars_mode(team.ctx[0], xcat.data(), xoff.data(), (uint32_t)xid.size(), rcat.data(), roff.data(), (uint32_t)rid.size(), target, rev, &AP, want_scoring ? &AS : nullptr, RATTLE_ALIGN_READ, L, G));
+        else if (want_ends) chk(rattle_hip_align_pairs_mode(team.ctx[0], xcat.data(), xoff.data(), (uint32_t)xid.size(), rcat.data(), roff.data(), (uint32_t)rid.size(), target, rev, &AP, want_scoring ? &AS : nullptr, RATTLE_ALIGN_READ, L));
+        else if (want_scoring && want_cigar) chk(rattle_hip_align_cigars_scored(team.ctx[0], xcat.data(), xoff.data(), (uint32_t)xid.size(), rcat.data(), roff.data(), (uint32_t)rid.size(), target, rev, &AP, &AS, L, G));
         else if (want_scoring) chk(rattle_hip_align_pairs_scored(team.ctx[0], xcat.data(), xoff.data(), (uint32_t)xid.size(), rcat.data(), roff.data(), (uint32_t)rid.size(), target, rev, &AP, &AS, L));
         else if (want_cigar) chk(rattle_hip_align_cigars(team.ctx[0], xcat.data(), xoff.data(), (uint32_t)xid.size(), rcat.data(), roff.data(), (uint32_t)rid.size(), target, rev, &AP, L, G));
         else chk(rattle_hip_align_pairs(team.ctx[0], xcat.data(), xoff.data(), (uint32_t)xid.size(), rcat.data(), roff.data(), (uint32_t)rid.size(), target, rev, &AP, L));
