@@ -24,7 +24,8 @@
 // payload), five 8-byte stores.  The strip is read back 64 columns at a time, one record per lane and one refill ahead of its use, so no
 // step waits on a load; the record of column s then reaches lane 0 by v_readlane.  The strip is updated in place: column c is read one
 // refill before step 64 floor(c / 64) and written at step c + 63 of the same block, after the load's data has been consumed.  On the
-// first block lane 0's U is PW_NEG, and no U or L that is computed lies below -64 once an H has entered it.  Lanes whose cell is off the
+// first block lane 0's U is PW_NEG, and a U or L that is kept is at least the H it was opened from less o: >= -64 in the local mode (o <= 64,
+// H >= 0), above -2^29 - 64 in the read mode, where H goes down to -(o + e (Lq - 1)) -- never near PW_NEG (pair_wave.h).  Lanes whose cell is off the
 // matrix keep their state frozen.  A lane keeps its best cell with a strict `>` over its rows in order (smallest i, then smallest j, per
 // lane); the lanes are reduced once, at the end, by (score desc, i asc, j asc).  No wavefront waits for another; every load and store
 // lies inside the pair's own two sequences, its own strip and its own record.

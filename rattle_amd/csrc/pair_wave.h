@@ -21,7 +21,11 @@ constexpr gap_form GAP_LINEAR = {K_ALIGN, K_CIGAR, AL_STRIP_BYTES, CG_REC_BYTES,
 constexpr gap_form GAP_AFFINE = {K_ALIGN_AFFINE, K_CIGAR_AFFINE, AL_AFFINE_STRIP_BYTES, CG_AFFINE_REC_BYTES, CG_AFFINE_STRIP_WORDS};
 
 constexpr rattle_align_scoring PW_LINEAR = {5, 4, 8, 8};       // the scoring of the linear form: a gap column costs 8, opened or extended
-constexpr int32_t PW_NEG = -(1 << 30);                         // minus infinity of a gap state: PW_NEG - 64 does not wrap
+// Minus infinity of a gap state.  It is never decremented twice: a gap state that is kept is max(H - o, state - e) >= H - o of a cell on the
+// matrix or its border, and every such H is >= 0 (local) or >= -(o + e (Lq - 1)) > -2^29 (read mode: H >= U >= the gap straight down from
+// row 0; abi.hip keeps that below 2^29).  So with o, e <= 64 every kept U is > -2^29 and every kept L > -2^29 - 64, both above PW_NEG, whose
+// own open or extend, PW_NEG - 64, does not wrap and loses every max.
+constexpr int32_t PW_NEG = -(1 << 30);
 constexpr uint32_t PW_OP_I = 1, PW_OP_D = 2, PW_OP_EQ = 7, PW_OP_X = 8;      // BAM's numbers
 constexpr uint32_t PW_MAX_RUN = 0x0FFFFFFFu;                   // 28 bits of length: a longer run is written in pieces
 
