@@ -3611,6 +3611,7 @@ struct poa_env {
     int head_start_us = std::max(0, std::min(1000, num("RATTLE_POA_HEAD_START_US", 30)));      // see poa_head_start (0: none)
     bool noring = num("RATTLE_POA_NORING", 0) != 0;             // =1: classes 4 .. 7 take their forms without a ring, as if the bitmaps left no LDS for one (tests)
     int64_t band_lds = getenv("RATTLE_POA_BAND_LDS") ? (int64_t)(uint32_t)num("RATTLE_POA_BAND_LDS", 0) : -1;      // the band's LDS bytes (measurements)
+    int fold = getenv("RATTLE_POA_FOLD") ? num("RATTLE_POA_FOLD", 0) != 0 : -1;      // 0 | 1: a barrier-form class never hands its packs to the next wider one / does so whatever their numbers (default: by poa_run::fold_classes' rule)
 };
 
 // A pass launches its groups on several streams at once, and the device places their workgroups in whatever order the queues reach it.
@@ -3644,6 +3645,7 @@ struct cls_plan {
     bool clamped = false;                      // cell_cap was cut to what one slot can get: packs that still fail are skipped
     bool no_teams = false;                     // a pack of this group failed with POA_ERR_SYNC: its retries take the barrier form
     bool no_band = false;                      // packs of this group failed with POA_ERR_BAND: what is left of the group takes the full rows
+    uint32_t folded = 0; int folded_from = -1; // packs the pass about to start took in from a narrower group (poa_run::fold_classes)
     const poa_variant *V = nullptr;
 };
 
@@ -3905,6 +3907,7 @@ struct poa_run {
         for (int c = 0; c < POA_GROUPS; ++c) {
             cls_plan &P = C[c];
             P.n_slots = 0;
+            P.folded = 0; P.folded_from = -1;
             if (P.todo.empty()) continue;
             if (P.rounds >= 6) { RT_TRY(give_up(P)); continue; }
             std::sort(P.todo.begin(), P.todo.end(), [this](uint32_t a, uint32_t b) { return pbases[a] != pbases[b] ? pbases[a] > pbases[b] : a < b; });
@@ -3930,6 +3933,45 @@ struct poa_run {
             want_bytes += P.per_slot * P.n_slots;
         }
         return 0;
+    }
+    // A device-filling pass of two barrier-form classes is short of workgroups when the narrower instance holds fewer of them per CU
+    // than the wider one (1024 columns: seven, 1536 columns: eight; stage 1 of `correct` averaged 1750 of 2048 places whichever grid the
+    // device placed first, profiles/round6_timeline_stage1_six_steps.txt).  A pack's class is only its LONGEST read -- the wide instance
+    // aligns shorter reads all the time, its idle wavefronts counting barriers -- so such a narrow group hands all its packs to the next
+    // wider one: one grid, one LDS footprint, the wider instance's places until the queue is dry.  Group g folds into g + 1 when
+    //   - both are ordinary classes in the barrier form on their first pass (same capacities rule; no clamp),
+    //   - each has more packs than places and the narrow one fewer places (RATTLE_POA_FOLD=1: whatever their numbers; =0: never),
+    //   - the arena budget binds neither before nor after (a folded pack takes a wide slot: config 5's passes must not lose slots to that).
+    // The wide group is planned again for the merged list; the packs stay with it for the rest of the call (the timeline keeps a pack's
+    // own class; the POA_PROFILE build counts its phases under the wide one).
+    void fold_classes() {
+        if (ENV.fold == 0 || want_bytes > budget) return;
+        bool narrowest = true;
+        for (int g = 0; g + 1 < 4; ++g) {
+            cls_plan &N = C[g], &W = C[g + 1];
+            if (N.todo.empty()) continue;
+            const bool alone_ok = ENV.fold == 1 && narrowest;      // (=1 also fills an EMPTY wide group, from the narrowest class of the pass: a class measured on its own)
+            narrowest = false;
+            if (!N.n_slots || N.folded || N.V != &k_dense[g] || W.V != &k_dense[g + 1]) continue;      // (one step: what a group took in stays there)
+            if (W.todo.empty() ? !alone_ok : !W.n_slots) continue;
+            if (N.rounds || W.rounds || N.clamped || W.clamped) continue;
+            if (ENV.fold < 0 && !(N.todo.size() > (size_t)n_cu * N.bpc && W.todo.size() > (size_t)n_cu * W.bpc && N.bpc < W.bpc)) continue;
+            const cls_plan keep = W;
+            W.todo.insert(W.todo.end(), N.todo.begin(), N.todo.end());
+            std::sort(W.todo.begin(), W.todo.end(), [this](uint32_t a, uint32_t b) { return pbases[a] != pbases[b] ? pbases[a] > pbases[b] : a < b; });
+            uint64_t tb = 0; uint32_t tl = 0;
+            for (uint32_t p : W.todo) { tb = std::max(tb, pbases[p]); tl = std::max(tl, pmaxL[p]); }
+            if (!ENV.node_cap) first_pass_caps(g + 1, tb, tl);
+            const uint64_t per = plan_group(g + 1, tb, tl);
+            W.bpc = W.V->max_blocks(W.shm);
+            W.n_slots = std::min<uint32_t>((uint32_t)W.todo.size(), n_cu * (uint32_t)W.bpc);
+            const uint64_t want = want_bytes - N.per_slot * N.n_slots - keep.per_slot * keep.n_slots + per * W.n_slots;
+            // (the merged list's largest pack may be a narrow one: more nodes, more LDS for their bitmaps -- no fold that costs the wide group a place)
+            if (per > budget || want > budget || W.V != &k_dense[g + 1] || (ENV.fold < 0 && W.bpc < keep.bpc)) { W = keep; continue; }
+            W.folded = (uint32_t)N.todo.size(); W.folded_from = g;
+            want_bytes = want;
+            N.todo.clear(); N.n_slots = 0;
+        }
     }
     // Memory decides how many packs of each group run at once.  A group lasts about (its work) / (its slots), so the pass
     // is shortest when every group gets slots in proportion to its work: T = sum(work x bytes per slot) / budget,
@@ -3999,10 +4041,11 @@ struct poa_run {
             aoff += P.per_slot * P.n_slots;
             qoff += (uint32_t)P.todo.size();
             if (ENV.timing)
-                fprintf(stderr, "[rattle]     poa class %s%u cols (%u waves x %u, %s %u%s) pass %d: %zu packs, %u slots x %.1f MB, %d blocks/CU, group %d pk %u%s\n",
+                fprintf(stderr, "[rattle]     poa class %s%u cols (%u waves x %u, %s %u%s) pass %d: %zu packs, %u slots x %.1f MB, %d blocks/CU, group %d pk %u%s%s\n",
                         poa_group_class(c) == POA_CLASSES - 1 ? "> 8192: segments of " : poa_group_band(c) ? (poa_group_chain(c) ? "(band, long chains) " : "(band) ") : c >= 12 ? "(long chains) " : c >= POA_CLASSES ? "(shallow packs) " : "", 64 * P.V->nw * P.V->cpl, P.V->nw, P.V->cpl,
                         P.V->pk == 7 ? "teams" : "ring", P.V->ring, P.V->pk == 7 ? (", ring " + std::to_string(A.ring_slots) + " reach " + std::to_string(A.ring_reach)).c_str() : "", pass, P.todo.size(), P.n_slots,
-                        P.per_slot / 1e6, P.bpc, c, P.V->pk, P.V->pk == 8 ? (" band " + std::to_string(A.band)).c_str() : "");      // (group, PK and the band's LDS bytes: which instance ran, for the tests)
+                        P.per_slot / 1e6, P.bpc, c, P.V->pk, P.V->pk == 8 ? (" band " + std::to_string(A.band)).c_str() : "",
+                        P.folded ? (", " + std::to_string(P.folded) + " folded from the " + std::to_string(k_class_cols[P.folded_from]) + " cols class").c_str() : "");      // (group, PK and the band's LDS bytes: which instance ran, for the tests; the packs fold_classes handed it)
         }
         if (e != hipSuccess) { set_error(std::string("poa setup: ") + hipGetErrorString(e)); return RATTLE_ERR_HIP; }
         return 0;
@@ -4217,6 +4260,7 @@ int poa_device_run(rattle_ctx *ctx, const uint8_t *d_seq_in, const uint64_t *d_o
         R.choose_variants();
         RT_TRY(R.size_pass(&any));
         if (!any) break;
+        R.fold_classes();
         R.share_budget();
         phase_timer T_round("    poa pass (arena+kernels)");
         RT_TRY(R.ensure_arena());
