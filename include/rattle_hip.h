@@ -268,6 +268,40 @@ int rattle_hip_assign_reads_top(rattle_ctx *ctx, const uint8_t *target_concat, c
                                 const rattle_assign_params *params, uint32_t k, rattle_assignment **out, rattle_candidates **cands);
 void rattle_hip_candidates_free(rattle_candidates *c);
 
+/* abundance (ABI 4): how much of every target is in the sample -- an expectation-maximisation over each read's compatible candidates, run
+ * on the device (csrc/abundance.hip) in INTEGER FIXED POINT, so that the result is the same bits on every run and a scalar model
+ * reproduces them (tests/abundance_ref.py).  The input is a candidate list as the _top calls return it; a hand-built one is as good.
+ *   compatible     slot j < count[r] of read r is compatible iff score[r, j] >= ratio * score[r, 0] (one double multiply, one compare);
+ *                  slot 0 always is.  The weights are uniform over the compatible slots.  A read with count[r] == 0 takes no part;
+ *                  n_placed is the number of reads that do.  compatible_reads[t]: the reads with t in a compatible slot.
+ *   units          A[t] is a uint64 in units of 2^-32 read, ONE = 2^32.  Start: a read with c compatible slots gives s = ONE / c to each
+ *                  compatible slot j >= 1 and ONE - s (c - 1) to slot 0.
+ *   one iteration  per read D = the sum of A[target] over its compatible slots; slot j >= 1 gets (uint64) floor((double)A_j / (double)D *
+ *                  2^32) -- correctly rounded conversions, one IEEE division, no contraction --, slot 0 gets ONE minus those shares
+ *                  (saturating at 0); A'[t] = the sum of the shares t receives, so sum(A') == n_placed * ONE after every iteration.
+ *   stop           delta[i] = max_t |A'[t] - A[t]| after iteration i = 0, 1, ..; the result is the state after the first iteration with
+ *                  delta[i] <= (uint64)(tol * 2^32), else the state after max_iters iterations with converged = 0.
+ *   posterior      one more E-step at the final state: posterior[r * k + j] = (double)share / 2^32, 0.0 in every other slot.
+ *   per target     units = A[t], est_reads = (double)A[t] / 2^32, cpm = (double)A[t] / (double)(n_placed * ONE) * 1e6 (0 if n_placed == 0).
+ * iter_block: iterations enqueued between two looks of the host at delta (0: 32); the result does not depend on it.  RATTLE_EM_PLAIN=1 in
+ * the environment: one atomic per entry instead of the sorted, merged scatter -- the same bits, for measurement.
+ * params == NULL: ratio 0.95, tol 0.001 read, max_iters 1000, iter_block 32.
+ * Errors, RATTLE_ERR_ARG before the device is looked at, in this order: a NULL pointer; k outside 1..8; a count[r] > k; a filled slot with
+ * a target outside [0, n_targets); ratio not in (0, 1]; tol negative, NaN or >= 2^20; max_iters == 0.  Then RATTLE_ERR_STATE on a context
+ * that is one rank of several.  n_reads == 0 or n_targets == 0: zeros, iterations 0, converged 1.  The context's loaded reads and index
+ * are left as they are.  rattle_hip_kernel_stats: id 10, the ordering and the start as one launch group, each iter_block as one (their
+ * launches are counted one by one), the posterior as one. */
+typedef struct { double ratio, tol; uint32_t max_iters, iter_block; } rattle_abundance_params;
+typedef struct {
+    uint32_t n_targets, n_reads, k, iterations; int converged; uint64_t n_placed;
+    uint64_t *units; double *est_reads, *cpm; uint32_t *compatible_reads;   /* [n_targets] */
+    uint64_t *delta;                                                        /* [iterations] */
+    double *posterior;                                                      /* [n_reads * k] */
+} rattle_abundance;
+int  rattle_hip_abundance(rattle_ctx *ctx, const rattle_candidates *cands, uint32_t n_targets, const rattle_abundance_params *params,
+                          rattle_abundance **out);
+void rattle_hip_abundance_free(rattle_abundance *a);
+
 /* ------------------------------------------------------------------------------------
  * align_pairs: WHERE on its transcript every placed read lies (kernel E, csrc/pair_align.hip); the reference has no counterpart.
  * target_of_read and rev are exactly rattle_assignment::target and ::rev: read r is aligned to target target_of_read[r] (-1: not
@@ -757,7 +791,7 @@ void rattle_hip_debug_consensus_support_free(rattle_debug_support *d);
  * kernel: 0 kmer_extract, 1 bv_filter, 2 pair_score, 3 poa_align, 4 post_msa, 5 the per-read reduction of
  * assign (alg_bytes: the bytes of its records copied to the host), 6 pair_align (kernel E; alg_bytes: the sequence bytes read plus
  * the record bytes written), 7 pair_cigar (kernel F; alg_bytes: see align_cigars), 8 and 9 their three-state forms
- * (align_pairs_scored, align_cigars_scored).  Accumulated since
+ * (align_pairs_scored, align_cigars_scored), 10 the abundance EM (csrc/abundance.hip).  Accumulated since
  * the last reset: total milliseconds, number of launches, algorithmic bytes moved.
  */
 int rattle_hip_kernel_stats(rattle_ctx *ctx, int kernel, double *total_ms, uint64_t *launches, uint64_t *alg_bytes);

@@ -154,6 +154,18 @@ class Candidates(C.Structure):
     _fields_ = [("n", C.c_uint32), ("k", C.c_uint32), ("count", C.POINTER(C.c_uint32))] + [(f, C.POINTER(t)) for f, t in CANDIDATE_FIELDS]
 
 
+# the EM of rattle_hip_abundance: its parameters and its result (per target, per iteration, per slot)
+class AbundanceParams(C.Structure):
+    _fields_ = [("ratio", C.c_double), ("tol", C.c_double), ("max_iters", C.c_uint32), ("iter_block", C.c_uint32)]
+
+
+class Abundance(C.Structure):
+    _fields_ = [("n_targets", C.c_uint32), ("n_reads", C.c_uint32), ("k", C.c_uint32), ("iterations", C.c_uint32), ("converged", C.c_int),
+                ("n_placed", C.c_uint64), ("units", C.POINTER(C.c_uint64)), ("est_reads", C.POINTER(C.c_double)),
+                ("cpm", C.POINTER(C.c_double)), ("compatible_reads", C.POINTER(C.c_uint32)), ("delta", C.POINTER(C.c_uint64)),
+                ("posterior", C.POINTER(C.c_double))]
+
+
 class AlignParams(C.Structure):
     _fields_ = [("max_cells", C.c_uint64), ("pair_chunk", C.c_uint32)]
 
@@ -228,6 +240,8 @@ SIGNATURES = {
     "rattle_hip_assign_reads_top": (C.c_int, [C.c_void_p, _u8p, _u64p, C.c_uint32, _u8p, _u64p, C.c_uint32, C.c_int, _P(AssignParams),
                                               C.c_uint32, _P(_P(Assignment)), _P(_P(Candidates))]),
     "rattle_hip_candidates_free": (None, [_P(Candidates)]),
+    "rattle_hip_abundance": (C.c_int, [C.c_void_p, _P(Candidates), C.c_uint32, _P(AbundanceParams), _P(_P(Abundance))]),
+    "rattle_hip_abundance_free": (None, [_P(Abundance)]),
     "rattle_hip_align_pairs": (C.c_int, [C.c_void_p, _u8p, _u64p, C.c_uint32, _u8p, _u64p, C.c_uint32, _i32p, _u8p, _P(AlignParams),
                                          _P(_P(Alignment))]),
     "rattle_hip_alignment_free": (None, [_P(Alignment)]),

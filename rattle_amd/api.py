@@ -20,6 +20,7 @@ from ._lib import ClusterParams, ClusterSet, Correction, CorrectParams, MsaSet, 
 
 K_KMER, K_FILTER, K_SCORE, K_POA, K_POST, K_ASSIGN, K_ALIGN, K_CIGAR = 0, 1, 2, 3, 4, 5, 6, 7
 K_ALIGN_AFFINE, K_CIGAR_AFFINE = 8, 9          # the three-state forms of kernels E and F (align_pairs / align_cigars with a scoring)
+K_ABUNDANCE = 10                               # the EM of Context.abundance (csrc/abundance.hip)
 ALIGN_MODES = {"local": 0, "read": 1}         # RATTLE_ALIGN_LOCAL, RATTLE_ALIGN_READ
 
 
@@ -660,6 +661,37 @@ class Context:
         self.n = self.k = 0               # the loaded read set was replaced by the last chunk's
         return self._take_assignment(out), self._take_candidates(cands)
 
+    # abundance
+    def abundance(self, cands: dict, n_targets: int, ratio=0.95, tol=1e-3, max_iters=1000, iter_block=0) -> dict:
+        """Per-target read estimates by the integer fixed-point EM over every read's compatible candidates (rattle_hip_abundance).
+        cands: what assign_top returns second, or a hand-built dict with "count" [n], "target" and "score" [n, k].  Slot j of a read is
+        compatible iff score[j] >= ratio * score[0].  Returns a dict: units (uint64, 2^-32 read), est_reads, cpm, compatible_reads
+        [n_targets]; delta [iterations] (uint64 units); posterior [n, k]; iterations, converged, n_placed.  The same bits on every run,
+        whatever iter_block (iterations enqueued between two looks of the host; 0: 32) is."""
+        count = np.ascontiguousarray(cands["count"], np.uint32)
+        target = np.ascontiguousarray(cands["target"], np.int32)
+        score = np.ascontiguousarray(cands["score"], np.float64)
+        n, k = target.shape if target.ndim == 2 else (len(count), 0)
+        if target.ndim != 2 or score.shape != target.shape or len(count) != n:
+            raise ValueError("cands: count [n], target and score [n, k]")
+        Cd = _lib.Candidates()
+        Cd.n, Cd.k = n, k
+        Cd.count = _ptr(count, C.c_uint32); Cd.target = _ptr(target, C.c_int32); Cd.score = _ptr(score, C.c_double)
+        P = _lib.AbundanceParams(float(ratio), float(tol), int(max_iters), int(iter_block))
+        out = C.POINTER(_lib.Abundance)()
+        check(self.lib.rattle_hip_abundance(self.h, C.byref(Cd), int(n_targets), C.byref(P), C.byref(out)))
+        R = out.contents
+        nt, it = int(R.n_targets), int(R.iterations)
+
+        def arr(ptr, m):
+            return np.ctypeslib.as_array(ptr, (max(m, 1),))[:m].copy()
+
+        res = {"units": arr(R.units, nt), "est_reads": arr(R.est_reads, nt), "cpm": arr(R.cpm, nt), "compatible_reads": arr(R.compatible_reads, nt),
+               "delta": arr(R.delta, it), "posterior": arr(R.posterior, n * k).reshape(n, k), "iterations": it, "converged": int(R.converged),
+               "n_placed": int(R.n_placed)}
+        self.lib.rattle_hip_abundance_free(out)
+        return res
+
     @staticmethod
     def _scoring(scoring):
         """(match, mismatch, gap_open, gap_extend), four positive magnitudes, as the library's struct; the library checks the limits"""
@@ -1076,24 +1108,52 @@ def target_counts_tsv(target_names: Sequence[bytes], target_lengths: Sequence[in
         b"%s\t%d\t%d\t%d\n" % (n, int(l), int(reads[i]), int(uniq[i])) for i, (n, l) in enumerate(zip(target_names, target_lengths)))
 
 
-def _assign_submitted(ctx, reads, targets, k, t_s, t_v, bv_threshold, is_rna, count_pass, target_batch, read_chunk, secondary):
-    """the clean reads through assign (secondary == 0) or assign_top, spread back over all reads: (record, candidates or None)"""
+def abundance_tsv(target_names: Sequence[bytes], target_lengths: Sequence[int], rec: dict, ab: dict) -> bytes:
+    """abundance.tsv as `rattle assign --abundance` writes it: a header line, then one line per target in file order: target, length,
+    reads and unique_reads (the columns of target_counts.tsv), compatible_reads, est_reads, cpm (Context.abundance); doubles as %.17g."""
+    t = np.asarray(rec["target"], np.int64)
+    hit = t >= 0
+    reads = np.bincount(t[hit], minlength=len(target_names))
+    uniq = np.bincount(t[hit & (np.asarray(rec["second_score"]) < 0)], minlength=len(target_names))
+    return b"target\tlength\treads\tunique_reads\tcompatible_reads\test_reads\tcpm\n" + b"".join(
+        b"%s\t%d\t%d\t%d\t%d\t%s\t%s\n" % (n, int(l), int(reads[i]), int(uniq[i]), int(ab["compatible_reads"][i]),
+                                        ("%.17g" % ab["est_reads"][i]).encode(), ("%.17g" % ab["cpm"][i]).encode())
+        for i, (n, l) in enumerate(zip(target_names, target_lengths)))
+
+
+def _abundance_text(ctx, target_headers, targets, rec, cands8, abundance):
+    """abundance = (ratio, tol, max_iters): the EM over the 8-slot list of all reads, as the bytes of abundance.tsv"""
+    ab = ctx.abundance(cands8, len(targets), *abundance)
+    return abundance_tsv([_first_token(h) for h in target_headers], [len(s) for s in targets], rec, ab)
+
+
+def _assign_submitted(ctx, reads, targets, k, t_s, t_v, bv_threshold, is_rna, count_pass, target_batch, read_chunk, secondary, abundance=False):
+    """the clean reads through assign (secondary == 0) or assign_top, spread back over all reads: (record, candidates or None, None).
+    abundance: the list is made with 8 slots whatever secondary is and comes third; the second is its first secondary + 1 slots (the
+    list has the prefix property: they are what the shorter list holds), None without secondary."""
     if not 0 <= int(secondary) <= 7:
         raise ValueError("secondary is in 0..7")
     sent = [i for i, s in enumerate(reads) if not s.translate(None, b"ACGTU")]
     rec = unassigned_records(len(reads))
     cands = None
-    if secondary:
-        got, part = ctx.assign_top(targets, [reads[i] for i in sent], secondary + 1, k, t_s, t_v, bv_threshold, False, is_rna, target_batch,
+    top = 8 if abundance else secondary + 1
+    if secondary or abundance:
+        got, part = ctx.assign_top(targets, [reads[i] for i in sent], top, k, t_s, t_v, bv_threshold, False, is_rna, target_batch,
                                    read_chunk, count_pass)
-        cands = unused_candidates(len(reads), secondary + 1)
+        cands = unused_candidates(len(reads), top)
         for f in cands:
             cands[f][sent] = part[f]
     else:
         got = ctx.assign(targets, [reads[i] for i in sent], k, t_s, t_v, bv_threshold, False, is_rna, target_batch, read_chunk, count_pass)
     for f in rec:
         rec[f][sent] = got[f]
-    return rec, cands
+    if not abundance:
+        return rec, cands, None
+    first = None
+    if secondary:
+        first = {f: np.ascontiguousarray(v[:, :secondary + 1]) for f, v in cands.items() if f != "count"}
+        first["count"] = np.minimum(cands["count"], secondary + 1).astype(np.uint32)
+    return rec, first, cands
 
 
 def unused_candidates(n: int, top: int) -> dict:
@@ -1121,16 +1181,23 @@ def candidates_tsv(read_names: Sequence[bytes], target_names: Sequence[bytes], c
 
 def assign_command(ctx: Context, read_headers: Sequence[bytes], reads: Sequence[bytes], target_headers: Sequence[bytes],
                    targets: Sequence[bytes], *, k=10, t_s=0.2, t_v=1000000.0, bv_threshold=0.4, is_rna=False, count_pass="auto",
-                   target_batch=0, read_chunk=0, secondary=0):
+                   target_batch=0, read_chunk=0, secondary=0, abundance=False, abundance_ratio=0.95, abundance_tol=1e-3, abundance_iters=1000):
     """`rattle assign -i reads -x transcripts` after input parsing: every record of both files takes part, in file order.  Returns the
     bytes of assignments.tsv and of target_counts.tsv.  A read with a base other than A, C, G, T, U is not compared: unassigned.
     secondary=N (1..7) is `--secondary N`: the first two are unchanged and the bytes of candidates.tsv (candidates_tsv, N + 1 slots per
-    read) come third."""
-    rec, cands = _assign_submitted(ctx, reads, targets, k, t_s, t_v, bv_threshold, is_rna, count_pass, target_batch, read_chunk, secondary)
+    read) come third.  abundance=True is `--abundance`: the candidate list is made with 8 slots whatever secondary is, the files above
+    do not change, and the bytes of abundance.tsv (abundance_tsv; Context.abundance with abundance_ratio, abundance_tol, abundance_iters)
+    come last."""
+    rec, cands, all8 = _assign_submitted(ctx, reads, targets, k, t_s, t_v, bv_threshold, is_rna, count_pass, target_batch, read_chunk, secondary,
+                                          abundance)
     tn = [_first_token(h) for h in target_headers]
     rn = [_first_token(h) for h in read_headers]
     out = (assignments_tsv(rn, tn, rec), target_counts_tsv(tn, [len(s) for s in targets], rec))
-    return out if cands is None else out + (candidates_tsv(rn, tn, cands),)
+    if cands is not None:
+        out = out + (candidates_tsv(rn, tn, cands),)
+    if abundance:
+        out = out + (_abundance_text(ctx, target_headers, targets, rec, all8, (abundance_ratio, abundance_tol, abundance_iters)),)
+    return out
 
 
 _CIGAR_LETTER = {1: b"I", 2: b"D", 7: b"=", 8: b"X"}
@@ -1207,16 +1274,20 @@ def align_ranks(ctx: Context, targets: Sequence[bytes], reads: Sequence[bytes], 
 def assign_paf_command(ctx: Context, read_headers: Sequence[bytes], reads: Sequence[bytes], target_headers: Sequence[bytes],
                        targets: Sequence[bytes], *, k=10, t_s=0.2, t_v=1000000.0, bv_threshold=0.4, is_rna=False, count_pass="auto",
                        target_batch=0, read_chunk=0, max_cells=0, pair_chunk=0, cigar=False, scoring=None, secondary=0,
-                       end_to_end=False):
+                       end_to_end=False, abundance=False, abundance_ratio=0.95, abundance_tol=1e-3, abundance_iters=1000):
     """`rattle assign --paf`: assign_command, then every placed read aligned to its transcript (Context.align_pairs).  Returns the bytes
     of assignments.tsv, target_counts.tsv and alignments.paf; the first two are what assign_command returns.  cigar=True is
     `--paf --cigar`: Context.align_cigars, and a cg:Z: tag on every line.  scoring=(m, x, o, e) is `--paf-scoring m,x,o,e`: affine gaps
     (Context.align_pairs); None is the linear default.  secondary=N (1..7) is `--secondary N`: every read is aligned to each of its
     N + 1 candidates (align_ranks), alignments.paf is the ranked one (paf_ranked_text) and the bytes of candidates.tsv come fourth.
     end_to_end=True is `--paf-end-to-end`: every alignment, of every rank, in mode "read" -- the whole read on every line; the tables
-    do not change."""
+    do not change.  abundance=True is `--abundance`, as for assign_command: the bytes of abundance.tsv come last, nothing else changes."""
     mode = "read" if end_to_end else "local"
-    rec, cands = _assign_submitted(ctx, reads, targets, k, t_s, t_v, bv_threshold, is_rna, count_pass, target_batch, read_chunk, secondary)
+    rec, cands, all8 = _assign_submitted(ctx, reads, targets, k, t_s, t_v, bv_threshold, is_rna, count_pass, target_batch, read_chunk, secondary,
+                                          abundance)
+    last = ()
+    if abundance:
+        last = (_abundance_text(ctx, target_headers, targets, rec, all8, (abundance_ratio, abundance_tol, abundance_iters)),)
     tn = [_first_token(h) for h in target_headers]
     rn = [_first_token(h) for h in read_headers]
     tl = [len(s) for s in targets]
@@ -1224,11 +1295,11 @@ def assign_paf_command(ctx: Context, read_headers: Sequence[bytes], reads: Seque
     if cands is not None:
         alns, cgs = align_ranks(ctx, targets, reads, cands, max_cells, pair_chunk, cigar, scoring, mode)
         return (assignments_tsv(rn, tn, rec), target_counts_tsv(tn, tl, rec), paf_ranked_text(rn, rl, tn, tl, cands, alns, cgs),
-                candidates_tsv(rn, tn, cands))
+                candidates_tsv(rn, tn, cands)) + last
     cigars = None
     if cigar:
         aln, offsets, ops = ctx.align_cigars(targets, reads, rec["target"], rec["rev"], max_cells, pair_chunk, scoring, mode)
         cigars = (offsets, ops)
     else:
         aln = ctx.align_pairs(targets, reads, rec["target"], rec["rev"], max_cells, pair_chunk, scoring, mode)
-    return (assignments_tsv(rn, tn, rec), target_counts_tsv(tn, tl, rec), paf_text(rn, rl, tn, tl, rec, aln, cigars))
+    return (assignments_tsv(rn, tn, rec), target_counts_tsv(tn, tl, rec), paf_text(rn, rl, tn, tl, rec, aln, cigars)) + last

@@ -674,6 +674,72 @@ void rattle_hip_candidates_free(rattle_candidates *c) {
     free(c);
 }
 
+// ---- abundance (abundance.hip) ----------------------------------------------------------------------------------------------
+// the checks in the order the header promises, the compatibility mask on the host (the rule's own double expression; this file is built
+// with -ffp-contract=off), the EM on the device, the per-target doubles from its integers
+int rattle_hip_abundance(rattle_ctx *c, const rattle_candidates *cands, uint32_t nt, const rattle_abundance_params *params, rattle_abundance **out) {
+    if (out) *out = nullptr;
+    if (!c || !cands || !out) { set_error("null argument"); return RATTLE_ERR_ARG; }
+    const uint32_t n = cands->n, k = cands->k;
+    if (n && (!cands->count || !cands->target || !cands->score)) { set_error("null argument"); return RATTLE_ERR_ARG; }
+    if (k < 1 || k > 8) { set_error("abundance: k, the slots per read, must be in [1,8]"); return RATTLE_ERR_ARG; }
+    for (uint32_t r = 0; r < n; ++r)
+        if (cands->count[r] > k) { set_error("abundance: count of read " + std::to_string(r) + " exceeds k"); return RATTLE_ERR_ARG; }
+    for (uint32_t r = 0; r < n; ++r)
+        for (uint32_t j = 0; j < cands->count[r]; ++j) {
+            const int32_t t = cands->target[(size_t)r * k + j];
+            if (t < 0 || (uint32_t)t >= nt) {
+                set_error("abundance: slot " + std::to_string(j) + " of read " + std::to_string(r) + " names target " + std::to_string(t) + " of " + std::to_string(nt));
+                return RATTLE_ERR_ARG;
+            }
+        }
+    const rattle_abundance_params dflt = {0.95, 1e-3, 1000, 0};
+    const rattle_abundance_params P = params ? *params : dflt;
+    if (!(P.ratio > 0.0 && P.ratio <= 1.0)) { set_error("abundance: ratio must be in (0, 1]"); return RATTLE_ERR_ARG; }
+    if (!(P.tol >= 0.0 && P.tol < 1048576.0)) { set_error("abundance: tol must be in [0, 2^20) reads"); return RATTLE_ERR_ARG; }
+    if (P.max_iters == 0) { set_error("abundance: max_iters must be at least 1"); return RATTLE_ERR_ARG; }
+    if (c->xchg.nranks > 1) {
+        set_error("abundance is not available on a context that is one rank of several: sharded jobs are not built, estimate on one device");
+        return RATTLE_ERR_STATE;
+    }
+    RT_TRY(use_device(c));
+    phase_timer T_all("abundance: total");
+    rattle_abundance *R = (rattle_abundance *)calloc(1, sizeof(rattle_abundance));
+    const size_t mt = std::max<size_t>(1, nt), ms = std::max<size_t>(1, (size_t)n * k);
+    R->n_targets = nt; R->n_reads = n; R->k = k; R->converged = 1;
+    R->units = (uint64_t *)calloc(mt, 8); R->est_reads = (double *)calloc(mt, 8); R->cpm = (double *)calloc(mt, 8);
+    R->compatible_reads = (uint32_t *)calloc(mt, 4); R->posterior = (double *)calloc(ms, 8);
+    std::vector<uint64_t> deltas;
+    if (n && nt) {
+        std::vector<int32_t> tgt((size_t)n * k, -1);
+        for (uint32_t r = 0; r < n; ++r) {
+            const size_t s = (size_t)r * k;
+            if (cands->count[r] == 0) continue;
+            ++R->n_placed;
+            const double least = P.ratio * cands->score[s];
+            tgt[s] = cands->target[s];
+            for (uint32_t j = 1; j < cands->count[r]; ++j) if (cands->score[s + j] >= least) tgt[s + j] = cands->target[s + j];
+        }
+        const int rc = abundance_run(c, tgt.data(), n, k, nt, (unsigned long long)(P.tol * 4294967296.0), P.max_iters, P.iter_block, R, deltas);
+        if (rc != 0) { rattle_hip_abundance_free(R); return rc; }
+    }
+    R->delta = (uint64_t *)calloc(std::max<size_t>(1, deltas.size()), 8);
+    for (size_t i = 0; i < deltas.size(); ++i) R->delta[i] = deltas[i];
+    const double mass = (double)(R->n_placed << 32);
+    for (uint32_t t = 0; t < nt; ++t) {
+        R->est_reads[t] = (double)R->units[t] / 4294967296.0;
+        R->cpm[t] = R->n_placed ? (double)R->units[t] / mass * 1e6 : 0.0;
+    }
+    *out = R;
+    return 0;
+}
+
+void rattle_hip_abundance_free(rattle_abundance *a) {
+    if (!a) return;
+    free(a->units); free(a->est_reads); free(a->cpm); free(a->compatible_reads); free(a->delta); free(a->posterior);
+    free(a);
+}
+
 void rattle_hip_assignment_free(rattle_assignment *a) {
     if (!a) return;
     free(a->target); free(a->rev); free(a->bases); free(a->hc_bases); free(a->min_len); free(a->score); free(a->variance);

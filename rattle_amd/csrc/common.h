@@ -129,7 +129,7 @@ struct hbuf {
     }
 };
 
-enum { K_KMER = 0, K_FILTER = 1, K_SCORE = 2, K_POA = 3, K_POST = 4, K_ASSIGN = 5, K_ALIGN = 6, K_CIGAR = 7, K_ALIGN_AFFINE = 8, K_CIGAR_AFFINE = 9, K_COUNT = 10 };
+enum { K_KMER = 0, K_FILTER = 1, K_SCORE = 2, K_POA = 3, K_POST = 4, K_ASSIGN = 5, K_ALIGN = 6, K_CIGAR = 7, K_ALIGN_AFFINE = 8, K_CIGAR_AFFINE = 9, K_ABUNDANCE = 10, K_COUNT = 11 };
 
 struct kstat {
     double ms = 0;
@@ -561,6 +561,11 @@ struct align_pair {                     // one submitted pair: where its sequenc
 int align_pairs_run(rattle_ctx *ctx, const uint8_t *tseq, const uint64_t *toff, uint32_t n_targets, const uint8_t *rseq, const uint64_t *roff,
                     uint32_t n_reads, const int32_t *target, const uint8_t *rev, const rattle_align_params *P, rattle_alignment *A,
                     cigar_run *cigars = nullptr, const rattle_align_scoring *scoring = nullptr, int mode = RATTLE_ALIGN_LOCAL);
+// abundance.hip : the EM over the compatible targets tgt[r * k + j] (-1: slot j of read r takes no part; a read whose slot 0 is -1 takes
+// none), n, nt >= 1, targets checked by the caller.  Fills R->iterations, converged, units, compatible_reads and posterior (allocated by
+// the caller) and `deltas`, one entry per iteration run.
+int abundance_run(rattle_ctx *ctx, const int32_t *h_tgt, uint32_t n, uint32_t k, uint32_t nt, unsigned long long tol_units, uint32_t max_iters,
+                  uint32_t iter_block, rattle_abundance *R, std::vector<uint64_t> &deltas);
 constexpr uint32_t AL_REC_WORDS = 10;   // a pair's record on the device: status, score, q_start, q_end, t_start, t_end, matches, mismatches, q_gap, t_gap
 
 // correct_driver.hip

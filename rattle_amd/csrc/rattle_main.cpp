@@ -27,6 +27,7 @@
 #include <vector>
 
 #include <chrono>
+#include <cmath>
 
 #include "../../include/rattle_hip.h"
 
@@ -770,6 +771,8 @@ int mode_cluster(int argc, char **argv) {
 // G, T, U is not compared and comes out unassigned (`cluster` skips such reads).  --paf: every placed read is then aligned to its transcript
 // (include/rattle_hip.h, "align_pairs") and alignments.paf appears beside the two tables.  --secondary N: the N next-best transcripts of
 // every read beside its best (include/rattle_hip.h, "The candidate list") as candidates.tsv, and with --paf each of them aligned.
+// --abundance: the list is made with 8 slots, the EM of include/rattle_hip.h, "abundance", runs over it, and abundance.tsv appears; the
+// other writers see the first --secondary + 1 slots, which are what the shorter list holds.
 struct assign_job {
     args_t a;
     int k = 10;
@@ -789,7 +792,10 @@ struct assign_job {
     bool want_scoring = false;                    // --paf-scoring m,x,o,e: affine gaps, the three-state kernels
     rattle_align_scoring AS;
     bool want_ends = false;                       // --paf-end-to-end: the whole read on every line (RATTLE_ALIGN_READ)
-    std::string text, counts, paf, cand;         // assignments.tsv, target_counts.tsv, alignments.paf (--paf), candidates.tsv (--secondary)
+    bool want_abundance = false;                  // --abundance: the candidate list with 8 slots, the EM over it, abundance.tsv
+    rattle_abundance_params EP;
+    rattle_abundance *E = nullptr;
+    std::string text, counts, paf, cand, abund;   // assignments.tsv, target_counts.tsv, alignments.paf (--paf), candidates.tsv (--secondary), abundance.tsv (--abundance)
     void options(int argc, char **argv) {
         a = parse(argc, argv, {
             {"help", {"-h", "--help"}, false}, {"input", {"-i", "--input"}, true}, {"targets", {"-x", "--transcripts"}, true},
@@ -798,8 +804,10 @@ struct assign_job {
             {"count-pass", {"--count-pass"}, true}, {"device", {"--device"}, true}, {"devices", {"--devices"}, true},
             {"target-batch", {"--target-batch"}, true}, {"read-chunk", {"--read-chunk"}, true}, {"paf", {"--paf"}, false},
             {"paf-max-cells", {"--paf-max-cells"}, true}, {"cigar", {"--cigar"}, false}, {"paf-scoring", {"--paf-scoring"}, true},
-            {"secondary", {"--secondary"}, true}, {"paf-end-to-end", {"--paf-end-to-end"}, false}});
-        const char *usage = "rattle assign -i reads.fq -x transcripts.fq [-o dir] [-k 10] [-s 0.2] [-v 1000000] [-B 0.4] [--rna] [--device n] [--paf [--cigar]] [--secondary n]\n"
+            {"secondary", {"--secondary"}, true}, {"paf-end-to-end", {"--paf-end-to-end"}, false}, {"abundance", {"--abundance"}, false},
+            {"abundance-ratio", {"--abundance-ratio"}, true}, {"abundance-tol", {"--abundance-tol"}, true},
+            {"abundance-iters", {"--abundance-iters"}, true}});
+        const char *usage = "rattle assign -i reads.fq -x transcripts.fq [-o dir] [-k 10] [-s 0.2] [-v 1000000] [-B 0.4] [--rna] [--device n] [--paf [--cigar]] [--secondary n] [--abundance]\n"
                             "  places every read of -i on the transcript of -x that accepts it with the best score (the comparison `cluster` joins\n"
                             "  reads by, the transcript in the seed's role) and writes assignments.tsv (one line per read: target, strand, score,\n"
                             "  second_score, n_accepted, bases, hc_bases, min_len, variance) and target_counts.tsv (reads per transcript)\n"
@@ -819,7 +827,15 @@ struct assign_job {
                             "  --secondary n                         n in 1..7: also write candidates.tsv, the best transcript of every read and its n next-best\n"
                             "                                        (one line per read and rank: read, rank, target, strand, score, bases, hc_bases, min_len,\n"
                             "                                        variance); with --paf every one of them is aligned, and each line of alignments.paf carries\n"
-                            "                                        tp:A:P (rank 0) or tp:A:S and rk:i:<rank>.  The other two files do not change\n";
+                            "                                        tp:A:P (rank 0) or tp:A:S and rk:i:<rank>.  The other two files do not change\n"
+                            "  --abundance                           also write abundance.tsv, one line per transcript: target, length, reads, unique_reads,\n"
+                            "                                        compatible_reads, est_reads, cpm.  est_reads shares every read among the transcripts that\n"
+                            "                                        accept it nearly as well as its best one (an EM over its 8 best transcripts, on the device,\n"
+                            "                                        in integer fixed point: the same bits on every run).  The other files do not change\n"
+                            "  --abundance-ratio f                   with --abundance: a transcript is compatible with a read if its score reaches f times the\n"
+                            "                                        read's best score; f in (0, 1] (default 0.95)\n"
+                            "  --abundance-tol f                     with --abundance: stop when no estimate moved by more than f reads; 0 <= f < 2^20 (default 0.001)\n"
+                            "  --abundance-iters n                   with --abundance: at most n iterations, n >= 1 (default 1000)\n";
         if (a.has("help")) { std::cerr << usage; exit(EXIT_SUCCESS); }
         if (!a.has("input")) die("ERROR: No input file provided (-i reads)");
         if (!a.has("targets")) die("ERROR: No transcript file provided (-x transcripts)");
@@ -857,6 +873,27 @@ struct assign_job {
             if (v.size() != 1 || v[0] < '1' || v[0] > '7') die("\nError: --secondary takes a number of further transcripts per read in 1..7\n");
             secondary = (uint32_t)(v[0] - '0');
         }
+        want_abundance = a.has("abundance");
+        for (const char *f : {"abundance-ratio", "abundance-tol", "abundance-iters"})
+            if (a.has(f) && !want_abundance) die(std::string("\nError: --") + f + " needs --abundance\n");
+        EP.ratio = 0.95; EP.tol = 1e-3; EP.max_iters = 1000; EP.iter_block = 0;
+        if (want_abundance) {
+            // the number an option holds; NaN, which every limit below refuses, for anything else
+            auto number = [&](const char *f, double fallback) {
+                if (!a.has(f)) return fallback;
+                const std::string v = a.str(f, "");
+                char *end = nullptr;
+                const double x = strtod(v.c_str(), &end);
+                return (v.empty() || *end) ? std::nan("") : x;
+            };
+            EP.ratio = number("abundance-ratio", 0.95);
+            if (!(EP.ratio > 0.0 && EP.ratio <= 1.0)) die("\nError: --abundance-ratio takes a number in (0, 1]\n");
+            EP.tol = number("abundance-tol", 1e-3);
+            if (!(EP.tol >= 0.0 && EP.tol < 1048576.0)) die("\nError: --abundance-tol takes a number of reads in [0, 2^20)\n");
+            const double it = number("abundance-iters", 1000);
+            if (!(it >= 1.0 && it <= 4294967295.0) || it != std::floor(it)) die("\nError: --abundance-iters takes a whole number of iterations, at least 1\n");
+            EP.max_iters = (uint32_t)it;
+        }
         memset(&AP, 0, sizeof AP);
         AP.max_cells = std::stoull(a.str("paf-max-cells", "0"));
         P.target_batch = (uint32_t)std::max(0, a.i("target-batch", 0)); P.read_chunk = (uint32_t)std::max(0, a.i("read-chunk", 0));
@@ -881,9 +918,20 @@ struct assign_job {
     }
     void run() {
         cli_timer t("library: assign");
-        if (secondary) chk(rattle_hip_assign_reads_top(team.ctx[0], xcat.data(), xoff.data(), (uint32_t)xid.size(), rcat.data(), roff.data(), (uint32_t)rid.size(), k, &P, secondary + 1, &A, &C));
+        if (secondary || want_abundance) chk(rattle_hip_assign_reads_top(team.ctx[0], xcat.data(), xoff.data(), (uint32_t)xid.size(), rcat.data(), roff.data(), (uint32_t)rid.size(), k, &P, want_abundance ? 8 : secondary + 1, &A, &C));
         else chk(rattle_hip_assign_reads(team.ctx[0], xcat.data(), xoff.data(), (uint32_t)xid.size(), rcat.data(), roff.data(), (uint32_t)rid.size(), k, &P, &A));
     }
+    // --abundance: the EM over the 8-slot list of the submitted reads (the reads that were not submitted have no candidate)
+    void estimate() {
+        cli_timer t("library: abundance");
+        chk(rattle_hip_abundance(team.ctx[0], C, (uint32_t)xid.size(), &EP, &E));
+        uint64_t full = 0;
+        for (uint32_t r = 0; r < C->n; ++r) full += C->count[r] == C->k;
+        std::cerr << "abundance: " << E->iterations << " iterations" << (E->converged ? "" : ", not converged") << "; " << full << " reads fill all "
+                  << C->k << " candidate slots (further transcripts may accept them)" << std::endl;
+    }
+    // the ranks the writers of --secondary see: the list holds 8 under --abundance, and its first ranks are what the shorter list holds
+    uint32_t ranks() const { return std::min(C->k, secondary + 1); }
     // the submitted reads on target[r] / rev[r] each (-1: not aligned): one call of the library
     void align_on(const int32_t *target, const uint8_t *rev, rattle_alignment **L, rattle_cigars **G) {
         if (want_ends && want_cigar) chk(rattle_hip_align_cigars_mode(team.ctx[0], xcat.data(), xoff.data(), (uint32_t)xid.size(), rcat.data(), roff.data(), (uint32_t)rid.size(), target, rev, &AP, want_scoring ? &AS : nullptr, RATTLE_ALIGN_READ, L, G));
@@ -934,7 +982,7 @@ struct assign_job {
         std::vector<rattle_cigars *> G;
         std::vector<int32_t> target(std::max<uint32_t>(1, n));
         std::vector<uint8_t> rev(std::max<uint32_t>(1, n));
-        for (uint32_t j = 0; j < K; ++j) {
+        for (uint32_t j = 0; j < ranks(); ++j) {
             bool any = false;
             for (uint32_t r = 0; r < n; ++r) { target[r] = C->target[(size_t)r * K + j]; rev[r] = C->rev[(size_t)r * K + j]; any = any || C->count[r] > j; }
             if (!any) break;
@@ -943,7 +991,7 @@ struct assign_job {
         }
         uint64_t skipped = 0;
         for (uint32_t at = 0; at < n; ++at)
-            for (uint32_t j = 0; j < C->count[at] && j < L.size(); ++j) {
+            for (uint32_t j = 0; j < C->count[at] && j < L.size(); ++j) {                 // (L.size() <= ranks())
                 skipped += L[j]->status[at] == 2;
                 if (L[j]->status[at] != 0) continue;
                 paf_line(at, (uint32_t)C->target[(size_t)at * K + j], C->rev[(size_t)at * K + j] != 0, L[j], G[j],
@@ -956,14 +1004,12 @@ struct assign_job {
     void format_candidates() {
         cand = "read\trank\ttarget\tstrand\tscore\tbases\thc_bases\tmin_len\tvariance\n";
         for (uint32_t at = 0; at < C->n; ++at)
-            for (uint32_t j = 0; j < C->count[at]; ++j) {
+            for (uint32_t j = 0; j < C->count[at] && j < ranks(); ++j) {
                 const size_t s = (size_t)at * C->k + j;
                 cand += record_name(R.header[rid[at]]) + "\t" + std::to_string(j) + "\t" + record_name(X.header[C->target[s]]) + "\t" + (C->rev[s] ? "-" : "+") + "\t" +
                         g17(C->score[s]) + "\t" + std::to_string(C->bases[s]) + "\t" + std::to_string(C->hc_bases[s]) + "\t" + std::to_string(C->min_len[s]) + "\t" +
                         g17(C->variance[s]) + "\n";
             }
-        rattle_hip_candidates_free(C);
-        C = nullptr;
     }
     // one line per read of -i, the reads that were not submitted included; then one line per transcript
     void format() {
@@ -981,15 +1027,23 @@ struct assign_job {
             if (sent) ++at;
         }
         rattle_hip_assignment_free(A);
+        rattle_hip_candidates_free(C);
         counts = "target\tlength\treads\tunique_reads\n";
         for (size_t t = 0; t < X.n(); ++t)
             counts += record_name(X.header[t]) + "\t" + std::to_string(X.seq[t].n) + "\t" + std::to_string(n_best[t]) + "\t" + std::to_string(n_unique[t]) + "\n";
+        if (!want_abundance) return;
+        abund = "target\tlength\treads\tunique_reads\tcompatible_reads\test_reads\tcpm\n";
+        for (size_t t = 0; t < X.n(); ++t)
+            abund += record_name(X.header[t]) + "\t" + std::to_string(X.seq[t].n) + "\t" + std::to_string(n_best[t]) + "\t" + std::to_string(n_unique[t]) + "\t" +
+                     std::to_string(E->compatible_reads[t]) + "\t" + g17(E->est_reads[t]) + "\t" + g17(E->cpm[t]) + "\n";
+        rattle_hip_abundance_free(E);
     }
     void write() {
         write_text(outdir + "/assignments.tsv", text);
         write_text(outdir + "/target_counts.tsv", counts);
         if (want_paf) write_text(outdir + "/alignments.paf", paf);
         if (secondary) write_text(outdir + "/candidates.tsv", cand);
+        if (want_abundance) write_text(outdir + "/abundance.tsv", abund);
         team.close();
         std::cerr << "Done" << std::endl;
     }
@@ -1000,6 +1054,7 @@ int mode_assign(int argc, char **argv) {
     J.options(argc, argv);
     J.read_input();
     J.run();
+    if (J.want_abundance) J.estimate();
     if (J.want_paf) { if (J.secondary) J.align_ranks(); else J.align(); }
     if (J.secondary) J.format_candidates();
     J.format();
