@@ -727,6 +727,11 @@ class Context:
     def align_pairs_packed(self, tcat: np.ndarray, toff: np.ndarray, rcat: np.ndarray, roff: np.ndarray, target_of_read, rev,
                            max_cells=0, pair_chunk=0, scoring=None, mode="local") -> dict:
         """align_pairs() on packed arrays (pack_reads)"""
+        return self._align_packed(False, tcat, toff, rcat, roff, target_of_read, rev, max_cells, pair_chunk, scoring, mode)
+
+    def _align_packed(self, cigar: bool, tcat, toff, rcat, roff, target_of_read, rev, max_cells, pair_chunk, scoring, mode):
+        """The body of align_pairs_packed and (cigar) align_cigars_packed.  mode "local" goes to the calls without a mode -- the plain one
+        for scoring None, the _scored one else --, any other mode to the _mode call."""
         M = self._align_mode(mode)
         P = _lib.AlignParams(int(max_cells), int(pair_chunk))
         n = len(roff) - 1
@@ -734,22 +739,29 @@ class Context:
         r = np.ascontiguousarray(rev, np.uint8)
         if len(t) != n or len(r) != n:
             raise ValueError("target_of_read and rev need one entry per read")
-        out = C.POINTER(_lib.Alignment)()
+        out, cg = C.POINTER(_lib.Alignment)(), C.POINTER(_lib.Cigars)()
         args = (self.h, _ptr(tcat, C.c_uint8) if len(tcat) else None, _ptr(toff, C.c_uint64), len(toff) - 1,
                 _ptr(rcat, C.c_uint8) if len(rcat) else None, _ptr(roff, C.c_uint64), n, _ptr(t, C.c_int32) if n else None,
                 _ptr(r, C.c_uint8) if n else None, C.byref(P))
+        outs = (C.byref(out), C.byref(cg)) if cigar else (C.byref(out),)
+        call = "rattle_hip_align_cigars" if cigar else "rattle_hip_align_pairs"
+        S = None if scoring is None else self._scoring(scoring)
         if M is not None:
-            S = None if scoring is None else self._scoring(scoring)
-            check(self.lib.rattle_hip_align_pairs_mode(*args, None if S is None else C.byref(S), M, C.byref(out)))
-        elif scoring is None:
-            check(self.lib.rattle_hip_align_pairs(*args, C.byref(out)))
+            check(getattr(self.lib, call + "_mode")(*args, None if S is None else C.byref(S), M, *outs))
+        elif S is None:
+            check(getattr(self.lib, call)(*args, *outs))
         else:
-            S = self._scoring(scoring)
-            check(self.lib.rattle_hip_align_pairs_scored(*args, C.byref(S), C.byref(out)))
+            check(getattr(self.lib, call + "_scored")(*args, C.byref(S), *outs))
         m = int(out.contents.n)
         res = {f: np.ctypeslib.as_array(getattr(out.contents, f), (max(m, 1),))[:m].copy() for f, _ in _lib.ALIGN_FIELDS}
         self.lib.rattle_hip_alignment_free(out)
-        return res
+        if not cigar:
+            return res
+        offsets = np.ctypeslib.as_array(cg.contents.offset, (m + 1,)).copy()
+        total = int(offsets[m])
+        ops = np.ctypeslib.as_array(cg.contents.ops, (max(total, 1),))[:total].copy()
+        self.lib.rattle_hip_cigars_free(cg)
+        return res, offsets, ops
 
     def align_cigars(self, targets: Sequence[bytes], reads: Sequence[bytes], target_of_read, rev, max_cells=0, pair_chunk=0, scoring=None,
                      mode="local"):
@@ -766,34 +778,7 @@ class Context:
     def align_cigars_packed(self, tcat: np.ndarray, toff: np.ndarray, rcat: np.ndarray, roff: np.ndarray, target_of_read, rev,
                             max_cells=0, pair_chunk=0, scoring=None, mode="local"):
         """align_cigars() on packed arrays (pack_reads)"""
-        M = self._align_mode(mode)
-        P = _lib.AlignParams(int(max_cells), int(pair_chunk))
-        n = len(roff) - 1
-        t = np.ascontiguousarray(target_of_read, np.int32)
-        r = np.ascontiguousarray(rev, np.uint8)
-        if len(t) != n or len(r) != n:
-            raise ValueError("target_of_read and rev need one entry per read")
-        out = C.POINTER(_lib.Alignment)()
-        cg = C.POINTER(_lib.Cigars)()
-        args = (self.h, _ptr(tcat, C.c_uint8) if len(tcat) else None, _ptr(toff, C.c_uint64), len(toff) - 1,
-                _ptr(rcat, C.c_uint8) if len(rcat) else None, _ptr(roff, C.c_uint64), n, _ptr(t, C.c_int32) if n else None,
-                _ptr(r, C.c_uint8) if n else None, C.byref(P))
-        if M is not None:
-            S = None if scoring is None else self._scoring(scoring)
-            check(self.lib.rattle_hip_align_cigars_mode(*args, None if S is None else C.byref(S), M, C.byref(out), C.byref(cg)))
-        elif scoring is None:
-            check(self.lib.rattle_hip_align_cigars(*args, C.byref(out), C.byref(cg)))
-        else:
-            S = self._scoring(scoring)
-            check(self.lib.rattle_hip_align_cigars_scored(*args, C.byref(S), C.byref(out), C.byref(cg)))
-        m = int(out.contents.n)
-        res = {f: np.ctypeslib.as_array(getattr(out.contents, f), (max(m, 1),))[:m].copy() for f, _ in _lib.ALIGN_FIELDS}
-        offsets = np.ctypeslib.as_array(cg.contents.offset, (m + 1,)).copy()
-        total = int(offsets[m])
-        ops = np.ctypeslib.as_array(cg.contents.ops, (max(total, 1),))[:total].copy()
-        self.lib.rattle_hip_alignment_free(out)
-        self.lib.rattle_hip_cigars_free(cg)
-        return res, offsets, ops
+        return self._align_packed(True, tcat, toff, rcat, roff, target_of_read, rev, max_cells, pair_chunk, scoring, mode)
 
     def debug_evaluate(self, rects, t_s=0.2, t_v=1000000.0, use_hc=False, is_rna=False, count_pass="auto"):
         """One evaluation of the greedy clustering on the loaded reads (rattle_hip_debug_evaluate, a test hook).

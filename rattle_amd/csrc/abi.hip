@@ -748,12 +748,29 @@ void rattle_hip_assignment_free(rattle_assignment *a) {
 }
 
 // ---- align_pairs (kernel E), align_cigars (kernels E and F), and their _scored forms (the three-state kernels) ------------
-// the body of the four entry points; `who` names the entry point in the messages, `run` (align_cigars) takes the ops of kernel F; `scored`:
-// S is checked behind every check of align_pairs, still before the device is looked at, and the three-state kernels run
-static int align_entry(const char *who, rattle_ctx *c, const uint8_t *tseq, const uint64_t *toff, uint32_t nt, const uint8_t *rseq, const uint64_t *roff,
-                       uint32_t nr, const int32_t *target, const uint8_t *rev, const rattle_align_params *P, rattle_alignment **out, cigar_run *run,
-                       bool scored = false, const rattle_align_scoring *S = nullptr, int mode = RATTLE_ALIGN_LOCAL) {
-    const std::string w = std::string(who) + ": ";
+// what an entry point asks of align_entry
+struct align_request {
+    std::string who;                  // the entry point's name in the messages
+    bool scored;                      // a scoring is required: S is checked behind every other argument, still before the device is looked
+                                      // at, and the three-state kernels run
+    const rattle_align_scoring *S;
+    int mode;
+};
+// the request of a *_mode entry point: scoring NULL is the linear form, and RATTLE_ALIGN_LOCAL is the call it stands for, name and all
+static align_request mode_request(const char *call, const rattle_align_scoring *S, int mode) {
+    return {std::string(call) + (mode != RATTLE_ALIGN_LOCAL ? "_mode" : S ? "_scored" : ""), S != nullptr, S, mode};
+}
+
+// the body of the six entry points, from the null-argument check on; `run` (the align_cigars calls) takes the ops of kernel F
+static int align_entry(const align_request &Q, rattle_ctx *c, const uint8_t *tseq, const uint64_t *toff, uint32_t nt, const uint8_t *rseq, const uint64_t *roff,
+                       uint32_t nr, const int32_t *target, const uint8_t *rev, const rattle_align_params *P, rattle_alignment **out, cigar_run *run) {
+    if (out) *out = nullptr;
+    if (!c || !P || !out || !toff || !roff || (nr && (!target || !rev)) || (!tseq && toff[nt] != toff[0]) || (!rseq && roff[nr] != roff[0])) {
+        set_error("null argument");
+        return RATTLE_ERR_ARG;
+    }
+    const auto &[who, scored, S, mode] = Q;
+    const std::string w = who + ": ";
     // the arguments, on the host: indices, strands, lengths, and the letters of every sequence that is submitted (a target once)
     auto clean = [](const uint8_t *s, uint64_t n) { for (uint64_t i = 0; i < n; ++i) if (!s[i] || !strchr("ACGTU", s[i])) return false; return true; };
     std::vector<uint8_t> seen(nt, 0);
@@ -770,7 +787,7 @@ static int align_entry(const char *who, rattle_ctx *c, const uint8_t *tseq, cons
         }
     }
     if (c->xchg.nranks > 1) {
-        set_error(std::string(who) + " is not available on a context that is one rank of several: sharded jobs are not built, align on one device");
+        set_error(who + " is not available on a context that is one rank of several: sharded jobs are not built, align on one device");
         return RATTLE_ERR_STATE;
     }
     if (scored) {
@@ -819,37 +836,24 @@ static int align_entry(const char *who, rattle_ctx *c, const uint8_t *tseq, cons
 
 int rattle_hip_align_pairs(rattle_ctx *c, const uint8_t *tseq, const uint64_t *toff, uint32_t nt, const uint8_t *rseq, const uint64_t *roff,
                            uint32_t nr, const int32_t *target, const uint8_t *rev, const rattle_align_params *P, rattle_alignment **out) {
-    if (out) *out = nullptr;
-    if (!c || !P || !out || !toff || !roff || (nr && (!target || !rev)) || (!tseq && toff[nt] != toff[0]) || (!rseq && roff[nr] != roff[0])) {
-        set_error("null argument");
-        return RATTLE_ERR_ARG;
-    }
-    return align_entry("align_pairs", c, tseq, toff, nt, rseq, roff, nr, target, rev, P, out, nullptr);
+    return align_entry({"align_pairs", false, nullptr, RATTLE_ALIGN_LOCAL}, c, tseq, toff, nt, rseq, roff, nr, target, rev, P, out, nullptr);
 }
 
 int rattle_hip_align_pairs_scored(rattle_ctx *c, const uint8_t *tseq, const uint64_t *toff, uint32_t nt, const uint8_t *rseq, const uint64_t *roff,
                                   uint32_t nr, const int32_t *target, const uint8_t *rev, const rattle_align_params *P, const rattle_align_scoring *S,
                                   rattle_alignment **out) {
-    if (out) *out = nullptr;
-    if (!c || !P || !out || !toff || !roff || (nr && (!target || !rev)) || (!tseq && toff[nt] != toff[0]) || (!rseq && roff[nr] != roff[0])) {
-        set_error("null argument");
-        return RATTLE_ERR_ARG;
-    }
-    return align_entry("align_pairs_scored", c, tseq, toff, nt, rseq, roff, nr, target, rev, P, out, nullptr, true, S);
+    return align_entry({"align_pairs_scored", true, S, RATTLE_ALIGN_LOCAL}, c, tseq, toff, nt, rseq, roff, nr, target, rev, P, out, nullptr);
 }
 
-// the body of align_cigars and align_cigars_scored
-static int cigars_entry(const char *who, rattle_ctx *c, const uint8_t *tseq, const uint64_t *toff, uint32_t nt, const uint8_t *rseq, const uint64_t *roff,
+// the body of the three align_cigars calls: its own null argument, align_entry, and the ops as the caller's arrays
+static int cigars_entry(const align_request &Q, rattle_ctx *c, const uint8_t *tseq, const uint64_t *toff, uint32_t nt, const uint8_t *rseq, const uint64_t *roff,
                         uint32_t nr, const int32_t *target, const uint8_t *rev, const rattle_align_params *P, rattle_alignment **out,
-                        rattle_cigars **cigars, bool scored, const rattle_align_scoring *S, int mode = RATTLE_ALIGN_LOCAL) {
+                        rattle_cigars **cigars) {
     if (out) *out = nullptr;
     if (cigars) *cigars = nullptr;
-    if (!c || !P || !out || !cigars || !toff || !roff || (nr && (!target || !rev)) || (!tseq && toff[nt] != toff[0]) || (!rseq && roff[nr] != roff[0])) {
-        set_error("null argument");
-        return RATTLE_ERR_ARG;
-    }
+    if (!cigars) { set_error("null argument"); return RATTLE_ERR_ARG; }
     cigar_run run;
-    RT_TRY(align_entry(who, c, tseq, toff, nt, rseq, roff, nr, target, rev, P, out, &run, scored, S, mode));
+    RT_TRY(align_entry(Q, c, tseq, toff, nt, rseq, roff, nr, target, rev, P, out, &run));
     rattle_cigars *G = (rattle_cigars *)calloc(1, sizeof(rattle_cigars));
     G->n = nr;
     G->offset = (uint64_t *)calloc((size_t)nr + 1, 8);
@@ -863,33 +867,26 @@ static int cigars_entry(const char *who, rattle_ctx *c, const uint8_t *tseq, con
 int rattle_hip_align_cigars(rattle_ctx *c, const uint8_t *tseq, const uint64_t *toff, uint32_t nt, const uint8_t *rseq, const uint64_t *roff,
                             uint32_t nr, const int32_t *target, const uint8_t *rev, const rattle_align_params *P, rattle_alignment **out,
                             rattle_cigars **cigars) {
-    return cigars_entry("align_cigars", c, tseq, toff, nt, rseq, roff, nr, target, rev, P, out, cigars, false, nullptr);
+    return cigars_entry({"align_cigars", false, nullptr, RATTLE_ALIGN_LOCAL}, c, tseq, toff, nt, rseq, roff, nr, target, rev, P, out, cigars);
 }
 
 int rattle_hip_align_cigars_scored(rattle_ctx *c, const uint8_t *tseq, const uint64_t *toff, uint32_t nt, const uint8_t *rseq, const uint64_t *roff,
                                    uint32_t nr, const int32_t *target, const uint8_t *rev, const rattle_align_params *P, const rattle_align_scoring *S,
                                    rattle_alignment **out, rattle_cigars **cigars) {
-    return cigars_entry("align_cigars_scored", c, tseq, toff, nt, rseq, roff, nr, target, rev, P, out, cigars, true, S);
+    return cigars_entry({"align_cigars_scored", true, S, RATTLE_ALIGN_LOCAL}, c, tseq, toff, nt, rseq, roff, nr, target, rev, P, out, cigars);
 }
 
-// the four calls above with a mode: scoring NULL is the linear form.  RATTLE_ALIGN_LOCAL is the call it stands for, name and all.
+// the four calls above with a mode
 int rattle_hip_align_pairs_mode(rattle_ctx *c, const uint8_t *tseq, const uint64_t *toff, uint32_t nt, const uint8_t *rseq, const uint64_t *roff,
                                 uint32_t nr, const int32_t *target, const uint8_t *rev, const rattle_align_params *P, const rattle_align_scoring *S,
                                 int mode, rattle_alignment **out) {
-    if (out) *out = nullptr;
-    if (!c || !P || !out || !toff || !roff || (nr && (!target || !rev)) || (!tseq && toff[nt] != toff[0]) || (!rseq && roff[nr] != roff[0])) {
-        set_error("null argument");
-        return RATTLE_ERR_ARG;
-    }
-    const char *who = mode != RATTLE_ALIGN_LOCAL ? "align_pairs_mode" : S ? "align_pairs_scored" : "align_pairs";
-    return align_entry(who, c, tseq, toff, nt, rseq, roff, nr, target, rev, P, out, nullptr, S != nullptr, S, mode);
+    return align_entry(mode_request("align_pairs", S, mode), c, tseq, toff, nt, rseq, roff, nr, target, rev, P, out, nullptr);
 }
 
 int rattle_hip_align_cigars_mode(rattle_ctx *c, const uint8_t *tseq, const uint64_t *toff, uint32_t nt, const uint8_t *rseq, const uint64_t *roff,
                                  uint32_t nr, const int32_t *target, const uint8_t *rev, const rattle_align_params *P, const rattle_align_scoring *S,
                                  int mode, rattle_alignment **out, rattle_cigars **cigars) {
-    const char *who = mode != RATTLE_ALIGN_LOCAL ? "align_cigars_mode" : S ? "align_cigars_scored" : "align_cigars";
-    return cigars_entry(who, c, tseq, toff, nt, rseq, roff, nr, target, rev, P, out, cigars, S != nullptr, S, mode);
+    return cigars_entry(mode_request("align_cigars", S, mode), c, tseq, toff, nt, rseq, roff, nr, target, rev, P, out, cigars);
 }
 
 void rattle_hip_cigars_free(rattle_cigars *g) {

@@ -934,12 +934,11 @@ struct assign_job {
     uint32_t ranks() const { return std::min(C->k, secondary + 1); }
     // the submitted reads on target[r] / rev[r] each (-1: not aligned): one call of the library
     void align_on(const int32_t *target, const uint8_t *rev, rattle_alignment **L, rattle_cigars **G) {
-        if (want_ends && want_cigar) chk(rattle_hip_align_cigars_mode(team.ctx[0], xcat.data(), xoff.data(), (uint32_t)xid.size(), rcat.data(), roff.data(), (uint32_t)rid.size(), target, rev, &AP, want_scoring ? &AS : nullptr, RATTLE_ALIGN_READ, L, G));
-        else if (want_ends) chk(rattle_hip_align_pairs_mode(team.ctx[0], xcat.data(), xoff.data(), (uint32_t)xid.size(), rcat.data(), roff.data(), (uint32_t)rid.size(), target, rev, &AP, want_scoring ? &AS : nullptr, RATTLE_ALIGN_READ, L));
-        else if (want_scoring && want_cigar) chk(rattle_hip_align_cigars_scored(team.ctx[0], xcat.data(), xoff.data(), (uint32_t)xid.size(), rcat.data(), roff.data(), (uint32_t)rid.size(), target, rev, &AP, &AS, L, G));
-        else if (want_scoring) chk(rattle_hip_align_pairs_scored(team.ctx[0], xcat.data(), xoff.data(), (uint32_t)xid.size(), rcat.data(), roff.data(), (uint32_t)rid.size(), target, rev, &AP, &AS, L));
-        else if (want_cigar) chk(rattle_hip_align_cigars(team.ctx[0], xcat.data(), xoff.data(), (uint32_t)xid.size(), rcat.data(), roff.data(), (uint32_t)rid.size(), target, rev, &AP, L, G));
-        else chk(rattle_hip_align_pairs(team.ctx[0], xcat.data(), xoff.data(), (uint32_t)xid.size(), rcat.data(), roff.data(), (uint32_t)rid.size(), target, rev, &AP, L));
+        const rattle_align_scoring *S = want_scoring ? &AS : nullptr;
+        const int mode = want_ends ? RATTLE_ALIGN_READ : RATTLE_ALIGN_LOCAL;      // (local through the _mode calls is the plain call, name and all)
+        const uint32_t nt = (uint32_t)xid.size(), nr = (uint32_t)rid.size();
+        if (want_cigar) chk(rattle_hip_align_cigars_mode(team.ctx[0], xcat.data(), xoff.data(), nt, rcat.data(), roff.data(), nr, target, rev, &AP, S, mode, L, G));
+        else chk(rattle_hip_align_pairs_mode(team.ctx[0], xcat.data(), xoff.data(), nt, rcat.data(), roff.data(), nr, target, rev, &AP, S, mode, L));
     }
     // the PAF line of submitted read `at` on transcript x; tags: what stands between nd:i: and cg:Z:
     void paf_line(uint32_t at, uint32_t x, bool rev, const rattle_alignment *L, const rattle_cigars *G, const std::string &tags) {

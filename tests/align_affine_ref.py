@@ -20,6 +20,8 @@ an H and left only into an H it equals, the first and the last column of every a
 Fact 2.  With o == e, U[i][j] = max(H[i-1][j], U[i-1][j]) - o = H[i-1][j] - o by fact 1, open wins every tie, and so the path is cell
 for cell the linear path of align_ref with gap -o.
 
+The recurrence itself is written once, in tests/align_model.py; the names below are its functions at the mode LOCAL:
+
   fill(q, t, sc)        the three matrices
   walk(q, t, F, i, j)   from the end cell back: the cells of the path (end first) and the (cell, state) pairs it visits
   traceback(q, t, sc)   the classic form: fill, end cell, walk, count the columns
@@ -31,204 +33,23 @@ for cell the linear path of align_ref with gap -o.
 No device, no numpy in the recurrences."""
 import numpy as np
 
+import align_model as M
 import align_ref as R
 import cigar_ref as CG
 
-NEG = -(1 << 30)
+NEG, H_, U_, L_ = M.NEG, M.H_, M.U_, M.L_           # minus infinity, and the states of a walk
 LINEAR, ENGINE, MM2, LONG = (5, 4, 8, 8), (5, 4, 8, 6), (2, 4, 4, 2), (5, 4, 12, 1)
 SCORINGS = (LINEAR, ENGINE, MM2, LONG)
-H_, U_, L_ = 0, 1, 2                                # the states of a walk
 
-
-def check_scoring(sc):
-    m, x, o, e = sc
-    assert 1 <= m <= 64 and 1 <= x <= 64 and 1 <= e <= o <= 64, sc
-
-
-def fill(q: bytes, t: bytes, sc):
-    """(H, U, L), each (len(q) + 1) x (len(t) + 1) as a list of rows; U and L hold NEG where the recurrence has minus infinity (and on
-    the borders, which no recurrence reads but through H)"""
-    check_scoring(sc)
-    m, x, o, e = sc
-    q, t = q.translate(R._T), t.translate(R._T)
-    n = len(t)
-    pH, pU = [0] * (n + 1), [NEG] * (n + 1)
-    H, U, L = [pH], [pU], [[NEG] * (n + 1)]
-    for qc in q:
-        cH, cU, cL = [0] * (n + 1), [NEG] * (n + 1), [NEG] * (n + 1)
-        h, l = 0, NEG
-        for j, tc in enumerate(t, 1):
-            a, b = pH[j] - o, pU[j] - e
-            u = a if a >= b else b
-            a, b = h - o, l - e
-            l = a if a >= b else b
-            h = pH[j - 1] + (m if qc == tc else -x)
-            if u > h:
-                h = u
-            if l > h:
-                h = l
-            if h < 0:
-                h = 0
-            cH[j], cU[j], cL[j] = h, u, l
-        H.append(cH); U.append(cU); L.append(cL)
-        pH, pU = cH, cU
-    return H, U, L
-
-
-def walk(q: bytes, t: bytes, F, i: int, j: int, sc, open_wins: bool = True):
-    """From H of cell (i, j) back to the zero cell its alignment begins behind.  Returns (cells, end first; visits [(i, j, state)], end
-    first).  In H: diagonal if it reproduces the score, else U, else L (a switch of state does not move); in U the step goes up and lands
-    in H if open >= extend reproduces U (open_wins=False: if open > extend -- the opposite tie rule, for the test of the rule), else
-    stays in U; L likewise to the left."""
-    m, x, o, e = sc
-    H, U, L = F
-    q, t = q.translate(R._T), t.translate(R._T)
-    path, visits, state = [(i, j)], [], H_
-    while i > 0 and j > 0:
-        visits.append((i, j, state))
-        if state == H_:
-            h = H[i][j]
-            if h == 0:
-                break
-            if h == H[i - 1][j - 1] + (m if q[i - 1] == t[j - 1] else -x):
-                i, j = i - 1, j - 1
-                path.append((i, j))
-            elif h == U[i][j]:
-                state = U_
-            else:
-                assert h == L[i][j]
-                state = L_
-            continue
-        M, di, dj = (U, 1, 0) if state == U_ else (L, 0, 1)
-        opn, ext = H[i - di][j - dj] - o, M[i - di][j - dj] - e
-        assert M[i][j] == max(opn, ext)
-        if opn > ext or (opn == ext and open_wins):
-            state = H_
-        i, j = i - di, j - dj
-        path.append((i, j))
-    return path, visits
-
-
-def _record(q, t, F, sc):
-    """(record, ops, visits) from filled matrices"""
-    m, x, o, e = sc
-    score, i, j = R.end_cell(F[0])
-    if score <= 0:
-        return R.NONE, [], []
-    path, visits = walk(q, t, F, i, j, sc)
-    ops = CG.ops_of_path(q, t, path)
-    n = CG.sums(ops)
-    si, sj = path[-1]
-    opens = sum(1 for o_, _ in ops if o_ in "ID")
-    assert F[0][si][sj] == 0 and score == m * n["="] - x * n["X"] - o * opens - e * (n["I"] + n["D"] - opens)
-    return (0, score, si, i, sj, j, n["="], n["X"], n["I"], n["D"]), ops, visits
-
-
-def full(q: bytes, t: bytes, sc):
-    """the whole matrices: (record, ops); (align_ref.NONE, []) if nothing aligns"""
-    if not q or not t:
-        return R.NONE, []
-    return _record(q, t, fill(q, t, sc), sc)[:2]
+# the model at this mode, under the signatures of the list above; walk(..., open_wins=False) is the opposite tie rule in a gap state,
+# records(..., max_cells=0, form="full") and cigars(..., max_cells=0) are what the _scored calls return for a case, pair(q, t, rev, sc)
+# is (record on the read as given, ops) of one pair, remembered
+check_scoring = M.check_scoring
+fill, walk, full, forward, rectangle, pair, records, cigars = M.bind(M.LOCAL, "fill", "walk", "full", "forward", "rectangle", "pair", "records", "cigars")
 
 
 def traceback(q: bytes, t: bytes, sc):
     return full(q, t, sc)[0]
-
-
-def forward(q: bytes, t: bytes, sc):
-    """the forward-carried payload: no matrix, no walk.  A payload is (start_i, start_j, matches, mismatches)."""
-    check_scoring(sc)
-    if not q or not t:
-        return R.NONE
-    m, x, o, e = sc
-    q, t = q.translate(R._T), t.translate(R._T)
-    n = len(t)
-    Z = (0, 0, 0, 0)
-    pH, pU, pHp, pUp = [0] * (n + 1), [NEG] * (n + 1), [Z] * (n + 1), [Z] * (n + 1)
-    best = (0, 0, 0, Z)                             # score, i, j, payload
-    for i, qc in enumerate(q, 1):
-        cH, cU, cHp, cUp = [0] * (n + 1), [NEG] * (n + 1), [Z] * (n + 1), [Z] * (n + 1)
-        l, lp = NEG, Z
-        for j in range(1, n + 1):
-            eq = qc == t[j - 1]
-            a, b = pH[j] - o, pU[j] - e
-            u, up = (a, pHp[j]) if a >= b else (b, pUp[j])
-            a, b = cH[j - 1] - o, l - e
-            l, lp = (a, cHp[j - 1]) if a >= b else (b, lp)
-            d = pH[j - 1] + (m if eq else -x)
-            h = max(0, d, u, l)
-            cU[j], cUp[j] = u, up
-            if h == 0:
-                continue                            # begins a new alignment: whatever continues from here takes its own coordinates
-            if d >= u and d >= l:
-                si, sj, M, X = (i - 1, j - 1, 0, 0) if pH[j - 1] == 0 else pHp[j - 1]
-                hp = (si, sj, M + eq, X + (not eq))
-            elif u >= l:
-                hp = up
-            else:
-                hp = lp
-            cH[j], cHp[j] = h, hp
-            if h > best[0]:
-                best = (h, i, j, hp)
-        pH, pU, pHp, pUp = cH, cU, cHp, cUp
-    S, i, j, (si, sj, M, X) = best
-    if S <= 0:
-        return R.NONE
-    sq, st = i - si, j - sj
-    assert sq - M - X >= 0 and st - M - X >= 0
-    return (0, S, si, i, sj, j, M, X, sq - M - X, st - M - X)
-
-
-def rectangle(q: bytes, t: bytes, rec, sc, left=0):
-    """The recurrence over the rectangle of `rec` alone (H' = 0, U' = L' = -inf on its borders), walked back from its last cell.  left:
-    columns the rectangle is cut short by on the left (the test of the test).  Returns (ops, H' of the last cell, end of the walk,
-    the three matrices)."""
-    _, _, si, i, sj, j = rec[:6]
-    qq, tt = q[si:i], t[sj + left:j]
-    F = fill(qq, tt, sc)
-    path, _ = walk(qq, tt, F, len(qq), len(tt), sc)
-    return CG.ops_of_path(qq, tt, path), F[0][len(qq)][len(tt)], path[-1], F
-
-
-_memo = {}
-
-
-def pair(q: bytes, t: bytes, rev: int, sc, form="full"):
-    """(record on the read as given, ops) of one pair: the strand applied as align_ref.align applies it.  form "forward" has no ops."""
-    key = (q, t, int(rev), tuple(sc), form)
-    if key not in _memo:
-        qq = R.revcomp(q) if rev else q
-        rec, ops = full(qq, t, sc) if form == "full" else (forward(qq, t, sc), None)
-        if rev and rec[0] == 0:
-            rec = rec[:2] + (len(q) - rec[3], len(q) - rec[2]) + rec[4:]
-        _memo[key] = (rec, ops)
-    return _memo[key]
-
-
-def records(targets, reads, target_of_read, rev, sc, max_cells=0, form="full"):
-    """what rattle_hip_align_pairs_scored returns: a dict of arrays (align_ref.FIELDS).  Pairs are remembered per scoring."""
-    out = []
-    for q, x, s in zip(reads, target_of_read, rev):
-        if x < 0:
-            out.append(R.NOT_SUBMITTED)
-        elif not q or not targets[x]:
-            out.append(R.NONE)
-        elif max_cells and len(q) * len(targets[x]) > max_cells:
-            out.append(R.SKIPPED)
-        else:
-            out.append(pair(q, targets[x], int(s), sc, form)[0])
-    return {f: np.array([r[k] for r in out], dt) for k, (f, dt) in enumerate(R.FIELDS)}
-
-
-def cigars(targets, reads, target_of_read, rev, sc, max_cells=0):
-    """the CIGAR string of every read, b"" for a read that is not submitted, skipped or aligns nothing"""
-    out = []
-    for q, x, s in zip(reads, target_of_read, rev):
-        if x < 0 or not q or not targets[x] or (max_cells and len(q) * len(targets[x]) > max_cells):
-            out.append(b"")
-        else:
-            out.append(CG.text(pair(q, targets[x], int(s), sc)[1]))
-    return out
 
 
 # ---- cases for the three-state kernels: (targets, reads, target_of_read, rev) --------------------------------------------------------

@@ -16,6 +16,8 @@ H[Lq][j] over j = 1..Lt, ties to the smallest j.  The walk goes back to row 0 an
 walk that reaches column 0 goes straight up: the remaining rows are one I run.  The record has status 0, q_start = 0, q_end = Lq, a
 score that may be zero or negative, and t_end - t_start may be 0 (the whole read one I run).
 
+The recurrence itself is written once, in tests/align_model.py; the names below are its functions at the mode READ:
+
   fill(q, t, sc)        the three matrices
   walk(q, t, F, j, sc)  from H[Lq][j] back to row 0: the cells of the path (end first) and the (cell, state) pairs it visits
   full(q, t, sc)        fill, end cell, walk, count the columns: (record, ops)
@@ -27,6 +29,7 @@ No device, no numpy in the recurrences."""
 import numpy as np
 
 import align_affine_ref as A
+import align_model as M
 import align_ref as R
 import cigar_ref as CG
 
@@ -35,191 +38,12 @@ H_, U_, L_ = A.H_, A.U_, A.L_
 CHEAP_GAP = (1, 64, 1, 1)                           # a mismatch costs more than any short gap: t_end == t_start occurs
 SCORINGS = A.SCORINGS + (CHEAP_GAP,)
 
-
-def border(i: int, sc) -> int:
-    """H[i][0] = U[i][0], i >= 1"""
-    return -(sc[2] + (i - 1) * sc[3])
-
-
-def fill(q: bytes, t: bytes, sc):
-    """(H, U, L), each (len(q) + 1) x (len(t) + 1) as a list of rows; NEG where the recurrence has minus infinity"""
-    A.check_scoring(sc)
-    m, x, o, e = sc
-    q, t = q.translate(R._T), t.translate(R._T)
-    n = len(t)
-    pH, pU = [0] * (n + 1), [NEG] * (n + 1)
-    H, U, L = [pH], [pU], [[NEG] * (n + 1)]
-    for i, qc in enumerate(q, 1):
-        b = border(i, sc)
-        cH, cU, cL = [b] + [0] * n, [b] + [NEG] * n, [NEG] * (n + 1)
-        h, l = b, NEG
-        for j, tc in enumerate(t, 1):
-            a, c = pH[j] - o, pU[j] - e
-            u = a if a >= c else c
-            a, c = h - o, l - e
-            l = a if a >= c else c
-            h = pH[j - 1] + (m if qc == tc else -x)
-            if u > h:
-                h = u
-            if l > h:
-                h = l
-            cH[j], cU[j], cL[j] = h, u, l
-        H.append(cH); U.append(cU); L.append(cL)
-        pH, pU = cH, cU
-    return H, U, L
-
-
-def end_cell(H):
-    """(score, j): the largest H of the last row over j >= 1, ties to the smallest j"""
-    row = H[-1]
-    best = max(row[1:])
-    return best, row.index(best, 1)
-
-
-def walk(q: bytes, t: bytes, F, j: int, sc):
-    """From H of cell (Lq, j) back to row 0.  Returns (cells, end first; visits [(i, j, state)], end first).  In column 0 the walk goes
-    up (the border is a gap straight down from (0, 0)); elsewhere as align_affine_ref.walk, without its stop at a zero."""
-    m, x, o, e = sc
-    H, U, L = F
-    q, t = q.translate(R._T), t.translate(R._T)
-    i = len(q)
-    path, visits, state = [(i, j)], [], H_
-    while i > 0:
-        if j == 0:
-            assert state == H_
-            i -= 1
-            path.append((i, 0))
-            continue
-        visits.append((i, j, state))
-        if state == H_:
-            h = H[i][j]
-            if h == H[i - 1][j - 1] + (m if q[i - 1] == t[j - 1] else -x):
-                i, j = i - 1, j - 1
-                path.append((i, j))
-            elif h == U[i][j]:
-                state = U_
-            else:
-                assert h == L[i][j]
-                state = L_
-            continue
-        M, di, dj = (U, 1, 0) if state == U_ else (L, 0, 1)
-        opn, ext = H[i - di][j - dj] - o, M[i - di][j - dj] - e
-        assert M[i][j] == max(opn, ext)
-        if opn >= ext:
-            state = H_
-        i, j = i - di, j - dj
-        path.append((i, j))
-    return path, visits
-
-
-def _record(q, t, F, sc):
-    m, x, o, e = sc
-    score, j = end_cell(F[0])
-    path, visits = walk(q, t, F, j, sc)
-    ops = CG.ops_of_path(q, t, path)
-    n = CG.sums(ops)
-    si, sj = path[-1]
-    opens = sum(1 for o_, _ in ops if o_ in "ID")
-    assert si == 0 and score == m * n["="] - x * n["X"] - o * opens - e * (n["I"] + n["D"] - opens)
-    return (0, score, 0, len(q), sj, j, n["="], n["X"], n["I"], n["D"]), ops, visits
-
-
-def full(q: bytes, t: bytes, sc):
-    """the whole matrices: (record, ops); (align_ref.NONE, []) for an empty sequence"""
-    if not q or not t:
-        return R.NONE, []
-    return _record(q, t, fill(q, t, sc), sc)[:2]
-
-
-def forward(q: bytes, t: bytes, sc):
-    """the forward-carried payload: no matrix, no walk.  A payload is (start_j, matches, mismatches); start_i is 0 everywhere."""
-    A.check_scoring(sc)
-    if not q or not t:
-        return R.NONE
-    m, x, o, e = sc
-    q, t = q.translate(R._T), t.translate(R._T)
-    n = len(t)
-    Z = (0, 0, 0)
-    pH, pU = [0] * (n + 1), [NEG] * (n + 1)
-    pHp, pUp = [(j, 0, 0) for j in range(n + 1)], [Z] * (n + 1)
-    for i, qc in enumerate(q, 1):
-        b = border(i, sc)
-        cH, cU, cHp, cUp = [b] + [0] * n, [b] + [NEG] * n, [Z] * (n + 1), [Z] * (n + 1)
-        l, lp = NEG, Z
-        for j in range(1, n + 1):
-            eq = qc == t[j - 1]
-            a, c = pH[j] - o, pU[j] - e
-            u, up = (a, pHp[j]) if a >= c else (c, pUp[j])
-            a, c = cH[j - 1] - o, l - e
-            l, lp = (a, cHp[j - 1]) if a >= c else (c, lp)
-            d = pH[j - 1] + (m if eq else -x)
-            if d >= u and d >= l:
-                sj, M, X = pHp[j - 1]
-                hp = (sj, M + eq, X + (not eq))
-            elif u >= l:
-                hp = up
-            else:
-                hp = lp
-            cH[j], cHp[j], cU[j], cUp[j] = max(d, u, l), hp, u, up
-        pH, pU, pHp, pUp = cH, cU, cHp, cUp
-    S = max(pH[1:])
-    j = pH.index(S, 1)
-    sj, M, X = pHp[j]
-    sq, st = len(q), j - sj
-    if tuple(sc) == A.LINEAR:                       # what the linear form of kernel E does: X from the score and the two spans
-        X12 = 8 * (sq + st) - 21 * M + S
-        assert X12 % 12 == 0 and X12 // 12 == X, (X12, X)
-    assert sq - M - X >= 0 and st - M - X >= 0
-    return (0, S, 0, sq, sj, j, M, X, sq - M - X, st - M - X)
-
-
-def rectangle(q: bytes, t: bytes, rec, sc, left=0):
-    """The recurrence over the rectangle of `rec` alone -- every row, columns (t_start, t_end] -- with this mode's borders, walked back
-    from its last cell.  left: columns the rectangle is cut short by on the left (the test of the test).  Returns (ops, H' of the last
-    cell, end of the walk, the three matrices).  With no column the walk is the border: one I run."""
-    sj, j = rec[4], rec[5]
-    tt = t[sj + left:j]
-    F = fill(q, tt, sc)
-    path, _ = walk(q, tt, F, len(tt), sc)
-    return CG.ops_of_path(q, tt, path), F[0][len(q)][len(tt)], path[-1], F
-
-
-_memo = {}
-
-
-def pair(q: bytes, t: bytes, rev: int, sc, form="full"):
-    """(record on the read as given, ops) of one pair.  q_start = 0 and q_end = Lq on either strand.  form "forward" has no ops."""
-    key = (q, t, int(rev), tuple(sc), form)
-    if key not in _memo:
-        qq = R.revcomp(q) if rev else q
-        _memo[key] = full(qq, t, sc) if form == "full" else (forward(qq, t, sc), None)
-    return _memo[key]
-
-
-def records(targets, reads, target_of_read, rev, sc, max_cells=0, form="full"):
-    """what rattle_hip_align_pairs_mode returns in read mode: a dict of arrays (align_ref.FIELDS)"""
-    out = []
-    for q, x, s in zip(reads, target_of_read, rev):
-        if x < 0:
-            out.append(R.NOT_SUBMITTED)
-        elif not q or not targets[x]:
-            out.append(R.NONE)
-        elif max_cells and len(q) * len(targets[x]) > max_cells:
-            out.append(R.SKIPPED)
-        else:
-            out.append(pair(q, targets[x], int(s), sc, form)[0])
-    return {f: np.array([r[k] for r in out], dt) for k, (f, dt) in enumerate(R.FIELDS)}
-
-
-def cigars(targets, reads, target_of_read, rev, sc, max_cells=0):
-    """the CIGAR string of every read, b"" for a read that is not submitted, skipped or has an empty sequence"""
-    out = []
-    for q, x, s in zip(reads, target_of_read, rev):
-        if x < 0 or not q or not targets[x] or (max_cells and len(q) * len(targets[x]) > max_cells):
-            out.append(b"")
-        else:
-            out.append(CG.text(pair(q, targets[x], int(s), sc)[1]))
-    return out
+# the model at this mode, under the signatures of the list above; records(..., max_cells=0, form="full") and cigars(..., max_cells=0) are
+# what the _mode calls return for a case in read mode, pair(q, t, rev, sc) is (record on the read as given, ops) of one pair, remembered
+fill, full, forward, rectangle, pair, records, cigars = M.bind(M.READ, "fill", "full", "forward", "rectangle", "pair", "records", "cigars")
+border = lambda i, sc: M.border(i, sc, M.READ)[0]                           # H[i][0] = U[i][0], i >= 1
+end_cell = lambda H: M.end_cell((H,), M.READ)[::2]                          # (score, j) of the last row
+walk = lambda q, t, F, j, sc: M.walk(q, t, F, len(q), j, sc, M.READ)        # from H[Lq][j]
 
 
 # ---- cases for the read mode: (targets, reads, target_of_read, rev) -------------------------------------------------------------------

@@ -4,7 +4,7 @@ co-optimal choices (diagonal, up, left; open before extend) beyond the first blo
 chosen q_start, pairs of sixteen and more row blocks, and scorings at both ends of the accepted range.
 
 The references stay as they are.  What is added here measures the CASES, on the CPU: walks of the reference matrices under a WRONG rule
-(H order "udl" or "dlu" for the rule's "dul", extend before open), an end cell keyed the wrong way round, and the path cells on which two
+(tests/align_model.py's walk with H order "udl" or "dlu" for the rule's "dul", extend before open), an end cell keyed the wrong way round, and the path cells on which two
 choices tie, by row and by column.  A case pins a rule where the wrong rule changes its CIGAR; tests/test_align_sweep.py asserts that it
 does, and where.  `mode` is "local" (align_affine_ref's matrices) or "read" (align_ends_ref's) throughout.
 
@@ -13,10 +13,12 @@ import numpy as np
 
 import align_affine_ref as A
 import align_ends_ref as E
+import align_model as M
 import align_ref as R
 import cigar_ref as CG
+from align_model import fill, walk                  # fill(q, t, sc, mode); walk(q, t, F, i, j, sc, mode, order="dul", open_wins=True)
 
-MODES = ("local", "read")
+MODES = M.MODES                                     # "local" and "read"
 # both ends of every magnitude; x > 2 o with o > e (1,64,64,1 has it the other way: a gap never pays); x > 2 o with o == e (1,64,1,1;
 # 2,5,2,2); o == e other than 8 (those two, 1,1,1,1, 64,64,64,64 and 3,2,5,5): by fact 2 of align_affine_ref the linear path
 SWEEP_SCORINGS = ((1, 1, 1, 1), (64, 64, 64, 64), (64, 1, 64, 1), (64, 64, 64, 1), (1, 64, 64, 1), (1, 64, 1, 1), (2, 5, 2, 2), (3, 2, 5, 5))
@@ -27,18 +29,18 @@ def scoring_id(sc) -> str:
     return "linear" if sc is None else ".".join(map(str, sc))
 
 
-# ---- the references by mode, and walks under a chosen rule ---------------------------------------------------------------------------
+# ---- the model by mode, and what a wrong rule changes ----------------------------------------------------------------------------------
 def ref(mode):
-    """the module that is the contract of `mode`"""
+    """the module that states the contract of `mode` and binds the model at it"""
     return {"local": A, "read": E}[mode]
 
 
 def records(case, sc, mode, **kw):
-    return ref(mode).records(*case, sc, **kw)
+    return M.records(*case, sc, mode, **kw)
 
 
 def cigars(case, sc, mode, **kw):
-    return ref(mode).cigars(*case, sc, **kw)
+    return M.cigars(*case, sc, mode, **kw)
 
 
 def submitted(case):
@@ -49,11 +51,8 @@ def submitted(case):
 
 def end_cell(F, mode):
     """the rule's end cell (score, i, j); None where nothing aligns locally"""
-    if mode == "read":
-        score, j = E.end_cell(F[0])
-        return score, len(F[0]) - 1, j
-    score, i, j = R.end_cell(F[0])
-    return (score, i, j) if score > 0 else None
+    end = M.end_cell(F, mode)
+    return end if mode == "read" or end[0] > 0 else None
 
 
 def end_cell_ji(F, mode):
@@ -69,51 +68,6 @@ def end_cell_ji(F, mode):
         return None
     j, i = min((j, i) for i, row in enumerate(H) for j, h in enumerate(row) if h == best)
     return best, i, j
-
-
-def walk(q, t, F, i, j, sc, mode, order="dul", open_wins=True):
-    """The walk of align_affine_ref (mode "local": it stops at H == 0) or of align_ends_ref (mode "read": back to row 0, straight up in
-    column 0) from H of cell (i, j), with the order in which H's predecessors are tried as a string of d (diagonal), u (the state U) and
-    l (the state L) -- "dul" is the rule, "udl" and "dlu" are wrong ones -- and with open_wins=False the opposite rule in a gap state.
-    Returns (cells, end first; visits [(i, j, state)], end first), like the references' walks, which it equals under the rule."""
-    assert sorted(order) == ["d", "l", "u"]
-    m, x, o, e = sc
-    H, U, L = F
-    q, t = q.translate(R._T), t.translate(R._T)
-    local = mode == "local"
-    path, visits, state = [(i, j)], [], A.H_
-    while i > 0 and (j > 0 or not local):
-        if j == 0:                                  # (read mode: the border is one gap straight down from (0, 0))
-            i -= 1
-            path.append((i, 0))
-            continue
-        visits.append((i, j, state))
-        if state == A.H_:
-            h = H[i][j]
-            if local and h == 0:
-                break
-            for c in order:
-                if c == "d" and h == H[i - 1][j - 1] + (m if q[i - 1] == t[j - 1] else -x):
-                    i, j = i - 1, j - 1
-                    path.append((i, j))
-                    break
-                if c == "u" and h == U[i][j]:
-                    state = A.U_
-                    break
-                if c == "l" and h == L[i][j]:
-                    state = A.L_
-                    break
-            else:
-                raise AssertionError("no predecessor reproduces H")
-            continue
-        M, di, dj = (U, 1, 0) if state == A.U_ else (L, 0, 1)
-        opn, ext = H[i - di][j - dj] - o, M[i - di][j - dj] - e
-        assert M[i][j] == max(opn, ext)
-        if opn > ext or (opn == ext and open_wins):
-            state = A.H_
-        i, j = i - di, j - dj
-        path.append((i, j))
-    return path, visits
 
 
 def tie_cells(q, t, F, visits, sc):
@@ -141,15 +95,11 @@ def count_ties(ties, kind=None, row=0, col=0):
     return sum(1 for i, j, k in ties if (kind is None or k == kind) and i > row and j > col)
 
 
-def fill(q, t, sc, mode):
-    return ref(mode).fill(q, t, sc)
-
-
 def full(q, t, sc, mode):
-    """One pair on the strand aligned, from the whole matrices, by the reference's own fill, end cell and walk: (record, ops, visits,
-    matrices).  (align_ref.NONE, [], [], F) where nothing aligns locally."""
+    """One pair on the strand aligned, from the whole matrices, by the model's fill, end cell and walk: (record, ops, visits, matrices).
+    (align_ref.NONE, [], [], F) where nothing aligns locally."""
     F = fill(q, t, sc, mode)
-    return ref(mode)._record(q, t, F, sc) + (F,)
+    return M.record(q, t, F, sc, mode) + (F,)
 
 
 def gap_held_two_steps(visits) -> bool:
