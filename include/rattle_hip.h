@@ -438,6 +438,47 @@ int  rattle_hip_align_cigars_mode(rattle_ctx *ctx, const uint8_t *target_concat,
                                   rattle_alignment **out, rattle_cigars **cigars);
 
 /* ------------------------------------------------------------------------------------
+ * align_pileup (ABI 4): align_cigars_mode, and what the aligned reads say about EVERY BASE of every target (kernel G,
+ * csrc/pair_pileup.hip, behind kernel F's gather on the ops that lie on the device; tests/pileup_ref.py is the contract in plain Python).
+ * *out, and *cigars when asked for, are what rattle_hip_align_cigars_mode returns for the same arguments.  With cigars == NULL the
+ * compact ops are NOT copied to the host (the per-pair counts still are: the offsets on the device need them).
+ * One table over the concatenated targets: n = target_offsets[n_targets] positions, position p is byte p of target_concat, eight uint32
+ * counts per position, as eight arrays (the table is planar on the device too: a wavefront on 64 consecutive columns of a run adds into
+ * at most four contiguous segments).  All counts are on the TARGET's strand.  Walk the CIGAR of every read with status 0 as align_cigars
+ * defines it -- the read reverse-complemented first when rev == 1, the target forward, U read as T -- from t_start, j the target position
+ * and i the row of the aligned read:
+ *   a, c, g, t at j      a column of an '=' or 'X' op whose READ base (on the aligned strand) is that letter
+ *   del at j             a column of a 'D' op
+ *   ins at j             an 'I' op that is NEITHER THE FIRST NOR THE LAST op of the read's CIGAR, once per op, at the target position of
+ *                        the column that follows it (the base to its right)
+ *   starts at t_start, ends at t_end - 1     a read whose rectangle has at least one column (t_end > t_start)
+ * depth = a + c + g + t + del.  A leading or trailing I run is not counted: it occurs in RATTLE_ALIGN_READ only and is the read's
+ * overhang, what the local mode would have clipped.  A read-mode pair with t_end == t_start (the host-written single I op) and a read
+ * with status 1, 2 or 3 add nothing.  So the four letter arrays sum to matches + mismatches over the aligned reads, del to their t_gap,
+ * starts and ends each to the number of status-0 reads with a column, and ins > 0 at a position implies depth > 0 there.  The counts
+ * are integers, so they do not depend on the order the device adds them in: two runs give the same bytes, and neither pair_chunk nor
+ * the cap on the code bytes changes them.  A count cannot overflow (n_reads is a uint32).  (A run of 2^28 columns or more comes in
+ * pieces and an I run would count once per piece; no input within the other limits reaches that.)
+ * The table is zeroed once on the device, added to by one launch per sub-chunk of kernel F that has an op, and copied to the host once,
+ * 32 n bytes.  The eight arrays are ONE allocation, freed by rattle_hip_pileup_free alone.
+ * Errors: those of rattle_hip_align_cigars_mode, in their order, with pileup == NULL (in place of cigars == NULL) RATTLE_ERR_ARG.  A
+ * failed allocation of the table, on the host or the device, is RATTLE_ERR_HIP and nothing is returned.
+ * rattle_hip_kernel_stats: kernel G is id 11, one launch per sub-chunk of kernel F that has an op; kernels E and F count under their ids
+ * as in align_cigars_mode, and the other calls never launch id 11.  alg_bytes of id 11, per aligned pair with a column, R rows:
+ *   4 * ops + R  (the ops and the read bases read)  +  4 * (matches + mismatches + t_gap + internal I ops + 2)  (the adds made)
+ * Every launch adds its pairs' share but the 4 bytes per internal I op: the host never sees the ops, so that share is counted from the
+ * ins array and added ONCE, when the call ends and the table is back.  Stats read while the call runs do not hold it yet.
+ */
+typedef struct { uint64_t n;  /* target_offsets[n_targets] */
+                 uint32_t *a, *c, *g, *t, *del, *ins, *starts, *ends; } rattle_pileup;
+int  rattle_hip_align_pileup(rattle_ctx *ctx, const uint8_t *target_concat, const uint64_t *target_offsets, uint32_t n_targets,
+                             const uint8_t *read_concat, const uint64_t *read_offsets, uint32_t n_reads,
+                             const int32_t *target_of_read /* -1: not submitted */, const uint8_t *rev,
+                             const rattle_align_params *params, const rattle_align_scoring *scoring /* NULL: the linear form */, int mode,
+                             rattle_alignment **out, rattle_cigars **cigars /* may be NULL */, rattle_pileup **pileup);
+void rattle_hip_pileup_free(rattle_pileup *p);
+
+/* ------------------------------------------------------------------------------------
  * a15  spoa engine + graph as called from /root/reference/correct.cpp:395-405,428-436,520-532
  * (createAlignmentEngine(kSW,5,-4,-8,-6); align + add_alignment per sequence;
  * generate_multiple_sequence_alignment).  Packs are independent; pack p holds sequences
@@ -791,7 +832,8 @@ void rattle_hip_debug_consensus_support_free(rattle_debug_support *d);
  * kernel: 0 kmer_extract, 1 bv_filter, 2 pair_score, 3 poa_align, 4 post_msa, 5 the per-read reduction of
  * assign (alg_bytes: the bytes of its records copied to the host), 6 pair_align (kernel E; alg_bytes: the sequence bytes read plus
  * the record bytes written), 7 pair_cigar (kernel F; alg_bytes: see align_cigars), 8 and 9 their three-state forms
- * (align_pairs_scored, align_cigars_scored), 10 the abundance EM (csrc/abundance.hip).  Accumulated since
+ * (align_pairs_scored, align_cigars_scored), 10 the abundance EM (csrc/abundance.hip), 11 pair_pileup (kernel G; alg_bytes: see
+ * align_pileup).  Accumulated since
  * the last reset: total milliseconds, number of launches, algorithmic bytes moved.
  */
 int rattle_hip_kernel_stats(rattle_ctx *ctx, int kernel, double *total_ms, uint64_t *launches, uint64_t *alg_bytes);

@@ -189,6 +189,14 @@ class Cigars(C.Structure):
     _fields_ = [("n", C.c_uint32), ("offset", C.POINTER(C.c_uint64)), ("ops", C.POINTER(C.c_uint32))]
 
 
+# the table of align_pileup (rattle_pileup): eight arrays of n counts, position p = byte p of the concatenated targets
+PILEUP_FIELDS = ("a", "c", "g", "t", "del", "ins", "starts", "ends")
+
+
+class Pileup(C.Structure):
+    _fields_ = [("n", C.c_uint64)] + [(f, C.POINTER(C.c_uint32)) for f in PILEUP_FIELDS]
+
+
 # int fn(void *user, const void *send, uint64 send_bytes, void *recv, const uint64 *recv_bytes)
 ALLGATHERV_FN = C.CFUNCTYPE(C.c_int, C.c_void_p, C.c_void_p, C.c_uint64, C.c_void_p, C.POINTER(C.c_uint64))
 
@@ -256,6 +264,9 @@ SIGNATURES = {
                                               _P(AlignScoring), C.c_int, _P(_P(Alignment))]),
     "rattle_hip_align_cigars_mode": (C.c_int, [C.c_void_p, _u8p, _u64p, C.c_uint32, _u8p, _u64p, C.c_uint32, _i32p, _u8p, _P(AlignParams),
                                                _P(AlignScoring), C.c_int, _P(_P(Alignment)), _P(_P(Cigars))]),
+    "rattle_hip_align_pileup": (C.c_int, [C.c_void_p, _u8p, _u64p, C.c_uint32, _u8p, _u64p, C.c_uint32, _i32p, _u8p, _P(AlignParams),
+                                          _P(AlignScoring), C.c_int, _P(_P(Alignment)), _P(_P(Cigars)), _P(_P(Pileup))]),
+    "rattle_hip_pileup_free": (None, [_P(Pileup)]),
     "rattle_hip_poa_msa": (C.c_int, [C.c_void_p, _u8p, _u64p, C.c_uint32, _u32p, C.c_uint32, _P(_P(MsaSet))]),
     "rattle_hip_msa_set_free": (None, [_P(MsaSet)]),
     "rattle_hip_correct_reads": (C.c_int, [C.c_void_p, _u8p, _u8p, _u64p, C.c_uint32, C.c_uint32, _u32p, _i32p, _u8p,

@@ -21,6 +21,7 @@ from ._lib import ClusterParams, ClusterSet, Correction, CorrectParams, MsaSet, 
 K_KMER, K_FILTER, K_SCORE, K_POA, K_POST, K_ASSIGN, K_ALIGN, K_CIGAR = 0, 1, 2, 3, 4, 5, 6, 7
 K_ALIGN_AFFINE, K_CIGAR_AFFINE = 8, 9          # the three-state forms of kernels E and F (align_pairs / align_cigars with a scoring)
 K_ABUNDANCE = 10                               # the EM of Context.abundance (csrc/abundance.hip)
+K_PILEUP = 11                                  # kernel G of Context.align_pileup (csrc/pair_pileup.hip)
 ALIGN_MODES = {"local": 0, "read": 1}         # RATTLE_ALIGN_LOCAL, RATTLE_ALIGN_READ
 
 
@@ -729,9 +730,10 @@ class Context:
         """align_pairs() on packed arrays (pack_reads)"""
         return self._align_packed(False, tcat, toff, rcat, roff, target_of_read, rev, max_cells, pair_chunk, scoring, mode)
 
-    def _align_packed(self, cigar: bool, tcat, toff, rcat, roff, target_of_read, rev, max_cells, pair_chunk, scoring, mode):
+    def _align_packed(self, cigar: bool, tcat, toff, rcat, roff, target_of_read, rev, max_cells, pair_chunk, scoring, mode, pileup=False):
         """The body of align_pairs_packed and (cigar) align_cigars_packed.  mode "local" goes to the calls without a mode -- the plain one
-        for scoring None, the _scored one else --, any other mode to the _mode call."""
+        for scoring None, the _scored one else --, any other mode to the _mode call.  pileup: rattle_hip_align_pileup, the one call
+        for every scoring and mode, with or without the CIGARs; returns (records, (offsets, ops) or None, table)."""
         M = self._align_mode(mode)
         P = _lib.AlignParams(int(max_cells), int(pair_chunk))
         n = len(roff) - 1
@@ -746,7 +748,11 @@ class Context:
         outs = (C.byref(out), C.byref(cg)) if cigar else (C.byref(out),)
         call = "rattle_hip_align_cigars" if cigar else "rattle_hip_align_pairs"
         S = None if scoring is None else self._scoring(scoring)
-        if M is not None:
+        pu = C.POINTER(_lib.Pileup)()
+        if pileup:
+            check(self.lib.rattle_hip_align_pileup(*args, None if S is None else C.byref(S), ALIGN_MODES["local"] if M is None else M,
+                                                   C.byref(out), C.byref(cg) if cigar else None, C.byref(pu)))
+        elif M is not None:
             check(getattr(self.lib, call + "_mode")(*args, None if S is None else C.byref(S), M, *outs))
         elif S is None:
             check(getattr(self.lib, call)(*args, *outs))
@@ -755,13 +761,35 @@ class Context:
         m = int(out.contents.n)
         res = {f: np.ctypeslib.as_array(getattr(out.contents, f), (max(m, 1),))[:m].copy() for f, _ in _lib.ALIGN_FIELDS}
         self.lib.rattle_hip_alignment_free(out)
+        table = None
+        if pileup:
+            N = int(pu.contents.n)
+            table = {f: np.ctypeslib.as_array(getattr(pu.contents, f), (max(N, 1),))[:N].copy() for f in _lib.PILEUP_FIELDS}
+            self.lib.rattle_hip_pileup_free(pu)
         if not cigar:
-            return res
+            return (res, None, table) if pileup else res
         offsets = np.ctypeslib.as_array(cg.contents.offset, (m + 1,)).copy()
         total = int(offsets[m])
         ops = np.ctypeslib.as_array(cg.contents.ops, (max(total, 1),))[:total].copy()
         self.lib.rattle_hip_cigars_free(cg)
-        return res, offsets, ops
+        return (res, (offsets, ops), table) if pileup else (res, offsets, ops)
+
+    def align_pileup(self, targets: Sequence[bytes], reads: Sequence[bytes], target_of_read, rev, max_cells=0, pair_chunk=0, scoring=None,
+                     mode="local", cigars=False):
+        """align_cigars(), and what the aligned reads say about every base of every target (rattle_hip_align_pileup, kernels E, F and
+        G).  Returns (records, cigars, table): the dict align_pairs returns for the same arguments; (offsets, ops) as align_cigars
+        returns them with cigars=True, else None -- the ops then never leave the device --; and a dict of eight uint32 arrays over the
+        concatenated targets (_lib.PILEUP_FIELDS; position p is byte p of b"".join(targets)), all on the target's strand: a, c, g, t
+        the read bases on '=' and 'X' columns, del the 'D' columns, ins the internal 'I' runs at the base to their right, starts and
+        ends the first and last column of every aligned read.  depth is a + c + g + t + del.  scoring and mode: as in align_pairs."""
+        tcat, toff = pack_reads(targets)
+        rcat, roff = pack_reads(reads)
+        return self.align_pileup_packed(tcat, toff, rcat, roff, target_of_read, rev, max_cells, pair_chunk, scoring, mode, cigars)
+
+    def align_pileup_packed(self, tcat: np.ndarray, toff: np.ndarray, rcat: np.ndarray, roff: np.ndarray, target_of_read, rev,
+                            max_cells=0, pair_chunk=0, scoring=None, mode="local", cigars=False):
+        """align_pileup() on packed arrays (pack_reads)"""
+        return self._align_packed(bool(cigars), tcat, toff, rcat, roff, target_of_read, rev, max_cells, pair_chunk, scoring, mode, pileup=True)
 
     def align_cigars(self, targets: Sequence[bytes], reads: Sequence[bytes], target_of_read, rev, max_cells=0, pair_chunk=0, scoring=None,
                      mode="local"):
@@ -1237,36 +1265,59 @@ def paf_ranked_text(read_names: Sequence[bytes], read_lengths: Sequence[int], ta
     return b"".join(lines)
 
 
+def pileup_tsv(target_names: Sequence[bytes], targets: Sequence[bytes], pileup: dict) -> bytes:
+    """pileup.tsv as `rattle assign --paf --pileup` writes it: a header, then one line per transcript position with depth > 0, in file
+    order: target, pos (0-based), ref (the transcript's byte as given), depth (A + C + G + T + del), A, C, G, T, del, ins, starts,
+    ends.  pileup: the table of Context.align_pileup over these targets.  A position of depth 0 has no line and no count."""
+    lines = [b"target\tpos\tref\tdepth\tA\tC\tG\tT\tdel\tins\tstarts\tends\n"]
+    planes = [np.asarray(pileup[f], np.int64) for f in _lib.PILEUP_FIELDS]
+    depth = planes[0] + planes[1] + planes[2] + planes[3] + planes[4]
+    base = 0
+    for name, s in zip(target_names, targets):
+        for pos in np.nonzero(depth[base:base + len(s)])[0]:
+            p = base + int(pos)
+            lines.append(b"%s\t%d\t%s\t%d\t%s\n" % (name, pos, s[pos:pos + 1], depth[p], b"\t".join(b"%d" % int(pl[p]) for pl in planes)))
+        base += len(s)
+    return b"".join(lines)
+
+
 def align_ranks(ctx: Context, targets: Sequence[bytes], reads: Sequence[bytes], cands: dict, max_cells=0, pair_chunk=0, cigar=False,
-                scoring=None, mode="local"):
+                scoring=None, mode="local", pileup=False):
     """Every read aligned to each of its candidates: one call of Context.align_pairs (cigar: align_cigars) per rank j, with slot j's
     target and strand as target_of_read and rev, up to the first rank no read has, every rank in the same `mode`.  Returns
-    (alignments, cigars): one record set per rank, and one (offsets, ops) per rank or None."""
-    alns, cgs = [], []
+    (alignments, cigars): one record set per rank, and one (offsets, ops) per rank or None.  pileup=True: rank 0's call is
+    Context.align_pileup, which returns the same records and CIGARs, and its table comes third (None if no read has a candidate)."""
+    alns, cgs, table = [], [], None
     for j in range(cands["target"].shape[1]):
         if not (np.asarray(cands["count"]) > j).any():
             break
         t = np.ascontiguousarray(cands["target"][:, j]); r = np.ascontiguousarray(cands["rev"][:, j])
-        if cigar:
+        if pileup and j == 0:
+            aln, cg, table = ctx.align_pileup(targets, reads, t, r, max_cells, pair_chunk, scoring, mode, cigars=cigar)
+            if cigar:
+                cgs.append(cg)
+        elif cigar:
             aln, offsets, ops = ctx.align_cigars(targets, reads, t, r, max_cells, pair_chunk, scoring, mode)
             cgs.append((offsets, ops))
         else:
             aln = ctx.align_pairs(targets, reads, t, r, max_cells, pair_chunk, scoring, mode)
         alns.append(aln)
-    return alns, (cgs if cigar else None)
+    return (alns, (cgs if cigar else None), table) if pileup else (alns, (cgs if cigar else None))
 
 
 def assign_paf_command(ctx: Context, read_headers: Sequence[bytes], reads: Sequence[bytes], target_headers: Sequence[bytes],
                        targets: Sequence[bytes], *, k=10, t_s=0.2, t_v=1000000.0, bv_threshold=0.4, is_rna=False, count_pass="auto",
                        target_batch=0, read_chunk=0, max_cells=0, pair_chunk=0, cigar=False, scoring=None, secondary=0,
-                       end_to_end=False, abundance=False, abundance_ratio=0.95, abundance_tol=1e-3, abundance_iters=1000):
+                       end_to_end=False, abundance=False, abundance_ratio=0.95, abundance_tol=1e-3, abundance_iters=1000, pileup=False):
     """`rattle assign --paf`: assign_command, then every placed read aligned to its transcript (Context.align_pairs).  Returns the bytes
     of assignments.tsv, target_counts.tsv and alignments.paf; the first two are what assign_command returns.  cigar=True is
     `--paf --cigar`: Context.align_cigars, and a cg:Z: tag on every line.  scoring=(m, x, o, e) is `--paf-scoring m,x,o,e`: affine gaps
     (Context.align_pairs); None is the linear default.  secondary=N (1..7) is `--secondary N`: every read is aligned to each of its
     N + 1 candidates (align_ranks), alignments.paf is the ranked one (paf_ranked_text) and the bytes of candidates.tsv come fourth.
     end_to_end=True is `--paf-end-to-end`: every alignment, of every rank, in mode "read" -- the whole read on every line; the tables
-    do not change.  abundance=True is `--abundance`, as for assign_command: the bytes of abundance.tsv come last, nothing else changes."""
+    do not change.  abundance=True is `--abundance`, as for assign_command: the bytes of abundance.tsv come last, nothing else changes.
+    pileup=True is `--pileup`: the alignment of every read on its transcript (rank 0 under `secondary`) is Context.align_pileup, with or
+    without `cigar`, and the bytes of pileup.tsv (pileup_tsv) come behind everything else; the other bytes do not change."""
     mode = "read" if end_to_end else "local"
     rec, cands, all8 = _assign_submitted(ctx, reads, targets, k, t_s, t_v, bv_threshold, is_rna, count_pass, target_batch, read_chunk, secondary,
                                           abundance)
@@ -1278,11 +1329,18 @@ def assign_paf_command(ctx: Context, read_headers: Sequence[bytes], reads: Seque
     tl = [len(s) for s in targets]
     rl = [len(s) for s in reads]
     if cands is not None:
-        alns, cgs = align_ranks(ctx, targets, reads, cands, max_cells, pair_chunk, cigar, scoring, mode)
+        alns, cgs, *table = align_ranks(ctx, targets, reads, cands, max_cells, pair_chunk, cigar, scoring, mode, pileup)
+        if pileup:
+            if table[0] is None:                # no read has a candidate: nothing was aligned
+                table = [{f: np.zeros(sum(tl), np.uint32) for f in _lib.PILEUP_FIELDS}]
+            last += (pileup_tsv(tn, targets, table[0]),)
         return (assignments_tsv(rn, tn, rec), target_counts_tsv(tn, tl, rec), paf_ranked_text(rn, rl, tn, tl, cands, alns, cgs),
                 candidates_tsv(rn, tn, cands)) + last
     cigars = None
-    if cigar:
+    if pileup:
+        aln, cigars, table = ctx.align_pileup(targets, reads, rec["target"], rec["rev"], max_cells, pair_chunk, scoring, mode, cigars=cigar)
+        last += (pileup_tsv(tn, targets, table),)
+    elif cigar:
         aln, offsets, ops = ctx.align_cigars(targets, reads, rec["target"], rec["rev"], max_cells, pair_chunk, scoring, mode)
         cigars = (offsets, ops)
     else:

@@ -845,6 +845,17 @@ int rattle_hip_align_pairs_scored(rattle_ctx *c, const uint8_t *tseq, const uint
     return align_entry({"align_pairs_scored", true, S, RATTLE_ALIGN_LOCAL}, c, tseq, toff, nt, rseq, roff, nr, target, rev, P, out, nullptr);
 }
 
+// the ops and counts of a finished run as the caller's arrays
+static rattle_cigars *cigars_from(const cigar_run &run, uint32_t nr) {
+    rattle_cigars *G = (rattle_cigars *)calloc(1, sizeof(rattle_cigars));
+    G->n = nr;
+    G->offset = (uint64_t *)calloc((size_t)nr + 1, 8);
+    G->ops = (uint32_t *)calloc(std::max<size_t>(1, run.ops.size()), 4);
+    for (uint32_t r = 0; r < nr; ++r) G->offset[r + 1] = G->offset[r] + run.count[r];
+    if (!run.ops.empty()) memcpy(G->ops, run.ops.data(), run.ops.size() * 4);
+    return G;
+}
+
 // the body of the three align_cigars calls: its own null argument, align_entry, and the ops as the caller's arrays
 static int cigars_entry(const align_request &Q, rattle_ctx *c, const uint8_t *tseq, const uint64_t *toff, uint32_t nt, const uint8_t *rseq, const uint64_t *roff,
                         uint32_t nr, const int32_t *target, const uint8_t *rev, const rattle_align_params *P, rattle_alignment **out,
@@ -854,13 +865,7 @@ static int cigars_entry(const align_request &Q, rattle_ctx *c, const uint8_t *ts
     if (!cigars) { set_error("null argument"); return RATTLE_ERR_ARG; }
     cigar_run run;
     RT_TRY(align_entry(Q, c, tseq, toff, nt, rseq, roff, nr, target, rev, P, out, &run));
-    rattle_cigars *G = (rattle_cigars *)calloc(1, sizeof(rattle_cigars));
-    G->n = nr;
-    G->offset = (uint64_t *)calloc((size_t)nr + 1, 8);
-    G->ops = (uint32_t *)calloc(std::max<size_t>(1, run.ops.size()), 4);
-    for (uint32_t r = 0; r < nr; ++r) G->offset[r + 1] = G->offset[r] + run.count[r];
-    if (!run.ops.empty()) memcpy(G->ops, run.ops.data(), run.ops.size() * 4);
-    *cigars = G;
+    *cigars = cigars_from(run, nr);
     return 0;
 }
 
@@ -887,6 +892,34 @@ int rattle_hip_align_cigars_mode(rattle_ctx *c, const uint8_t *tseq, const uint6
                                  uint32_t nr, const int32_t *target, const uint8_t *rev, const rattle_align_params *P, const rattle_align_scoring *S,
                                  int mode, rattle_alignment **out, rattle_cigars **cigars) {
     return cigars_entry(mode_request("align_cigars", S, mode), c, tseq, toff, nt, rseq, roff, nr, target, rev, P, out, cigars);
+}
+
+// align_cigars_mode, and kernel G's table of the same call; without `cigars` the ops stay on the device
+int rattle_hip_align_pileup(rattle_ctx *c, const uint8_t *tseq, const uint64_t *toff, uint32_t nt, const uint8_t *rseq, const uint64_t *roff,
+                            uint32_t nr, const int32_t *target, const uint8_t *rev, const rattle_align_params *P, const rattle_align_scoring *S,
+                            int mode, rattle_alignment **out, rattle_cigars **cigars, rattle_pileup **pileup) {
+    if (out) *out = nullptr;
+    if (cigars) *cigars = nullptr;
+    if (pileup) *pileup = nullptr;
+    if (!pileup) { set_error("null argument"); return RATTLE_ERR_ARG; }
+    cigar_run run;
+    run.want_pileup = true; run.keep_ops = cigars != nullptr;
+    const int rc = align_entry({"align_pileup", S != nullptr, S, mode}, c, tseq, toff, nt, rseq, roff, nr, target, rev, P, out, &run);
+    if (rc != 0) { free(run.h_pileup); return rc; }
+    if (cigars) *cigars = cigars_from(run, nr);
+    rattle_pileup *U = (rattle_pileup *)calloc(1, sizeof(rattle_pileup));
+    const uint64_t N = toff[nt];
+    U->n = N;
+    uint32_t **planes[8] = {&U->a, &U->c, &U->g, &U->t, &U->del, &U->ins, &U->starts, &U->ends};
+    for (uint32_t k = 0; k < 8; ++k) *planes[k] = run.h_pileup + k * N;      // one allocation: rattle_hip_pileup_free frees it through `a`
+    *pileup = U;
+    return 0;
+}
+
+void rattle_hip_pileup_free(rattle_pileup *u) {
+    if (!u) return;
+    free(u->a);
+    free(u);
 }
 
 void rattle_hip_cigars_free(rattle_cigars *g) {

@@ -129,7 +129,7 @@ struct hbuf {
     }
 };
 
-enum { K_KMER = 0, K_FILTER = 1, K_SCORE = 2, K_POA = 3, K_POST = 4, K_ASSIGN = 5, K_ALIGN = 6, K_CIGAR = 7, K_ALIGN_AFFINE = 8, K_CIGAR_AFFINE = 9, K_ABUNDANCE = 10, K_COUNT = 11 };
+enum { K_KMER = 0, K_FILTER = 1, K_SCORE = 2, K_POA = 3, K_POST = 4, K_ASSIGN = 5, K_ALIGN = 6, K_CIGAR = 7, K_ALIGN_AFFINE = 8, K_CIGAR_AFFINE = 9, K_ABUNDANCE = 10, K_PILEUP = 11, K_COUNT = 12 };
 
 struct kstat {
     double ms = 0;
@@ -545,8 +545,17 @@ struct cigar_run {                      // one call of rattle_hip_align_cigars: 
     hbuf<cigar_pair> h_pairs;
     hbuf<uint32_t> h_count, h_out;
     hbuf<uint64_t> h_off;
+    // rattle_hip_align_pileup alone (kernel G, pair_pileup.hip); the align_cigars calls leave all of it as it stands here
+    bool want_pileup = false;           // align_pairs_run makes the two tables below and hands h_pileup on filled
+    bool keep_ops = true;               // false: the compact ops stay on the device: `ops` stays empty, `count` is filled for the pairs that
+                                        // went to kernel F and stays 0 for a read-mode pair without a column (cigar_no_column is not run)
+    uint32_t *h_pileup = nullptr;       // calloc'ed, the caller's to free: 8 planes of target_offsets[n_targets] counts, position p = byte p
+    uint32_t *d_pileup = nullptr;       // 8 planes of pileup_n counts, position 0 = the first uploaded target byte (d_t)
+    uint64_t pileup_n = 0;
 };
 uint64_t cigar_code_cap();              // 4 GiB, or what RATTLE_CIGAR_CODE_BYTES says
+// pair_pileup.hip : kernel G over the m pairs of the sub-chunk that pair_cigar_chunk has just gathered (R.d_pairs, R.d_off, R.d_out), into R.d_pileup
+int pair_pileup_launch(rattle_ctx *ctx, const cigar_run &R, uint32_t m, const uint8_t *d_q, uint64_t alg);
 // scoring == nullptr: the linear form (GAP_LINEAR of pair_wave.h, id 7); else the affine form with that scoring (GAP_AFFINE, id 9)
 int pair_cigar_chunk(rattle_ctx *ctx, const uint8_t *d_q, const uint8_t *d_t, const cigar_in *in, uint32_t n, uint32_t pair_chunk, cigar_run &R,
                      const rattle_align_scoring *scoring = nullptr, int mode = RATTLE_ALIGN_LOCAL);

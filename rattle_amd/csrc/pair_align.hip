@@ -211,6 +211,8 @@ __global__ __launch_bounds__(256) void pair_align_kernel(const align_pair *__res
 // (rattle_hip_align_*_scored) the form is GAP_AFFINE, the launches are those of the <true> kernels; the plan, the uploads and the records are the
 // same, the strip's records are 40 bytes.  With mode RATTLE_ALIGN_READ (rattle_hip_align_*_mode) the launches are those of the <*, true>
 // kernels under the ids of their gap form; every submitted pair comes back with status 0 and the rectangle (0, Lq] x (t_start, t_end].
+// With cigars->want_pileup (rattle_hip_align_pileup) the call also owns kernel G's table (pair_pileup.hip): eight planes over the uploaded
+// targets on the device, zeroed here, added to by every sub-chunk of pair_cigar_chunk, copied once into cigars->h_pileup at the end.
 int align_pairs_run(rattle_ctx *ctx, const uint8_t *tseq, const uint64_t *toff, uint32_t nt, const uint8_t *rseq, const uint64_t *roff, uint32_t nr,
                     const int32_t *target, const uint8_t *rev, const rattle_align_params *AP, rattle_alignment *A, cigar_run *cigars, const rattle_align_scoring *scoring,
                     int mode) {
@@ -219,6 +221,11 @@ int align_pairs_run(rattle_ctx *ctx, const uint8_t *tseq, const uint64_t *toff, 
     align_plan plan;
     plan_align(toff, roff, nr, target, AP->max_cells, AP->pair_chunk ? AP->pair_chunk : 32768u, (1ull << 30) / F.strip_bytes /* 1 GiB of records */, plan);
     for (uint32_t r = 0; r < nr; ++r) A->status[r] = plan.status[r];
+    const bool pileup = cigars && cigars->want_pileup;
+    if (pileup) {                                                    // the host table: zero wherever nothing is counted
+        cigars->h_pileup = (uint32_t *)calloc(std::max<uint64_t>(1, 8 * toff[nt]), 4);
+        if (!cigars->h_pileup) { set_error("align_pileup: out of memory (the table of " + std::to_string(toff[nt]) + " positions)"); return RATTLE_ERR_HIP; }
+    }
     if (plan.sub.empty()) return 0;
     const std::vector<uint32_t> &sub = plan.sub, &first = plan.first;
     const std::vector<uint64_t> &strip_len = plan.strip;
@@ -232,6 +239,12 @@ int align_pairs_run(rattle_ctx *ctx, const uint8_t *tseq, const uint64_t *toff, 
     hbuf<int32_t> h_rec;
     RT_TRY(d_t.reserve(tbytes));
     RT_HIP(hipMemcpyAsync(d_t.p, tseq + t0, tbytes, hipMemcpyHostToDevice, ctx->stream));
+    dbuf<uint32_t> d_pile;                                           // kernel G's table: zeroed once, added to by every sub-chunk, copied back once
+    if (pileup) {
+        RT_TRY(d_pile.reserve(8 * tbytes));
+        RT_HIP(hipMemsetAsync(d_pile.p, 0, 8 * tbytes * 4, ctx->stream));
+        cigars->d_pileup = d_pile.p; cigars->pileup_n = tbytes;
+    }
     for (size_t c = 0; c + 1 < first.size(); ++c) {
         const uint32_t a = first[c], n = first[c + 1] - a;
         // the chunk's reads: one span of the caller's buffer, from its first submitted read to its last
@@ -288,6 +301,17 @@ int align_pairs_run(rattle_ctx *ctx, const uint8_t *tseq, const uint64_t *toff, 
             }
             RT_TRY(pair_cigar_chunk(ctx, d_q.p, d_t.p, in.data(), n, AP->pair_chunk ? AP->pair_chunk : 32768u, *cigars, scoring, mode));
         }
+    }
+    if (pileup) {
+        // plane k of the device table is positions [t0, t0 + tbytes) of plane k of the caller's; the ins adds of id 11's alg_bytes, 4 bytes each
+        const uint64_t N = toff[nt];
+        cigars->d_pileup = nullptr;
+        for (uint32_t k = 0; k < 8; ++k)
+            RT_HIP(hipMemcpyAsync(cigars->h_pileup + k * N + t0, d_pile.p + k * tbytes, tbytes * 4, hipMemcpyDeviceToHost, ctx->stream));
+        RT_HIP(hipStreamSynchronize(ctx->stream));
+        uint64_t ins = 0;
+        for (uint64_t i = 0; i < N; ++i) ins += cigars->h_pileup[5 * N + i];
+        ctx->stats[K_PILEUP].bytes += 4 * ins;
     }
     return 0;
 }

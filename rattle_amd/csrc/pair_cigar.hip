@@ -276,7 +276,9 @@ static void cigar_no_column(const cigar_in *in, uint32_t n, cigar_run &R, size_t
 // The pairs `in` of one chunk of kernel E, whose sequences lie in d_q and d_t: the ops of every pair with status 0 appended to R.ops, their
 // number to R.count[read].  Sub-chunks as cigar_plan.h plans them; per sub-chunk one launch of kernel F (id 7 of the stats), the counts to
 // the host, offsets from them, one gather launch, and the compact ops back.  With `scoring` the form is GAP_AFFINE (id 9): the <true>
-// kernel, 32-byte records, two strip words per column; everything around it is the same.
+// kernel, 32-byte records, two strip words per column; everything around it is the same.  With R.d_pileup (rattle_hip_align_pileup) one
+// launch of kernel G (pair_pileup.hip, id 11) follows the gather of every sub-chunk that has an op, and without R.keep_ops the compact
+// ops are not copied back; the align_cigars calls set neither and launch, allocate and copy what they always did.
 int pair_cigar_chunk(rattle_ctx *ctx, const uint8_t *d_q, const uint8_t *d_t, const cigar_in *in, uint32_t n, uint32_t pair_chunk, cigar_run &R,
                      const rattle_align_scoring *scoring, int mode) {
     const gap_form &F = scoring ? GAP_AFFINE : GAP_LINEAR;
@@ -331,15 +333,27 @@ int pair_cigar_chunk(rattle_ctx *ctx, const uint8_t *d_q, const uint8_t *d_t, co
         ctx->stats[F.k_cigar].bytes += 4 * total;                    // ... and 4 bytes per op
         if (!total) continue;
         RT_TRY(R.d_out.reserve(total));
-        RT_TRY(R.h_out.reserve(total));
+        if (R.keep_ops) RT_TRY(R.h_out.reserve(total));
         RT_HIP(hipMemcpyAsync(R.d_off.p, R.h_off.p, ((size_t)m + 1) * 8, hipMemcpyHostToDevice, ctx->stream));
         hipLaunchKernelGGL(cigar_gather_kernel, dim3((m + 3) / 4), dim3(256), 0, ctx->stream, R.d_pairs.p, m, R.d_off.p, R.d_ops.p, R.d_out.p);
         RT_HIP(hipGetLastError());
-        RT_HIP(hipMemcpyAsync(R.h_out.p, R.d_out.p, total * 4, hipMemcpyDeviceToHost, ctx->stream));
+        if (R.d_pileup) {
+            // kernel G (pair_pileup.hip, id 11) behind the gather: per pair the ops and read bases read, the adds made -- one per column
+            // with a target base (= cols of a path that ends in the rectangle's corners) and two for starts and ends; the ins adds are
+            // counted when the table is back (align_pairs_run).  Every rectangle's columns lie inside a plane, or nothing is launched
+            uint64_t g = 4 * total;
+            for (uint32_t i = 0; i < m; ++i) {
+                const cigar_in &I = in[plan.sub[a + i]];
+                if (I.t > R.pileup_n || I.cols > R.pileup_n - I.t) { set_error("align_pileup: a rectangle lies outside the table"); return RATTLE_ERR_HIP; }
+                g += (uint64_t)I.rows + 4 * ((uint64_t)I.cols + 2);
+            }
+            RT_TRY(pair_pileup_launch(ctx, R, m, d_q, g));
+        }
+        if (R.keep_ops) RT_HIP(hipMemcpyAsync(R.h_out.p, R.d_out.p, total * 4, hipMemcpyDeviceToHost, ctx->stream));
         RT_HIP(hipStreamSynchronize(ctx->stream));
-        R.ops.insert(R.ops.end(), R.h_out.p, R.h_out.p + total);
+        if (R.keep_ops) R.ops.insert(R.ops.end(), R.h_out.p, R.h_out.p + total);
     }
-    if (mode == RATTLE_ALIGN_READ) cigar_no_column(in, n, R, ops_before);
+    if (mode == RATTLE_ALIGN_READ && R.keep_ops) cigar_no_column(in, n, R, ops_before);
     return 0;
 }
 

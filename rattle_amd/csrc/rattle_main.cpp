@@ -795,7 +795,10 @@ struct assign_job {
     bool want_abundance = false;                  // --abundance: the candidate list with 8 slots, the EM over it, abundance.tsv
     rattle_abundance_params EP;
     rattle_abundance *E = nullptr;
+    bool want_pileup = false;                     // --pileup: the alignment of every read on its transcript also fills kernel G's table
+    rattle_pileup *U = nullptr;
     std::string text, counts, paf, cand, abund;   // assignments.tsv, target_counts.tsv, alignments.paf (--paf), candidates.tsv (--secondary), abundance.tsv (--abundance)
+    std::string pile;                             // pileup.tsv (--pileup)
     void options(int argc, char **argv) {
         a = parse(argc, argv, {
             {"help", {"-h", "--help"}, false}, {"input", {"-i", "--input"}, true}, {"targets", {"-x", "--transcripts"}, true},
@@ -806,8 +809,8 @@ struct assign_job {
             {"paf-max-cells", {"--paf-max-cells"}, true}, {"cigar", {"--cigar"}, false}, {"paf-scoring", {"--paf-scoring"}, true},
             {"secondary", {"--secondary"}, true}, {"paf-end-to-end", {"--paf-end-to-end"}, false}, {"abundance", {"--abundance"}, false},
             {"abundance-ratio", {"--abundance-ratio"}, true}, {"abundance-tol", {"--abundance-tol"}, true},
-            {"abundance-iters", {"--abundance-iters"}, true}});
-        const char *usage = "rattle assign -i reads.fq -x transcripts.fq [-o dir] [-k 10] [-s 0.2] [-v 1000000] [-B 0.4] [--rna] [--device n] [--paf [--cigar]] [--secondary n] [--abundance]\n"
+            {"abundance-iters", {"--abundance-iters"}, true}, {"pileup", {"--pileup"}, false}});
+        const char *usage = "rattle assign -i reads.fq -x transcripts.fq [-o dir] [-k 10] [-s 0.2] [-v 1000000] [-B 0.4] [--rna] [--device n] [--paf [--cigar] [--pileup]] [--secondary n] [--abundance]\n"
                             "  places every read of -i on the transcript of -x that accepts it with the best score (the comparison `cluster` joins\n"
                             "  reads by, the transcript in the seed's role) and writes assignments.tsv (one line per read: target, strand, score,\n"
                             "  second_score, n_accepted, bases, hc_bases, min_len, variance) and target_counts.tsv (reads per transcript)\n"
@@ -824,6 +827,11 @@ struct assign_job {
                             "  --paf-end-to-end                      with --paf: align every read from its first base to its last, the transcript's ends free\n"
                             "                                        (semi-global): nothing is clipped, an overhang or a foreign exon shows as I or X at the\n"
                             "                                        line's end, AS may be negative, and the AS of --secondary's ranks are comparable\n"
+                            "  --pileup                              with --paf: also write pileup.tsv, one line per transcript position that a read covers:\n"
+                            "                                        target, pos (0-based), ref, depth, A, C, G, T (the reads' bases there, on the transcript's\n"
+                            "                                        strand), del, ins (insertions before this base), starts, ends (alignments that begin / end\n"
+                            "                                        here).  Counted on the device from the alignments of alignments.paf (with --secondary: the\n"
+                            "                                        tp:A:P lines); --cigar is not needed.  The other files do not change\n"
                             "  --secondary n                         n in 1..7: also write candidates.tsv, the best transcript of every read and its n next-best\n"
                             "                                        (one line per read and rank: read, rank, target, strand, score, bases, hc_bases, min_len,\n"
                             "                                        variance); with --paf every one of them is aligned, and each line of alignments.paf carries\n"
@@ -868,6 +876,8 @@ struct assign_job {
         }
         want_ends = a.has("paf-end-to-end");
         if (want_ends && !want_paf) die("\nError: --paf-end-to-end needs --paf\n");
+        want_pileup = a.has("pileup");
+        if (want_pileup && !want_paf) die("\nError: --pileup needs --paf\n");
         if (a.has("secondary")) {
             const std::string v = a.str("secondary", "");
             if (v.size() != 1 || v[0] < '1' || v[0] > '7') die("\nError: --secondary takes a number of further transcripts per read in 1..7\n");
@@ -932,12 +942,14 @@ struct assign_job {
     }
     // the ranks the writers of --secondary see: the list holds 8 under --abundance, and its first ranks are what the shorter list holds
     uint32_t ranks() const { return std::min(C->k, secondary + 1); }
-    // the submitted reads on target[r] / rev[r] each (-1: not aligned): one call of the library
-    void align_on(const int32_t *target, const uint8_t *rev, rattle_alignment **L, rattle_cigars **G) {
+    // the submitted reads on target[r] / rev[r] each (-1: not aligned): one call of the library; with `table` (--pileup, the reads on
+    // their own transcripts) the call that also counts, which returns the same records and, under --cigar, the same ops
+    void align_on(const int32_t *target, const uint8_t *rev, rattle_alignment **L, rattle_cigars **G, rattle_pileup **table = nullptr) {
         const rattle_align_scoring *S = want_scoring ? &AS : nullptr;
         const int mode = want_ends ? RATTLE_ALIGN_READ : RATTLE_ALIGN_LOCAL;      // (local through the _mode calls is the plain call, name and all)
         const uint32_t nt = (uint32_t)xid.size(), nr = (uint32_t)rid.size();
-        if (want_cigar) chk(rattle_hip_align_cigars_mode(team.ctx[0], xcat.data(), xoff.data(), nt, rcat.data(), roff.data(), nr, target, rev, &AP, S, mode, L, G));
+        if (table) chk(rattle_hip_align_pileup(team.ctx[0], xcat.data(), xoff.data(), nt, rcat.data(), roff.data(), nr, target, rev, &AP, S, mode, L, want_cigar ? G : nullptr, table));
+        else if (want_cigar) chk(rattle_hip_align_cigars_mode(team.ctx[0], xcat.data(), xoff.data(), nt, rcat.data(), roff.data(), nr, target, rev, &AP, S, mode, L, G));
         else chk(rattle_hip_align_pairs_mode(team.ctx[0], xcat.data(), xoff.data(), nt, rcat.data(), roff.data(), nr, target, rev, &AP, S, mode, L));
     }
     // the PAF line of submitted read `at` on transcript x; tags: what stands between nd:i: and cg:Z:
@@ -959,10 +971,10 @@ struct assign_job {
     }
     // --paf: the submitted reads on the transcripts `run` placed them on; one PAF line per read that aligns, in file order
     void align() {
-        cli_timer t(want_cigar ? "library: align_cigars" : "library: align_pairs");
+        cli_timer t(want_pileup ? "library: align_pileup" : want_cigar ? "library: align_cigars" : "library: align_pairs");
         rattle_alignment *L = nullptr;
         rattle_cigars *G = nullptr;
-        align_on(A->target, A->rev, &L, &G);
+        align_on(A->target, A->rev, &L, &G, want_pileup ? &U : nullptr);
         uint64_t skipped = 0;
         for (uint32_t at = 0; at < L->n; ++at) {
             skipped += L->status[at] == 2;
@@ -975,7 +987,8 @@ struct assign_job {
     // --paf --secondary: one call per rank, every read on its slot of that rank, up to the first rank no read has; then one PAF line
     // per (read, rank) that aligns, in file order and then by rank
     void align_ranks() {
-        cli_timer t(want_cigar ? "library: align_cigars, every rank" : "library: align_pairs, every rank");
+        cli_timer t(want_pileup ? (want_cigar ? "library: align_pileup (rank 0), align_cigars, every rank" : "library: align_pileup (rank 0), align_pairs, every rank")
+                                : want_cigar ? "library: align_cigars, every rank" : "library: align_pairs, every rank");
         const uint32_t n = C->n, K = C->k;
         std::vector<rattle_alignment *> L;
         std::vector<rattle_cigars *> G;
@@ -986,7 +999,7 @@ struct assign_job {
             for (uint32_t r = 0; r < n; ++r) { target[r] = C->target[(size_t)r * K + j]; rev[r] = C->rev[(size_t)r * K + j]; any = any || C->count[r] > j; }
             if (!any) break;
             L.push_back(nullptr); G.push_back(nullptr);
-            align_on(target.data(), rev.data(), &L.back(), &G.back());
+            align_on(target.data(), rev.data(), &L.back(), &G.back(), want_pileup && j == 0 ? &U : nullptr);      // rank 0: the tp:A:P alignments
         }
         uint64_t skipped = 0;
         for (uint32_t at = 0; at < n; ++at)
@@ -998,6 +1011,24 @@ struct assign_job {
             }
         for (size_t j = 0; j < L.size(); ++j) { rattle_hip_alignment_free(L[j]); rattle_hip_cigars_free(G[j]); }
         if (skipped) std::cerr << "\n" << skipped << "  pairs over --paf-max-cells are left out of alignments.paf" << std::endl;
+    }
+    // --pileup: one line per transcript position a read covers, in file order (no table: nothing was aligned)
+    void format_pileup() {
+        pile = "target\tpos\tref\tdepth\tA\tC\tG\tT\tdel\tins\tstarts\tends\n";
+        uint64_t covered = 0, deepest = 0;
+        for (size_t x = 0; U && x < xid.size(); ++x) {
+            const std::string name = record_name(X.header[xid[x]]);
+            for (uint64_t p = xoff[x]; p < xoff[x + 1] && p < U->n; ++p) {
+                const uint64_t depth = (uint64_t)U->a[p] + U->c[p] + U->g[p] + U->t[p] + U->del[p];
+                if (!depth) continue;
+                ++covered; deepest = std::max(deepest, depth);
+                pile += name + "\t" + std::to_string(p - xoff[x]) + "\t" + std::string(1, (char)xcat.data()[p]) + "\t" + std::to_string(depth) + "\t" + std::to_string(U->a[p]) + "\t" +
+                        std::to_string(U->c[p]) + "\t" + std::to_string(U->g[p]) + "\t" + std::to_string(U->t[p]) + "\t" + std::to_string(U->del[p]) + "\t" +
+                        std::to_string(U->ins[p]) + "\t" + std::to_string(U->starts[p]) + "\t" + std::to_string(U->ends[p]) + "\n";
+            }
+        }
+        rattle_hip_pileup_free(U);
+        std::cerr << "pileup: " << covered << " transcript positions covered, largest depth " << deepest << std::endl;
     }
     // --secondary: one line per filled slot, in file order of the reads, then by rank
     void format_candidates() {
@@ -1043,6 +1074,7 @@ struct assign_job {
         if (want_paf) write_text(outdir + "/alignments.paf", paf);
         if (secondary) write_text(outdir + "/candidates.tsv", cand);
         if (want_abundance) write_text(outdir + "/abundance.tsv", abund);
+        if (want_pileup) write_text(outdir + "/pileup.tsv", pile);
         team.close();
         std::cerr << "Done" << std::endl;
     }
@@ -1055,6 +1087,7 @@ int mode_assign(int argc, char **argv) {
     J.run();
     if (J.want_abundance) J.estimate();
     if (J.want_paf) { if (J.secondary) J.align_ranks(); else J.align(); }
+    if (J.want_pileup) J.format_pileup();
     if (J.secondary) J.format_candidates();
     J.format();
     J.write();
