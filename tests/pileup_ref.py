@@ -19,7 +19,10 @@ nothing.  depth = a + c + g + t + del.
   identities(table, records)                                         the four sums the header promises, as a list of what fails
   model(case, sc, mode)                                              (records, CIGAR strings, table) of a case from tests/align_model.py
 
-and the cases aimed at kernel G's own edges: rounds of 64 ops, column steps of 64, many reads on few positions, neighbouring targets.
+and the cases aimed at kernel G's own edges: rounds of 64 ops, column steps of 64, many reads on few positions, neighbouring targets;
+ins_pairs(), one interior I op at a chosen op index -- 1, 63, 64, 65, 127, 128, the last but one, with the op count on a round's edge,
+beside a read-mode overhang that is alone in its round or is op 0 -- each with the position it counts at; reverse_given(), a read as it
+is handed over on the other strand; gap_contention_case(), 4096 reads with a D run and an I run on the same positions.
 No device, no numpy in the walk."""
 import re
 
@@ -149,6 +152,89 @@ def op_count_pairs():
 
 def n_ops(q, t, sc, mode):
     return len(M.pair(q, t, 0, sc, mode)[1])
+
+
+def ins_pair(L: int, at: int, base: bytes, extra=None, lead=b"", trail=b"", seed=7):
+    """(read, target): thirds_pair(L, seed, extra) with `base` put into the read in front of its base `at` -- one I op between the
+    2= and 1X runs, at about op 2 at / 3 -- and with `lead` in front of the read and `trail` behind it (read mode: the overhangs)"""
+    q, t = thirds_pair(L, seed, extra)
+    return lead + q[:at] + base + q[at:] + trail, t
+
+
+# name -> (arguments of ins_pair, {mode: (ops, index of the one interior I op, target position that op counts at)}).  A round of kernel
+# G takes 64 ops, so index 63 is the last lane of round 0, 64 the first of round 1, 127 and 128 the same one round on; `ops - 2` is the
+# last op that can count.  `extra` shifts the parity of the later indices: without it every I op of these pairs has an odd index.
+# The numbers are what tests/align_model.py gives, found once by a search over `at`, `base` and `extra`; ins_pairs() asserts them.
+INS_PAIRS = {
+    "index_1": ((200, 2, b"G"), {M.LOCAL: (133, 1, 3), M.READ: (133, 1, 3)}),
+    "index_63": ((200, 95, b"G"), {M.LOCAL: (133, 63, 96), M.READ: (133, 63, 96)}),
+    "index_63_of_65": ((98, 95, b"G"), {M.LOCAL: (65, 63, 96), M.READ: (65, 63, 96)}),           # the one op behind it is in round 1
+    "index_64": ((200, 94, b"G", 20), {M.LOCAL: (134, 64, 96), M.READ: (134, 64, 96)}),
+    "index_64_of_66": ((98, 94, b"G", 20), {M.LOCAL: (66, 64, 96), M.READ: (66, 64, 96)}),       # lane 0 of round 1, one op behind it
+    "index_65": ((200, 94, b"G", 50), {M.LOCAL: (135, 65, 96), M.READ: (135, 65, 96)}),
+    "index_127": ((200, 191, b"T"), {M.LOCAL: (133, 127, 192), M.READ: (133, 127, 192)}),
+    "index_127_of_129": ((193, 191, b"T"), {M.READ: (129, 127, 192)}),
+    "index_128": ((200, 190, b"T", 20), {M.LOCAL: (134, 128, 192), M.READ: (134, 128, 192)}),
+    "index_131_of_133": ((200, 197, b"A"), {M.LOCAL: (133, 131, 198), M.READ: (133, 131, 198)}),
+    # read mode: an overhang that is op 64 of 65, alone in round 1, and one that is op 0 of 134; neither counts, the I inside does
+    "trailing_overhang": ((95, 50, b"G", None, b"", b"GTTGTTT"), {M.READ: (65, 33, 50)}),
+    "leading_overhang": ((200, 95, b"G", None, b"CTT"), {M.READ: (134, 64, 96)}),
+}
+INS_SCORING = {M.LOCAL: LINEAR, M.READ: ENGINE}
+
+
+def interior_ins(ops):
+    """[(index, target columns in front of it)] of the I ops that are neither the first nor the last op"""
+    out, cols = [], 0
+    for k, (o, n) in enumerate(ops):
+        if o == "I" and 0 < k < len(ops) - 1:
+            out.append((k, cols))
+        if o != "I":
+            cols += n
+    return out
+
+
+INS_FORMS = tuple((name, mode) for name, (_, forms) in INS_PAIRS.items() for mode in forms)
+
+
+def ins_pairs(name, mode):
+    """(scoring, ops, index, position, read, target) of INS_PAIRS[name] under `mode`, asserted through the model: that many ops, one
+    interior I op, at that index, counted at that target position; the overhang pairs begin or end with an I op, no other does"""
+    args, forms = INS_PAIRS[name]
+    ops, index, position = forms[mode]
+    q, t = ins_pair(*args)
+    rec, got = M.pair(q, t, 0, INS_SCORING[mode], mode)
+    assert len(got) == ops and interior_ins(got) == [(index, position - rec[4])], (name, mode, len(got), interior_ins(got), rec[4])
+    assert (got[0][0] == "I") == (name == "leading_overhang") and (got[-1][0] == "I") == (name == "trailing_overhang"), name
+    return INS_SCORING[mode], ops, index, position, q, t
+
+
+def reverse_given(q: bytes) -> bytes:
+    """the read as it is handed over for rev = 1: reverse-complemented and written with U"""
+    return R.revcomp(q).replace(b"T", b"U")
+
+
+GAP_COPIES = 4096
+
+
+def gap_contention_pair(seed=58):
+    """(read, target): a target of 101 bases and the 100-base read that lacks its bases 35 .. 37 and holds two more in front of its
+    base 70; under 5,4,8,6 the flanks of 35, 32 and 31 carry both gaps: 35=3D32=2I31= (asserted where it is used)"""
+    rng = np.random.default_rng(seed)
+    t = R.rnd(rng, 101)
+    extra = bytes([_other(t[70]), _other(t[70], 2)])
+    return t[:35] + t[38:70] + extra + t[70:], t
+
+
+GAP_CONTENTION_CIGAR = b"35=3D32=2I31="
+
+
+def gap_contention_case(seed=58):
+    """4096 copies of gap_contention_pair's read on its target, every second one handed over on the other strand"""
+    q, t = gap_contention_pair(seed)
+    back = reverse_given(q)
+    n = GAP_COPIES
+    return [t], [back if r % 2 else q for r in range(n)], [0] * n, [r % 2 for r in range(n)]
 
 
 def identical_case(seed=51):

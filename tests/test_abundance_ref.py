@@ -53,6 +53,81 @@ def test_the_two_forms_agree_on_lists_no_assignment_would_make():
         assert e["iterations"] == 0 and e["converged"] == 1 and len(e["units"]) == 0
 
 
+def agree(cands, nt, label, **kw):
+    a, b = ref.scalar(cands, nt, **kw), ref.vector(cands, nt, **kw)
+    assert ref.same(a, b) is None, (label, ref.same(a, b))
+    assert int(a["units"].sum()) == a["n_placed"] * ONE, label
+    return a
+
+
+@pytest.mark.parametrize("nt,empties,unnamed",
+                         [(nt, e, None) for nt in ref.SCAN_NT for e in (False, True)] + [(nt, True, u) for nt, u in ref.SCAN_UNNAMED])
+def test_scan_rounds_case_names_targets_on_both_sides_of_every_round_edge(nt, empties, unnamed):
+    cands = ref.scan_rounds_case(nt, empties, unnamed)
+    assert ref.scan_rounds_holds(cands, nt, empties, unnamed)
+    assert not ref.scan_rounds_holds(cands, nt, not empties, unnamed)
+    t0 = ref.slot0(cands)
+    assert 600 < len(t0) <= 700 == len(cands["count"]) and cands["target"].shape == (700, 4) and t0.max() == nt - 1
+    for first in range(0, nt, ref.SCAN):                                 # every round the scan takes over the targets holds reads
+        assert ((t0 >= first) & (t0 < first + ref.SCAN)).any()
+    if unnamed is not None:
+        assert ref.scan_rounds_holds(ref.scan_rounds_case(nt, empties), nt, empties) and (ref.scan_rounds_case(nt, empties)["target"] == unnamed).any()
+    r = agree(cands, nt, "scan rounds", max_iters=12)
+    assert r["n_placed"] == len(t0) and (unnamed is None or r["units"][unnamed] == 0)
+
+
+def test_leftover_and_spread_cases_hold_more_than_eight_distinct_targets_where_they_say():
+    for distinct in (9, 8):
+        cands = ref.leftover_case(distinct)
+        assert ref.leftover_holds(cands, distinct) and not ref.leftover_holds(cands, 17 - distinct)
+        assert np.bincount(cands["target"][:64, 1][cands["target"][:64, 1] >= 0]).tolist()[1:] == ([7] * 9 if distinct == 9 else [8] * 7 + [7])
+        r = agree(cands, ref.LEFTOVER_NT, "leftover")
+        assert r["converged"] == 1 and r["n_placed"] == 94
+    for alone_every in (0, 5):
+        cands = ref.spread_case(alone_every)
+        assert ref.spread_holds(cands, alone_every) and not ref.spread_holds(cands, 5 - alone_every)
+        target = cands["target"]
+        for j in range(1, 8):
+            assert np.bincount(target[:, j][target[:, j] >= 0]).max() <= 7
+        assert all(len(set(row[row >= 0])) == (row >= 0).sum() for row in target)         # a read names a target once
+        assert (target[::5, 1:] < 0).all() == bool(alone_every) and target.max() == 300
+        agree(cands, ref.SPREAD_NT, "spread", max_iters=60)
+
+
+def test_the_cases_of_whole_empty_wavefronts():
+    cands, nt = ref.empty_wavefront_case()
+    assert ref.empty_wavefronts(cands) == 2 and (cands["count"] > 0).sum() == 100 and len(cands["count"]) == 300
+    r = agree(cands, nt, "empties", max_iters=60)
+    assert r["iterations"] > 3 and r["n_placed"] == 100
+    cands, nt = ref.run_to_the_edge_case()
+    t0 = ref.slot0(cands)
+    assert ref.empty_wavefronts(cands) == 1 and np.bincount(t0).tolist() == [62, 130] and (62 + 130) % ref.WAVE == 0
+    r = agree(cands, nt, "run to the edge", max_iters=60)
+    assert r["iterations"] > 3 and r["n_placed"] == 192
+
+
+def test_the_odd_lists_hold_a_target_twice_a_hole_and_a_negative_best_score():
+    for k in (4, 8):
+        cands = ref.odd_lists(k)
+        assert ref.odd_holds(cands) == (True, True, True)
+        agree(cands, ref.ODD_NT, "odd lists", ratio=ref.ODD_RATIO, max_iters=50)
+    assert ref.odd_holds(ref.lists(200, 8, 40, np.random.default_rng(2))) == (False, False, False)
+    cands = ref.odd_hand()
+    assert ref.odd_holds(cands) == (True, True, False)
+    r = agree(cands, ref.ODD_NT, "odd lists by hand", ratio=ref.ODD_RATIO, max_iters=50)
+    assert r["compatible_reads"].tolist() == ref.ODD_HAND_COMPATIBLE == [1, 1, 1, 1, 0, 1]
+    assert r["units"].tolist()[2] == ONE and r["units"][1] + r["units"][3] == ONE and r["units"][0] + r["units"][5] == ONE
+
+
+def test_beyond_2_53_case_is_what_it_says_without_running_it():
+    """(the run itself takes the vector form two seconds: tests/test_gpu_abundance_edges.py makes it, once per variant)"""
+    for handing_over in (0, 10):
+        cands = ref.beyond_2_53_case(handing_over)
+        assert len(cands["count"]) == ref.BEYOND_N + handing_over and ref.BEYOND_N * ONE > 2 ** 53 >= (1 << 21) * ONE
+        assert (cands["count"] == 2).sum() == 3000 + handing_over and (cands["target"][:ref.BEYOND_N, 0] == 0).all()
+        assert cands["target"][ref.BEYOND_N:].tolist() == [[1, 0]] * handing_over
+
+
 def test_the_worked_example_converges_to_six_and_two():
     r = ref.scalar(example(), 2)
     assert r["converged"] == 1 and r["iterations"] == 10 and r["n_placed"] == 8

@@ -94,6 +94,59 @@ def test_op_count_pairs_have_the_intended_number_of_ops(name):
     assert P.identities(planes, records) == []
 
 
+@pytest.mark.parametrize("name,mode", P.INS_FORMS)
+def test_ins_pairs_hold_one_interior_i_op_at_the_index_they_are_named_for(name, mode):
+    sc, ops, index, position, q, t = P.ins_pairs(name, mode)             # (asserts count, index and position through the model)
+    named = name.split("_")
+    if named[0] == "index":
+        assert index == int(named[1]) and (len(named) == 2 or ops == int(named[3]))
+    texts = M.cigars(*R.pairs_case([(q, t, 0)]), sc, mode)
+    parsed = P.parse(texts[0])
+    assert len(parsed) == ops and [k for k, (o, _) in enumerate(parsed) if o == b"I" and 0 < k < ops - 1] == [index]
+    if name == "trailing_overhang":
+        assert ops == 65 and parsed[64] == (b"I", 7) and index < 64      # the overhang is alone in the second round of 64 ops
+    if name == "leading_overhang":
+        assert ops > 64 and parsed[0] == (b"I", 3)
+    # the table: that one count, at that position, and on both strands the same
+    case = R.pairs_case([(q, t, 0)])
+    records, _, planes = P.model("ins_" + name, case, sc, mode)
+    assert sum(planes[P.INS]) == 1 and planes[P.INS][position] == 1 and P.identities(planes, records) == []
+    back = P.reverse_given(q)
+    rec2, texts2, planes2 = P.model("rev_ins_" + name, R.pairs_case([(back, t, 1)]), sc, mode)
+    assert texts2 == texts and planes2 == planes and P.identities(planes2, rec2) == []
+    assert int(rec2["q_start"][0]) == len(q) - int(records["q_end"][0]) and int(rec2["q_end"][0]) == len(q) - int(records["q_start"][0])
+
+
+def test_ins_pairs_cover_the_indices_at_the_round_edges():
+    have = {(forms[mode][1], forms[mode][0]) for _, forms in P.INS_PAIRS.values() for mode in forms}
+    assert {i for i, _ in have} >= {1, 63, 64, 65, 127, 128} and {(63, 65), (64, 66), (127, 129), (131, 133)} <= have
+    for mode in M.MODES:                                                 # ... each index under both forms (127 of 129 ops: read mode alone)
+        mine = {forms[mode][1] for name, (_, forms) in P.INS_PAIRS.items() if mode in forms and name.startswith("index")}
+        assert mine >= {1, 63, 64, 65, 127, 128, 131}
+
+
+@pytest.mark.parametrize("name", sorted(P.op_count_pairs()))
+def test_op_count_pairs_on_the_reverse_strand_give_the_forward_table(name):
+    sc, mode, ops, q, t = P.op_count_pairs()[name]
+    _, texts, planes = P.model("ops_" + name, R.pairs_case([(q, t, 0)]), sc, mode)
+    rec2, texts2, planes2 = P.model("rev_ops_" + name, R.pairs_case([(P.reverse_given(q), t, 1)]), sc, mode)
+    assert texts2 == texts and planes2 == planes and P.identities(planes2, rec2) == [] and b"T" not in P.reverse_given(q)
+
+
+def test_gap_contention_case_spans_both_gaps_on_both_strands():
+    q, t = P.gap_contention_pair()
+    case = P.gap_contention_case()
+    assert (len(q), len(t)) == (100, 101) and len(case[1]) == P.GAP_COPIES and sum(case[3]) == P.GAP_COPIES // 2
+    assert set(case[1]) == {q, P.reverse_given(q)} and case[1][0] == q and case[3][:2] == [0, 1]
+    for rev, given in ((0, q), (1, P.reverse_given(q))):
+        assert M.pair(given, t, rev, P.ENGINE, M.LOCAL)[1] == [("=", 35), ("D", 3), ("=", 32), ("I", 2), ("=", 31)]
+    small = [t], case[1][:2], [0, 0], [0, 1]
+    records, texts, planes = P.model("gap_contention_2", small, P.ENGINE, M.LOCAL)
+    assert texts == [P.GAP_CONTENTION_CIGAR] * 2 and P.identities(planes, records) == []
+    assert sparse(planes)["del"] == {35: 2, 36: 2, 37: 2} and sparse(planes)["ins"] == {70: 2}
+    assert sparse(planes)["starts"] == {0: 2} and sparse(planes)["ends"] == {100: 2} and set(P.depth(planes)) == {2}
+
+
 def test_constructed_cases_sit_on_their_edges():
     # identical: one '=' run each, of the named lengths
     case = P.identical_case()
